@@ -24,6 +24,10 @@ MFMA-only stream sustains on EVERY rank's GPU while all of them run it at once (
 power budget, so the clocks differ from a one-GPU box), and -- measured by rank 0 after the timed region while the other ranks wait at a
 host-side (gloo) barrier -- `cpu_baseline`, `train_step` and `roofline.gemm_ref` exactly as in the N = 1 line.
 
+A plain run measures the headline only: set-up, warm-up, the `--steps` timed steps, the line.  `--full` adds what is measured after the
+timed region in runs of its own -- `cpu_baseline`, `train_step`, `roofline.mfma_stream_ref`, `roofline.gemm_ref` -- and `--dump-outputs DIR`
+writes what the last timed step computed (dump_outputs) for an output-by-output comparison of two builds.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -90,7 +94,16 @@ def parse():
     p.add_argument("--dump-image", default=None, help="render-strong: rank 0 saves the last timed image (N,4) to this path (N-independence tests)")
     p.add_argument("--launch-check", action="store_true",
                    help="control-flow check of the N-rank launch path only (rendezvous, world size, barrier, max-over-ranks): no GPU work")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="after the timed region also measure what the headline figure does not need: cpu_baseline, train_step and the "
+                        "MFMA-stream / hipBLASLt ceilings (roofline.mfma_stream_ref, roofline.gemm_ref); a plain run leaves them out")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="write what the timed path computed in its last timed step to DIR/<name>.npy (float32; a fixed, seeded row sample "
+                        "of the per-sample weights), for output-by-output comparison of two builds")
+    a = p.parse_args()
+    if not a.full:                                           # the extra legs run only on request (--no-* still turns one off under --full)
+        a.no_cpu_baseline = a.no_train_rate = a.no_gemm_ref = True
+    return a
 
 
 def committed_traffic(key: str):
@@ -577,6 +590,34 @@ def mfma_stream_reference(comm, dev, achieved_tflops, executed_tflops):
                     "(the ceiling a kernel multiplying real data can be held against); 64 MFMAs per iteration and wave, 40 ms per stream"}
 
 
+DUMP_WHOLE_MAX = 4 << 20           # --dump-outputs: an output of more elements than this is stored as a row sample ...
+DUMP_SAMPLE_ROWS = 32768           # ... of this many rows
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the arrays the timed path handed its caller in its last timed step, written as <dirname>/<name>.npy in float32.
+    An array of more than DUMP_WHOLE_MAX elements (the per-sample weights of a full image) is stored as `<name>_sample`: DUMP_SAMPLE_ROWS of
+    its rows, drawn without replacement by numpy's default_rng(0) and kept in ascending order -- the same rows in every run, so that two
+    builds compare output for output and the whole dump stays under 64 MB."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total, files = 0, {}
+    for name, t in arrays.items():
+        if t is None:
+            continue
+        t = t.detach()
+        if t.numel() > DUMP_WHOLE_MAX:
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], size=min(DUMP_SAMPLE_ROWS, t.shape[0]), replace=False))
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+            name += "_sample"
+        arr = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+        total += arr.nbytes
+        assert total <= 64 * 10 ** 6, "bench.py --dump-outputs: %d bytes, more than 64 MB" % total
+        np.save(os.path.join(dirname, name + ".npy"), arr)
+        files[name] = list(arr.shape)
+    sys.stderr.write("bench.py: the last timed step's outputs written to %s: %s\n" % (dirname, json.dumps(files)))
+
+
 def _spread(xs):
     xs = sorted(xs)
     return {"min": xs[0], "median": statistics.median(xs), "max": xs[-1], "n": len(xs)}
@@ -880,6 +921,10 @@ def train_ddp(a, comm):
     spread = rank_spread(comm, local_dt, a.steps)
     ar_ms = [s_.elapsed_time(e_) for s_, e_ in ev] if graph is None else None
     ar_ranks = comm.gather((sum(ar_ms) / a.steps * 1e3) if ar_ms else None)
+    if a.dump_outputs and rank == 0:                                     # what a training step leaves its caller: the updated weights
+        dump_outputs(a.dump_outputs, {"mip_params": torch.cat([q.detach().reshape(-1) for q in mip.parameters()]),
+                                      "prop_params": torch.cat([q.detach().reshape(-1) for q in prop.parameters()]),
+                                      "grad_flat": flat.flat})
     flop_per_ray = 3 * FLOP_PER_RAY                                      # forward + dgrad + wgrad
     if is_ref:                                                           # 64 proposal + (128 + 64 merged) Ref-NeRF samples; the two density-gradient chains not counted
         flop_per_ray = 3 * 2 * (C_COARSE * MAC_PROP + (N_FINE + C_COARSE) * 1_071_616)
@@ -969,6 +1014,8 @@ def render_strong(a, comm):
     assert img.shape == (n, 4) and bool(torch.isfinite(img).all())
     if a.dump_image and rank == 0:                          # the LAST timed image (every rank holds the same one): N-independence checks
         torch.save(img.cpu(), a.dump_image)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"rgb": img[:, :3], "depth": img[:, 3]})
     achieved = a.steps * n * FLOP_PER_RAY / dt / 1e12 / world          # per GPU
     rec = None
     if rank == 0:
@@ -1139,6 +1186,8 @@ def main():
     dt = comm.max_over_ranks(local_dt)
     spread = rank_spread(comm, local_dt, a.steps)
     assert os.environ.get("NERF_AMD_LIB") or bool(torch.isfinite(out[0]).all())     # (ablation builds compute garbage)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"rgb": out[0], "depth": out[1], "weights": out[2]})
 
     fine_ms = sum(s.elapsed_time(e) for s, e in ev) / a.steps
     fine_ms_ranks = comm.gather(fine_ms)

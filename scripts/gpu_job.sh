@@ -20,13 +20,13 @@ while [ $# -gt 0 ]; do
   case $job in
     tests)    timeout ${TESTS_TIMEOUT:-3000} python -m pytest tests -m gpu -q -x --durations=15 "${args[@]}" > $OUT/tests.log 2>&1; echo "rc=$?" >> $OUT/tests.log; tail -5 $OUT/tests.log ;;
     bench)    python bench.py "${args[@]}" > $OUT/bench_default.json 2> $OUT/bench_default.err; tail -c 1500 $OUT/bench_default.json ;;
-    benchall) python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+    benchall) python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
               python bench.py --model ref --no-cpu-baseline --no-gemm-ref > $OUT/bench_refnerf.json 2>/dev/null
               python bench.py --precision fp32 --steps 3 --warmup 1 --no-cpu-baseline --no-gemm-ref --no-train-rate > $OUT/bench_fp32.json 2>/dev/null
-              python bench.py --mode render-strong --steps 10 --warmup 3 > $OUT/bench_render_strong.json 2>/dev/null
-              for f in "" "--ipe" "--contract" "--hipgraph" "--train-dumps fp8"; do python bench.py --mode train-ddp --steps 20 --warmup 5 --no-cpu-baseline $f 2>/dev/null | tail -1; done > $OUT/bench_train_variants.jsonl
-              python bench.py --mode train-ddp --steps 50 --warmup 5 --train-rays 512 --hipgraph --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT/bench_train_variants.jsonl
-              python bench.py --mode train-ddp --model ref --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT/bench_train_variants.jsonl
+              python bench.py --mode render-strong --steps 10 --warmup 3 --full > $OUT/bench_render_strong.json 2>/dev/null
+              for f in "" "--ipe" "--contract" "--hipgraph" "--train-dumps fp8"; do python bench.py --mode train-ddp --steps 20 --warmup 5 --full --no-cpu-baseline $f 2>/dev/null | tail -1; done > $OUT/bench_train_variants.jsonl
+              python bench.py --mode train-ddp --steps 50 --warmup 5 --train-rays 512 --hipgraph --full --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT/bench_train_variants.jsonl
+              python bench.py --mode train-ddp --model ref --steps 10 --warmup 3 --full --no-cpu-baseline 2>/dev/null | tail -1 >> $OUT/bench_train_variants.jsonl
               tail -c 600 $OUT/bench_default.json ;;
     profile)  bash scripts/gpu_round_profile.sh > $OUT/round_profile.log 2>&1; tail -3 $OUT/round_profile.log ;;
     trainprof) PMC=${PMC:-1} bash scripts/gpu_train_profile.sh "${args[@]}" > $OUT/train_profile.log 2>&1; tail -3 $OUT/train_profile.log ;;

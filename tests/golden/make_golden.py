@@ -95,6 +95,35 @@ def write_entry_imports():
     print("wrote g23_entry_imports.json (%d names)" % sum(len(v) for s in rec.values() for v in s.values()))
 
 
+def checkpoint_pattern(i, shape):
+    """the values of the i-th tensor of a G25 checkpoint: a period-97 ramp shifted per tensor (distinct tensors, a file that gzips small)"""
+    n = math.prod(shape)
+    return ((torch.arange(n) % 97).float() * 2.0 ** -7 - 0.375 + i * 2.0 ** -10).reshape(shape)
+
+
+def write_checkpoint_abi():
+    """G25: checkpoints written by the REAL reference's saveModel (nerf_helper.py:7-15) -- MipNeRF(10, 4, 256) with its Adam state and two
+    extra entries, ProposalNetwork(10, 256) bare -- gzipped.  The parameters hold checkpoint_pattern(i) instead of a random init: the files
+    are the reference's on-disk format (pickle layout, key names and order, optimizer state), the values only have to be told apart."""
+    import gzip
+    import tempfile
+    from nerf import mip_model, addtional, nerf_helper
+    r_mip, r_prop = mip_model.MipNeRF(10, 4, 256), addtional.ProposalNetwork(10, 256)
+    for net in (r_mip, r_prop):
+        with torch.no_grad():
+            for i, v in enumerate(net.state_dict().values()):
+                v.copy_(checkpoint_pattern(i, tuple(v.shape)))
+    opt = torch.optim.Adam(list(r_mip.parameters()), lr=1e-3)
+    for name, args in (("g25_ckpt_mip", (r_mip, {"train_cnt": 123, "epoch": 4}, opt)), ("g25_ckpt_prop", (r_prop,))):
+        with tempfile.TemporaryDirectory() as tmp:
+            nerf_helper.saveModel(args[0], os.path.join(tmp, "ckpt.pt"), *args[1:])
+            raw = open(os.path.join(tmp, "ckpt.pt"), "rb").read()
+        path = os.path.join(HERE, name + ".pt.gz")
+        with gzip.GzipFile(path, "wb", mtime=0) as f:
+            f.write(raw)
+        print("wrote %-28s %7.1f KB" % (name + ".pt.gz", os.path.getsize(path) / 1024))
+
+
 def write_config0_train_step():
     """G24: BASELINE configs[0] at ITS shape -- one training iteration of train.py:151-218 (non-ref) on a 200 x 200 image, 256 rays, 32 + 64
     samples, run by the REAL reference: randomFromOneImage -> validSampler -> ProposalNetwork -> get_weights -> maxBlurFilter ->
@@ -216,6 +245,8 @@ def main():
         return write_shallow_encodings()
     if "--generic-ref-only" in sys.argv:
         return write_generic_refnerf()
+    if "--checkpoint-only" in sys.argv:
+        return write_checkpoint_abi()
     from nerf import nerf_helper, nerf_base, mip_methods, mip_model, addtional, utils, procedures
     import weights as W
 
@@ -552,6 +583,7 @@ def main():
     write_entry_imports()
     write_signatures()
     write_config0_train_step()
+    write_checkpoint_abi()
 
 
 if __name__ == "__main__":

@@ -169,53 +169,61 @@ def test_ipe_is_a_hip_entry_point_without_cpu_path(golden):
         coneParameters(g["z"], 0.0015)
 
 
-def test_checkpoint_roundtrip_with_reference_modules(tmp_path):
-    """Checkpoint ABI: a file written by the reference's saveModel loads into the nerf_amd modules and
-    back.  Needs the reference checkout (build container only); skipped where /root/reference is absent (GPU box)."""
-    import importlib
-    import sys
-    if not os.path.isdir("/root/reference/nerf"):
-        pytest.skip("reference checkout not present")
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    import make_golden
-    saved_cuda = (torch.Tensor.cuda, torch.nn.Module.cuda)
-    make_golden.install_shims()
-    try:
-        ref_mip = importlib.import_module("nerf.mip_model")
-        ref_add = importlib.import_module("nerf.addtional")
-        ref_helper = importlib.import_module("nerf.nerf_helper")
-        from nerf_amd.addtional import ProposalNetwork
-        from nerf_amd.mip_model import MipNeRF
-        from nerf_amd.nerf_helper import saveModel
-        torch.manual_seed(0)
-        r_mip, r_prop = ref_mip.MipNeRF(10, 4, 256), ref_add.ProposalNetwork(10, 256)
-        opt = torch.optim.Adam(list(r_mip.parameters()), lr=1e-3)
-        ref_helper.saveModel(r_mip, str(tmp_path / "a_mip.pt"), {"train_cnt": 123, "epoch": 4}, opt=opt)
-        ref_helper.saveModel(r_prop, str(tmp_path / "a_prop.pt"))
-        mine_mip, mine_prop = MipNeRF(10, 4, 256), ProposalNetwork(10, 256)
-        opt2 = torch.optim.Adam(list(mine_mip.parameters()), lr=1e-3)
-        assert mine_mip.loadFromFile(str(tmp_path / "a_mip.pt"), False, opt2, ["train_cnt", "epoch"]) == [123, 4]
-        mine_prop.loadFromFile(str(tmp_path / "a_prop.pt"))
-        for k, v in r_mip.state_dict().items():
-            assert torch.equal(v, mine_mip.state_dict()[k])
-        for k, v in r_prop.state_dict().items():
-            assert torch.equal(v, mine_prop.state_dict()[k])
-        # and back: DDP-style "module." prefixes are stripped on load (nerf_base.py:34-38)
-        sd = {"module." + k: v for k, v in mine_mip.state_dict().items()}
-        torch.save({"model": sd}, str(tmp_path / "b_mip.pt"))
-        r2 = ref_mip.MipNeRF(10, 4, 256)
-        r2.loadFromFile(str(tmp_path / "b_mip.pt"))
-        assert all(torch.equal(v, r2.state_dict()[k]) for k, v in mine_mip.state_dict().items())
-        saveModel(mine_prop, str(tmp_path / "c_prop.pt"))
-        r3 = ref_add.ProposalNetwork(10, 256)
-        r3.loadFromFile(str(tmp_path / "c_prop.pt"))
-        assert all(torch.equal(v, r3.state_dict()[k]) for k, v in mine_prop.state_dict().items())
-    finally:
-        torch.Tensor.cuda, torch.nn.Module.cuda = saved_cuda
-        for m in [k for k in sys.modules if k == "nerf" or k.startswith("nerf.")]:
-            del sys.modules[m]
-        if "/root/reference" in sys.path:
-            sys.path.remove("/root/reference")
+def _reference_load(path, keys_shapes):
+    """What the reference's NeRF.loadFromFile (nerf_base.py:30-42) does with a checkpoint, restated for the checks below: read
+    save['model'], strip DDP's "module." prefix, pick the module's own state_dict keys in order -> [(key, tensor)] (KeyError / shape
+    mismatch = the reference module could not load the file)."""
+    save = torch.load(path, map_location="cpu")
+    stripped = {(k[7:] if k.startswith("module") else k): v for k, v in save["model"].items()}
+    out = [(k, stripped[k]) for k, _ in keys_shapes]
+    assert [tuple(v.shape) for _, v in out] == [tuple(s) for _, s in keys_shapes]
+    return save, out
+
+
+def test_checkpoint_roundtrip_with_reference_modules(tmp_path, golden):
+    """Checkpoint ABI: a file written by the reference's saveModel (golden G25: MipNeRF with Adam state and
+    extra entries, ProposalNetwork bare -- written by tests/golden/make_golden.py from the real reference) loads into the nerf_amd
+    modules, and the files nerf_amd writes have the reference's layout and load the way the reference's loadFromFile reads them (module
+    keys and shapes: golden G16)."""
+    import gzip
+    from nerf_amd.addtional import ProposalNetwork
+    from nerf_amd.mip_model import MipNeRF
+    from nerf_amd.nerf_helper import saveModel
+    g16 = golden("g16_state_dict_abi")
+    ref_files = {}
+    for name in ("mip", "prop"):
+        ref_files[name] = str(tmp_path / ("a_%s.pt" % name))
+        with gzip.open(os.path.join(ROOT, "tests", "golden", "g25_ckpt_%s.pt.gz" % name)) as f, open(ref_files[name], "wb") as o:
+            o.write(f.read())
+    ref_mip, ref_prop = (torch.load(ref_files[n], map_location="cpu") for n in ("mip", "prop"))
+    assert list(ref_mip["model"].keys()) == [k for k, _ in g16["mip"]] and list(ref_prop["model"].keys()) == [k for k, _ in g16["prop"]]
+    mine_mip, mine_prop = MipNeRF(10, 4, 256), ProposalNetwork(10, 256)
+    opt2 = torch.optim.Adam(list(mine_mip.parameters()), lr=1e-3)
+    assert mine_mip.loadFromFile(ref_files["mip"], False, opt2, ["train_cnt", "epoch"]) == [123, 4]
+    mine_prop.loadFromFile(ref_files["prop"])
+    for k, v in ref_mip["model"].items():
+        assert torch.equal(v, mine_mip.state_dict()[k])
+    for k, v in ref_prop["model"].items():
+        assert torch.equal(v, mine_prop.state_dict()[k])
+    assert opt2.state_dict() == ref_mip["optimizer"]
+    # and back: the same modules saved by nerf_amd's saveModel -> a file of the reference's layout, entry for entry ...
+    saveModel(mine_mip, str(tmp_path / "c_mip.pt"), {"train_cnt": 123, "epoch": 4}, opt=opt2)
+    saveModel(mine_prop, str(tmp_path / "c_prop.pt"))
+    for name, ref in (("mip", ref_mip), ("prop", ref_prop)):
+        mine = torch.load(str(tmp_path / ("c_%s.pt" % name)), map_location="cpu")
+        assert list(mine.keys()) == list(ref.keys()) and list(mine["model"].keys()) == list(ref["model"].keys())
+        assert all(torch.equal(v, ref["model"][k]) for k, v in mine["model"].items())
+        assert {k: v for k, v in mine.items() if k != "model"} == {k: v for k, v in ref.items() if k != "model"}
+        # ... which the reference's loader reads back, and so does a DDP-style "module." prefixed one (nerf_base.py:34-38)
+        _, got = _reference_load(str(tmp_path / ("c_%s.pt" % name)), g16[name])
+        assert all(torch.equal(v, ref["model"][k]) for k, v in got)
+    sd = {"module." + k: v for k, v in mine_mip.state_dict().items()}
+    torch.save({"model": sd}, str(tmp_path / "b_mip.pt"))
+    _, got = _reference_load(str(tmp_path / "b_mip.pt"), g16["mip"])
+    assert all(torch.equal(v, mine_mip.state_dict()[k]) for k, v in got)
+    m2 = MipNeRF(10, 4, 256)
+    m2.loadFromFile(str(tmp_path / "b_mip.pt"))
+    assert all(torch.equal(v, m2.state_dict()[k]) for k, v in mine_mip.state_dict().items())
 
 
 def test_coarse_grad_select_without_mask_gather():

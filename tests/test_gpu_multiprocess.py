@@ -593,7 +593,7 @@ def test_train_step_losses_equal_the_oracles_step_on_the_same_draws(branch):
 
 # ------------------------------------------------------------------------------------------------ bench.py's real N > 1 path on the box
 def _bench_line(tmp_path, tag, *args, gpus=1):
-    """Run bench.py as the driver does (stand-alone for N = 1; for N = 2 it re-executes itself under torch.distributed.run) with the gloo
+    """Run bench.py --full (every leg of the line) as the driver does (stand-alone for N = 1; for N = 2 it re-executes itself under torch.distributed.run) with the gloo
     control-flow backend -- two ranks on the box's one GPU, which RCCL refuses -- and return the parsed JSON line."""
     import json
     import subprocess
@@ -601,7 +601,7 @@ def _bench_line(tmp_path, tag, *args, gpus=1):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
         e.pop(k, None)
     e.update(BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--cpu-rays", "2500"] + list(args)
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--full", "--cpu-rays", "2500"] + list(args)
     r = subprocess.run(cmd, capture_output=True, text=True, env=e, timeout=900)
     assert r.returncode == 0, (tag, r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -667,3 +667,37 @@ def test_bench_n_gt_1_path_runs_on_the_box_and_its_line_is_self_contained(mode, 
     if mode == "render-strong":
         a, b = torch.load(img[1]), torch.load(img[2])
         assert a.shape == (800 * 800, 4) and torch.equal(a, b)              # N = 2 == N = 1, bit for bit
+
+
+@pytest.mark.timeout(900)
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` measures the headline only (no cpu_baseline / train_step / MFMA-stream or GEMM
+    ceilings: those are --full's), times exactly K steps, and with --dump-outputs DIR writes the last timed step's rgb, depth and a fixed
+    row sample of the weights as float32 .npy files, under 64 MB in all."""
+    import json
+    import subprocess
+    import numpy as np
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    e = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT"):
+        e.pop(k, None)
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, env=e, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    rec = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in rec, k
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["value"] > 0 and rec["ms_per_step"] > 0 and rec["dtype"] == "bf16"
+    assert abs(rec["value"] * rec["ms_per_step"] * 1e-3 - 800 * 800) <= 1e-6 * 800 * 800        # value = rays of one step / its time
+    assert "cpu_baseline" not in rec and "train_step" not in rec
+    assert "mfma_stream_ref" not in rec["roofline"] and "gemm_ref" not in rec["roofline"]
+    got = {f: np.load(str(out / f)) for f in sorted(os.listdir(str(out)))}
+    assert set(got) == {"rgb.npy", "depth.npy", "weights_sample.npy"}, sorted(got)
+    assert got["rgb.npy"].shape == (800 * 800, 3) and got["depth.npy"].shape == (800 * 800,) and got["weights_sample.npy"].shape == (32768, 128)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert sum(os.path.getsize(str(out / f)) for f in got) <= 64 * 10 ** 6
+    assert -1e-4 <= got["rgb.npy"].min() and got["rgb.npy"].max() <= 1.0 + 1e-4
