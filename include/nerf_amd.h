@@ -298,6 +298,22 @@ int nerf_amd_weighted_dot_loss(const float* w, const float* a, const float* b, i
 int nerf_amd_weighted_dot_loss_backward(const float* g, const float* w, const float* a, const float* b, int64_t M, int mode, float scale, float* d_w,
                                         float* d_a, float* d_b, void* stream);
 
+/* Distortion regularisers, one wavefront per ray (the row staged in LDS in fp32, pair sums in fp64) + a fixed-order two-stage sum
+ * (deterministic; no host synchronisation, so capturable).  t (N, S) fp32 contiguous, 2 <= S <= NERF_AMD_DISTORTION_MAX_S depths per row:
+ *   mode 0  Regularizer (addtional.py:26-35): w (N, S), rows in any order, M = S - 1 intervals with c_i = (t_i + t_i+1) / 2,
+ *           a_i = (w_i + w_i+1) / 2, d_i = t_i+1 - t_i, r_i = sqrt(sum_j (c_i - c_j)^2):
+ *           out[0] = scale * ( sum_n sum_ij a_i a_j |c_i - c_j| / r_i / (N M^2)  +  sum_n sum_i d_i a_i^2 / (3 N M) )
+ *           -- the reference's two means; a row whose centres coincide (S = 2 among them) gives 0/0 = NaN, as the reference does.
+ *   mode 1  Mip-NeRF 360 L_dist (Barron et al. 2022, eq. 15): w (N, S - 1), t = the S sorted interval edges, m_i = interval midpoints:
+ *           out[0] = scale / N * sum_n ( sum_ij w_i w_j |m_i - m_j|  +  sum_i w_i^2 (t_i+1 - t_i) / 3 )
+ * workspace: NERF_AMD_DISTORTION_WORKSPACE_FLOATS floats.  Backward: g = d loss / d out (ONE float in device memory) -> d_w (the shape of w),
+ * d_t (N, S); either may be NULL (not computed).  sgn(0) = 0 in the gradient of |x|, as torch. */
+#define NERF_AMD_DISTORTION_MAX_S 1024
+#define NERF_AMD_DISTORTION_WORKSPACE_FLOATS 4096
+int nerf_amd_distortion_loss(const float* w, const float* t, int64_t N, int S, int mode, float scale, float* out, float* workspace, void* stream);
+int nerf_amd_distortion_loss_backward(const float* w, const float* t, int64_t N, int S, int mode, float scale, const float* g, float* d_w,
+                                      float* d_t, void* stream);
+
 /* Measurement aid, no reference counterpart (the roofline's denominator checked on the box): `workgroups` workgroups of four
  * waves (one per SIMD; 160 KiB of LDS each, so one workgroup per CU) issue iters * 64 v_mfma_f32_32x32x16_bf16 per wave and nothing else;
  * timed by the caller, 32 768 flop per MFMA and wave.  mode 0: constant operands (optimistic: the datapath does not toggle); 1: a rotating

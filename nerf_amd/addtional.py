@@ -23,6 +23,55 @@ class ProposalLoss(nn.Module):
         return torch.sum(F.relu(nerf_weights - prop_bounds) ** 2 / (nerf_weights + 1e-8))
 
 
+def _distortion(weights: torch.Tensor, t: torch.Tensor, mode: int, scale: float, expr) -> torch.Tensor:
+    """scale * distortion loss on the device: one wavefront per ray + a fixed-order sum forward, one kernel backward
+    (nerf_amd_distortion_loss[_backward]); `expr` = the torch expression, the specification (and what CPU tensors evaluate)."""
+    if not weights.is_cuda:
+        return expr(weights, t) * scale
+    if t.shape[-1] > ops.BWD_MAX_SAMPLES:
+        ab.unsupported("a distortion loss over rows of %d depths (the kernels stage a ray in LDS: <= %d)" % (t.shape[-1], ops.BWD_MAX_SAMPLES))
+    if not ab.needs_grad(weights, t):
+        return ops.distortion_loss(weights, t, mode, scale)
+    need = (weights.requires_grad, t.requires_grad)
+    return ab.HipOp.apply(lambda w_, t_: ops.distortion_loss(w_, t_, mode, scale),
+                          lambda g, w_, t_: ops.distortion_loss_backward(g, w_, t_, mode, scale, need), 1, weights, t)
+
+
+class Regularizer(nn.Module):
+    def __init__(self) -> None:
+        super().__init__()
+
+    def forward(self, weights: torch.Tensor, fine_ts: torch.Tensor):
+        """mean_ij a_i a_j |c_i - c_j| / r_i + mean_i delta_i a_i^2 / 3 over the 2-tap averages a of the weights and the centres c of
+        consecutive depths, r_i = || c_i - c ||  (addtional.py:26-35): weights, fine_ts (N, S), rows in any order.  Rows whose centres
+        coincide (S = 2 among them) give NaN, like the reference."""
+        def expr(weights, fine_ts):
+            center = (fine_ts[..., :-1] + fine_ts[..., 1:]) / 2.
+            dists = torch.abs(center[:, None, :] - center[..., None])
+            dists = dists / dists.norm(dim=-1, keepdim=True)
+            avg_weights = (weights[..., :-1] + weights[..., 1:]) / 2.
+            delta = fine_ts[..., 1:] - fine_ts[..., :-1]
+            return torch.mean(avg_weights[:, None, :] * avg_weights[..., None] * dists) + torch.mean(delta * (avg_weights ** 2)) / 3.
+        return _distortion(weights, fine_ts, 0, 1.0, expr)
+
+
+class DistortionLoss(nn.Module):
+    """Mip-NeRF 360's distortion loss L_dist (Barron et al. 2022, eq. 15), not in the reference: for weights w (N, M) of the M intervals
+    between sorted edges e (N, M+1) with midpoints m,  scale * mean_rays [ sum_ij w_i w_j |m_i - m_j| + sum_i w_i^2 (e_i+1 - e_i) / 3 ].
+    L_dist is 1-homogeneous in the edges: the loss in normalised coordinates s = (e - near) / (far - near) is scale = 1 / (far - near)."""
+
+    def __init__(self, scale: float = 1.0) -> None:
+        super().__init__()
+        self.scale = float(scale)
+
+    def forward(self, weights: torch.Tensor, edges: torch.Tensor) -> torch.Tensor:
+        def expr(w, e):
+            mid = (e[..., :-1] + e[..., 1:]) / 2.
+            pair = (w[..., :, None] * w[..., None, :] * torch.abs(mid[..., :, None] - mid[..., None, :])).sum((-2, -1))
+            return torch.mean(pair + (w * w * (e[..., 1:] - e[..., :-1])).sum(-1) / 3.)
+        return _distortion(weights, edges, 1, self.scale, expr)
+
+
 class SoftL1Loss(nn.Module):
     def __init__(self, epsilon=0.001) -> None:
         super().__init__()

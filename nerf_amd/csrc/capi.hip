@@ -25,6 +25,8 @@ int sk_coarse_grad_select(const float*, const int64_t*, int64_t, int, int, int, 
 int pack_mfma_stream(int, int, int, float*, hipStream_t);
 int sk_weighted_dot_loss(const float*, const float*, const float*, int64_t, int, float, float*, float*, hipStream_t);
 int sk_weighted_dot_loss_backward(const float*, const float*, const float*, const float*, int64_t, int, float, float*, float*, float*, hipStream_t);
+int sk_distortion_loss(const float*, const float*, int64_t, int, int, float, float*, float*, hipStream_t);
+int sk_distortion_loss_backward(const float*, const float*, int64_t, int, int, float, const float*, float*, float*, hipStream_t);
 int sk_encode_rows(const float*, int, int64_t, int, int, int, void*, hipStream_t);
 int sk_frag_rows_mask_blocks();
 int sk_frag_rows_mask(const void*, int, int64_t, int, int64_t, void*, void*, float*, hipStream_t);
@@ -128,6 +130,12 @@ int check_samples(const nerf_amd_samples* s, bool need_dir) {
     return NERF_AMD_OK;
 }
 bool bad_prec(int p) { return p != NERF_AMD_F32 && p != NERF_AMD_BF16; }
+int check_distortion(int64_t N, int Sn, int mode) {
+    if (N < 0) return fail(NERF_AMD_EINVAL, "negative ray count");
+    if (mode != 0 && mode != 1) return fail(NERF_AMD_EINVAL, "unknown mode (0: Regularizer, 1: Mip-NeRF 360 L_dist)");
+    if (Sn < 2 || Sn > NERF_AMD_DISTORTION_MAX_S) return fail(NERF_AMD_EINVAL, "bad size (S must be 2..1024 depths per row: a ray's rows live in LDS)");
+    return NERF_AMD_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -411,6 +419,19 @@ int nerf_amd_weighted_dot_loss_backward(const float* g, const float* w, const fl
     if (M < 0 || (mode != 0 && mode != 1)) return fail(NERF_AMD_EINVAL, "bad size / mode");
     if (M && (!g || !w || !a || !b)) return fail(NERF_AMD_EINVAL, "NULL argument");
     return hip_status(sk_weighted_dot_loss_backward(g, w, a, b, M, mode, scale, d_w, d_a, d_b, S(stream)), "nerf_amd_weighted_dot_loss_backward");
+}
+
+int nerf_amd_distortion_loss(const float* w, const float* t, int64_t N, int Sn, int mode, float scale, float* out, float* workspace, void* stream) {
+    if (int e = check_distortion(N, Sn, mode)) return e;
+    if (!out || !workspace || (N && (!w || !t))) return fail(NERF_AMD_EINVAL, "NULL argument");
+    return hip_status(sk_distortion_loss(w, t, N, Sn, mode, scale, out, workspace, S(stream)), "nerf_amd_distortion_loss");
+}
+
+int nerf_amd_distortion_loss_backward(const float* w, const float* t, int64_t N, int Sn, int mode, float scale, const float* g, float* d_w, float* d_t,
+                                      void* stream) {
+    if (int e = check_distortion(N, Sn, mode)) return e;
+    if (N && (!w || !t || !g)) return fail(NERF_AMD_EINVAL, "NULL argument");
+    return hip_status(sk_distortion_loss_backward(w, t, N, Sn, mode, scale, g, d_w, d_t, S(stream)), "nerf_amd_distortion_loss_backward");
 }
 
 int nerf_amd_mfma_stream(int iters, int workgroups, int mode, float* sink, void* stream) {

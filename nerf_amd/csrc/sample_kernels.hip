@@ -1318,6 +1318,240 @@ __global__ void weighted_dot_loss_backward_kernel(const float* __restrict__ g, c
     }
 }
 
+// ---------------------------------------------------------------------------------------- distortion regularisers (include/nerf_amd.h)
+// Per ray M = S - 1 intervals with centres c_i, weights a_i and widths d_i = t_i+1 - t_i:
+//   mode 0  Regularizer (addtional.py:26-35): c = (t_i + t_i+1) / 2, a = (w_i + w_i+1) / 2, r_i = sqrt(sum_j (c_i - c_j)^2)
+//   mode 1  Mip-NeRF 360 L_dist:              c = (e_i + e_i+1) / 2, a = w_i,               r_i = 1
+//   P = sum_ij a_i a_j |c_i - c_j| / r_i,  Q = sum_i d_i a_i^2;  the mode's normalisation (dist_coeffs) turns sum P, sum Q into the loss.
+// One wavefront per ray: the row's (c, a) pairs staged in LDS in fp32 (any order: nothing assumes sorted depths), each lane owns DIST_R
+// intervals and walks every j with broadcast LDS reads, the pair sums in fp64.  The reference's expression materialises (N, M, M) tensors.
+// Backward (s_kj = sgn(c_k - c_j), sgn(0) = 0; u = a / r, q = a D / r^3, D_k = sum_j a_j |c_k - c_j|):
+//   dP/da_k = D_k / r_k + sum_i u_i |c_i - c_k|,   dP/dc_k = u_k sum_j a_j s_kj + a_k sum_i u_i s_ki - q_k sum_j (c_k - c_j) - sum_i q_i (c_k - c_i)
+//   dQ/da_k = 2 d_k a_k,  dQ/dd_k = a_k^2;  then the 2-tap averages / differences scatter to columns k and k + 1 of w and t.
+// Mode 0 needs u and q of every interval: a first pass stores them next to (c, a) in fp64 -- the depth gradient's four terms cancel where
+// centres come close (exactly with two intervals, where P is constant in t), and fp32 rows of u, q left ~1e-7 / |c_i - c_j| of its largest
+// entry --, 24 bytes per interval; mode 1 (r = 1, q = 0) is one pass over fp32 (c, a).
+constexpr int DIST_R = 2;
+constexpr int DIST_BLOCKS = 1024;                    // forward grid cap: the workspace's (P, Q) partial pairs (NERF_AMD_DISTORTION_WORKSPACE_FLOATS / 4)
+DEVINL void dist_coeffs(int mode, int64_t N, int M, double& cP, double& cQ) {
+    if (mode == 0) { cP = 1.0 / ((double)N * M * M); cQ = 1.0 / (3.0 * N * M); }     // torch.mean over (N, M, M) and over (N, M), / 3
+    else { cP = 1.0 / (double)N; cQ = 1.0 / (3.0 * N); }
+}
+// row[W i] = c_i, row[W i + 1] = a_i for the M intervals of ray n
+template <int MODE, int W>
+DEVINL void dist_stage(const float* __restrict__ w, const float* __restrict__ t, int64_t n, int S, float* row) {
+    const int M = S - 1;
+    const float* tn = t + n * S;
+    const float* wn = w + n * (MODE == 0 ? S : M);
+    for (int i = lane_id(); i < M; i += 64) {
+        row[W * i] = (tn[i] + tn[i + 1]) / 2.0f;
+        row[W * i + 1] = MODE == 0 ? (wn[i] + wn[i + 1]) / 2.0f : wn[i];
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void distortion_loss_kernel(const float* __restrict__ w, const float* __restrict__ t, int64_t N, int S,
+                                                              double* __restrict__ partial) {
+    const int M = S - 1, lane = lane_id();
+    float* row = reinterpret_cast<float*>(smem) + (size_t)wave_in_block() * 2 * M;
+    double accP = 0.0, accQ = 0.0;
+    for (int64_t n = blockIdx.x * (int64_t)WAVES_PER_BLOCK + wave_in_block(); n < N; n += (int64_t)gridDim.x * WAVES_PER_BLOCK) {
+        lds_wave_sync();
+        dist_stage<MODE, 2>(w, t, n, S, row);
+        lds_wave_sync();
+        const float* tn = t + n * S;
+        for (int base = 0; base < M; base += 64 * DIST_R) {
+            float ci[DIST_R];
+            double D[DIST_R], R2[DIST_R];
+#pragma unroll
+            for (int r = 0; r < DIST_R; ++r) {
+                const int i = base + 64 * r + lane;
+                ci[r] = row[2 * (i < M ? i : M - 1)];
+                D[r] = 0.0; R2[r] = 0.0;
+            }
+#pragma unroll 4
+            for (int j = 0; j < M; ++j) {
+                const float2 cj = reinterpret_cast<const float2*>(row)[j];
+                const double aj = (double)cj.y;
+#pragma unroll
+                for (int r = 0; r < DIST_R; ++r) {
+                    const float d = ci[r] - cj.x;
+                    D[r] = fma(aj, (double)fabsf(d), D[r]);
+                    if (MODE == 0) R2[r] = fma((double)d, (double)d, R2[r]);
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < DIST_R; ++r) {
+                const int i = base + 64 * r + lane;
+                if (i < M) {
+                    const double a = (double)row[2 * i + 1];
+                    accP += MODE == 0 ? a * D[r] / sqrt(R2[r]) : a * D[r];                  // r_i = 0 (coincident centres): 0/0 = NaN, as the reference
+                    accQ += (double)(tn[i + 1] - tn[i]) * a * a;
+                }
+            }
+        }
+    }
+    accP = wave_sum_d(accP);
+    accQ = wave_sum_d(accQ);
+    __syncthreads();                                                                         // (the rows' LDS becomes the block's reduction slots)
+    double* red = reinterpret_cast<double*>(smem);
+    if (lane == 0) { red[2 * wave_in_block()] = accP; red[2 * wave_in_block() + 1] = accQ; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        partial[2 * blockIdx.x] = ((red[0] + red[2]) + red[4]) + red[6];
+        partial[2 * blockIdx.x + 1] = ((red[1] + red[3]) + red[5]) + red[7];
+    }
+}
+__global__ __launch_bounds__(256) void distortion_loss_final_kernel(const double* __restrict__ partial, int n, int64_t N, int M, int mode, float scale,
+                                                                    float* __restrict__ out) {
+    double p = 0.0, q = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) { p += partial[2 * i]; q += partial[2 * i + 1]; }
+    p = wave_sum_d(p);
+    q = wave_sum_d(q);
+    double* red = reinterpret_cast<double*>(smem);
+    if (lane_id() == 0) { red[2 * wave_in_block()] = p; red[2 * wave_in_block() + 1] = q; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double cP, cQ;
+        dist_coeffs(mode, N, M, cP, cQ);
+        const double P = ((red[0] + red[2]) + red[4]) + red[6], Q = ((red[1] + red[3]) + red[5]) + red[7];
+        out[0] = (float)((P * cP + Q * cQ) * (double)scale);
+    }
+}
+
+// dL/d(column k) = the interval-k part h plus the interval-(k-1) part l of the lane below (lane 0: `carry`, lane 63 of the previous register)
+DEVINL double dist_from_below(double l, double& carry) {
+    double below = __shfl_up(l, 1, 64);
+    if (lane_id() == 0) below = carry;
+    carry = __shfl(l, 63, 64);
+    return below;
+}
+template <int MODE>
+__global__ __launch_bounds__(256) void distortion_loss_backward_kernel(const float* __restrict__ w, const float* __restrict__ t, int64_t N, int S,
+                                                                       float scale, const float* __restrict__ g, float* __restrict__ d_w,
+                                                                       float* __restrict__ d_t) {
+    constexpr int W = MODE == 0 ? 6 : 2;                                                     // LDS floats per interval: c, a (, u, q as doubles)
+    const int M = S - 1, lane = lane_id();
+    float* row = reinterpret_cast<float*>(smem) + (size_t)wave_in_block() * W * M;
+    double kP, kQ;
+    dist_coeffs(MODE, N, M, kP, kQ);
+    const double gs = (double)g[0] * (double)scale;
+    kP *= gs; kQ *= gs;
+    for (int64_t n = blockIdx.x * (int64_t)WAVES_PER_BLOCK + wave_in_block(); n < N; n += (int64_t)gridDim.x * WAVES_PER_BLOCK) {
+        lds_wave_sync();
+        dist_stage<MODE, W>(w, t, n, S, row);
+        lds_wave_sync();
+        const float* tn = t + n * S;
+        if (MODE == 0) {                                                                     // pass 1: u_i = a_i / r_i, q_i = a_i D_i / r_i^3 into the row
+            for (int base = 0; base < M; base += 64 * DIST_R) {
+                float ci[DIST_R];
+                double D[DIST_R], R2[DIST_R];
+#pragma unroll
+                for (int r = 0; r < DIST_R; ++r) {
+                    const int i = base + 64 * r + lane;
+                    ci[r] = row[W * (i < M ? i : M - 1)];
+                    D[r] = 0.0; R2[r] = 0.0;
+                }
+#pragma unroll 4
+                for (int j = 0; j < M; ++j) {
+                    const float2 cj = *reinterpret_cast<const float2*>(row + W * j);
+                    const double aj = (double)cj.y;
+#pragma unroll
+                    for (int r = 0; r < DIST_R; ++r) {
+                        const float d = ci[r] - cj.x;
+                        D[r] = fma(aj, (double)fabsf(d), D[r]);
+                        R2[r] = fma((double)d, (double)d, R2[r]);
+                    }
+                }
+#pragma unroll
+                for (int r = 0; r < DIST_R; ++r) {
+                    const int i = base + 64 * r + lane;
+                    if (i < M) {
+                        const double a = (double)row[W * i + 1], rr = sqrt(R2[r]);
+                        double* uq = reinterpret_cast<double*>(row + W * i + 2);
+                        uq[0] = a / rr;
+                        uq[1] = a * D[r] / (rr * R2[r]);
+                    }
+                }
+            }
+            lds_wave_sync();
+        }
+        double carry_w = 0.0, carry_t = 0.0;
+        for (int base = 0; base < M; base += 64 * DIST_R) {
+            float ck[DIST_R];
+            double D[DIST_R], R2[DIST_R], E[DIST_R], Sg[DIST_R], T[DIST_R], V[DIST_R], Cs[DIST_R];
+#pragma unroll
+            for (int r = 0; r < DIST_R; ++r) {
+                const int k = base + 64 * r + lane;
+                ck[r] = row[W * (k < M ? k : M - 1)];
+                D[r] = R2[r] = E[r] = Sg[r] = T[r] = V[r] = Cs[r] = 0.0;
+            }
+            if (MODE == 0) {
+#pragma unroll 2
+                for (int j = 0; j < M; ++j) {
+                    const float2 x = *reinterpret_cast<const float2*>(row + W * j);          // (c_j, a_j), then (u_j, q_j) in fp64
+                    const double* uq = reinterpret_cast<const double*>(row + W * j + 2);      // (8-byte aligned: 24-byte intervals)
+                    const double aj = (double)x.y, uj = uq[0], qj = uq[1];
+#pragma unroll
+                    for (int r = 0; r < DIST_R; ++r) {
+                        const float d = ck[r] - x.x;
+                        const double ad = (double)fabsf(d), dd = (double)d, s = (double)((d > 0.0f) - (d < 0.0f));
+                        D[r] = fma(aj, ad, D[r]);
+                        R2[r] = fma(dd, dd, R2[r]);
+                        E[r] = fma(uj, ad, E[r]);
+                        Sg[r] = fma(aj, s, Sg[r]);
+                        T[r] = fma(uj, s, T[r]);
+                        V[r] = fma(qj, dd, V[r]);
+                        Cs[r] += dd;
+                    }
+                }
+            } else {
+#pragma unroll 4
+                for (int j = 0; j < M; ++j) {
+                    const float2 x = *reinterpret_cast<const float2*>(row + W * j);
+                    const double aj = (double)x.y;
+#pragma unroll
+                    for (int r = 0; r < DIST_R; ++r) {
+                        const float d = ck[r] - x.x;
+                        D[r] = fma(aj, (double)fabsf(d), D[r]);
+                        Sg[r] += (double)(d > 0.0f ? x.y : (d < 0.0f ? -x.y : 0.0f));
+                    }
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < DIST_R; ++r) {
+                const int k = base + 64 * r + lane;
+                double ga = 0.0, gc = 0.0, gd = 0.0;
+                if (k < M) {
+                    const double a = (double)row[W * k + 1], dk = (double)(tn[k + 1] - tn[k]);
+                    if (MODE == 0) {
+                        const double rr = sqrt(R2[r]), u = a / rr, q = a * D[r] / (rr * R2[r]);
+                        ga = kP * (D[r] / rr + E[r]);
+                        gc = kP * (((u * Sg[r] + a * T[r]) - q * Cs[r]) - V[r]);
+                    } else {
+                        ga = kP * (2.0 * D[r]);
+                        gc = kP * (2.0 * a * Sg[r]);
+                    }
+                    ga += kQ * (2.0 * dk * a);
+                    gd = kQ * (a * a);
+                }
+                // column k of t: 0.5 gc_k - gd_k + (0.5 gc_k-1 + gd_k-1);  mode 0, column k of w: 0.5 ga_k + 0.5 ga_k-1
+                const double lt = 0.5 * gc + gd, lw = 0.5 * ga;
+                const double bt = dist_from_below(lt, carry_t), bw = dist_from_below(lw, carry_w);
+                if (k <= M) {                                                                // (k = M: the last column, its interval part is 0)
+                    if (d_t) d_t[n * S + k] = (float)((0.5 * gc - gd) + bt);
+                    if (MODE == 0 && d_w) d_w[n * S + k] = (float)(lw + bw);
+                }
+                if (MODE == 1 && d_w && k < M) d_w[n * M + k] = (float)ga;
+            }
+        }
+        if (M % (64 * DIST_R) == 0 && lane == 0) {                                           // column M fell past the last register block
+            if (d_t) d_t[n * S + M] = (float)carry_t;
+            if (MODE == 0 && d_w) d_w[n * S + M] = (float)carry_w;
+        }
+    }
+}
+
 int blocks_for(int64_t work, int per_block) {
     int64_t b = (work + per_block - 1) / per_block;
     const int64_t cap = 256 * 8;
@@ -1575,6 +1809,31 @@ int sk_weighted_dot_loss_backward(const float* g, const float* w, const float* a
                                   float* d_b, hipStream_t st) {
     if (M == 0) return 0;
     hipLaunchKernelGGL(weighted_dot_loss_backward_kernel, dim3(blocks_for(M, 256)), dim3(256), 0, st, g, w, a, b, M, mode, scale, d_w, d_a, d_b);
+    return (int)hipGetLastError();
+}
+// S <= 1024 (checked by the C-ABI): the rows take <= WAVES_PER_BLOCK x 24 x 1023 B = 96 KiB of LDS (mode 0 backward; above the default
+// dynamic limit from S = 684 on), the other kernels <= 32 KiB
+int sk_distortion_loss(const float* w, const float* t, int64_t N, int S, int mode, float scale, float* out, float* workspace, hipStream_t st) {
+    const int M = S - 1;
+    int64_t nb = (N + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
+    const int blocks = (int)(nb > DIST_BLOCKS ? DIST_BLOCKS : (nb < 1 ? 1 : nb));
+    size_t lds = (size_t)WAVES_PER_BLOCK * 2 * M * 4;
+    if (lds < 64) lds = 64;                                                                  // (the block reduction's 4 x 2 doubles)
+    double* partial = reinterpret_cast<double*>(workspace);
+    if (mode == 0) hipLaunchKernelGGL(distortion_loss_kernel<0>, dim3(blocks), dim3(256), lds, st, w, t, N, S, partial);
+    else hipLaunchKernelGGL(distortion_loss_kernel<1>, dim3(blocks), dim3(256), lds, st, w, t, N, S, partial);
+    hipLaunchKernelGGL(distortion_loss_final_kernel, dim3(1), dim3(256), 64, st, partial, blocks, N, M, mode, scale, out);
+    return (int)hipGetLastError();
+}
+int sk_distortion_loss_backward(const float* w, const float* t, int64_t N, int S, int mode, float scale, const float* g, float* d_w, float* d_t,
+                                hipStream_t st) {
+    if (N == 0 || (!d_w && !d_t)) return 0;
+    const size_t lds = (size_t)WAVES_PER_BLOCK * (mode == 0 ? 6 : 2) * (S - 1) * 4;
+    const dim3 grid(blocks_for(N, WAVES_PER_BLOCK)), block(256);
+    if (mode == 0 && lds > 64 * 1024)
+        if (int e = nerf_host::allow_dynamic_lds(reinterpret_cast<const void*>(distortion_loss_backward_kernel<0>), lds)) return e;
+    if (mode == 0) hipLaunchKernelGGL(distortion_loss_backward_kernel<0>, grid, block, lds, st, w, t, N, S, scale, g, d_w, d_t);
+    else hipLaunchKernelGGL(distortion_loss_backward_kernel<1>, grid, block, lds, st, w, t, N, S, scale, g, d_w, d_t);
     return (int)hipGetLastError();
 }
 int sk_encode_rows(const float* x, int x_stride, int64_t M, int L, int normalize, int elem_bytes, void* out, hipStream_t st) {

@@ -589,6 +589,38 @@ def weighted_dot_loss_backward(g: torch.Tensor, w: torch.Tensor, a: torch.Tensor
     return d_w, d_a, d_b
 
 
+DISTORTION_WORKSPACE_FLOATS = 4096
+
+
+def _distortion_args(w: torch.Tensor, t: torch.Tensor, mode: int):
+    w, t = _dev(w, "weights"), _dev(t, "t")
+    if t.dim() != 2 or w.dim() != 2 or mode not in (0, 1) or tuple(w.shape) != (t.shape[0], t.shape[1] - (0 if mode == 0 else 1)):
+        raise ValueError("nerf_amd: distortion_loss needs t (N, S) and weights (N, S) (mode 0) or (N, S - 1) (mode 1); got %s, %s, mode %r"
+                         % (tuple(w.shape), tuple(t.shape), mode))
+    return w, t, t.shape[0], t.shape[1]
+
+
+def distortion_loss(w: torch.Tensor, t: torch.Tensor, mode: int, scale: float) -> torch.Tensor:
+    """scale * distortion loss -> 0-dim tensor.  mode 0: the reference's Regularizer()(w, t) (addtional.py:26-35), w and t (N, S), rows
+    in any order; mode 1: Mip-NeRF 360 L_dist of weights (N, S-1) over the sorted interval edges t (N, S) (include/nerf_amd.h)"""
+    w, t, N, S = _distortion_args(w, t, mode)
+    out = torch.empty((1,), dtype=torch.float32, device=t.device)
+    ws = torch.empty((DISTORTION_WORKSPACE_FLOATS,), dtype=torch.float32, device=t.device)
+    check(lib.nerf_amd_distortion_loss(_ptr(w), _ptr(t), N, S, int(mode), float(scale), _ptr(out), _ptr(ws), _stream()), "nerf_amd_distortion_loss")
+    return out.reshape(())
+
+
+def distortion_loss_backward(g: torch.Tensor, w: torch.Tensor, t: torch.Tensor, mode: int, scale: float, need=(True, True)):
+    """gradients of distortion_loss w.r.t. (w, t) for the upstream gradient g (a 0-dim device tensor); `need` picks which are produced"""
+    w, t, N, S = _distortion_args(w, t, mode)
+    g = _dev(g, "g").reshape(1)
+    d_w = torch.empty_like(w) if need[0] else None
+    d_t = torch.empty_like(t) if need[1] else None
+    check(lib.nerf_amd_distortion_loss_backward(_ptr(w), _ptr(t), N, S, int(mode), float(scale), _ptr(g), _ptr(d_w), _ptr(d_t), _stream()),
+          "nerf_amd_distortion_loss_backward")
+    return d_w, d_t
+
+
 def merge_depths(z_fine: torch.Tensor, z_coarse: torch.Tensor) -> torch.Tensor:
     """sort(cat(z_fine, z_coarse))[..., :-1] (the render path of coarseFineMerge): a merge when both sets are ascending, which they
     normally are; rays with an out-of-order input are sorted first."""

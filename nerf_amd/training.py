@@ -26,7 +26,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .addtional import ProposalLoss, ProposalNetwork, getBounds
+from .addtional import DistortionLoss, ProposalLoss, ProposalNetwork, getBounds
 from .mip_methods import maxBlurFilter
 from .nerf_base import NeRF
 from .optim import Adam
@@ -37,7 +37,7 @@ class TrainStep:
     def __init__(self, prop_net, mip_net, optimizer: Adam, image_hw: Tuple[int, int], focal, near: float, far: float, ray_num: int = 512,
                  coarse_pnum: int = 64, fine_pnum: int = 128, crop_xy=(1.0, 1.0), seed: Optional[int] = None, white_bkg: bool = False,
                  prop_normal: bool = False, grad_hook=None, ipe_radius: Optional[float] = None, contract: bool = False, flat_grads=None,
-                 grad_clip: float = -0.01):
+                 grad_clip: float = -0.01, distortion: float = 0.0):
         """``grad_hook``: called between ``loss.backward()`` and ``optimizer.step()`` -- the place of ddp_train.py's gradient all-reduce
         (``lambda: parallel.allreduce_gradients([mip_net, prop_net])``).  An iteration with a hook runs eagerly (``capture`` refuses).
         ``ipe_radius`` (BASELINE configs[2]): the fine network encodes the conical frusta between consecutive fine depths with the
@@ -50,7 +50,11 @@ class TrainStep:
         (RCCL) averages it over the ranks.  Unlike a ``grad_hook`` this is part of the captured iteration: ``capture()`` records the
         collective into the hipGraph (backend nccl), so the replayed iteration keeps its launch-free pace on N GPUs.
         ``grad_clip`` (train.py:119-121,217 `--grad_clip`, negative = off like the reference's default): global-norm clipping between
-        backward and the optimizer step, evaluated on the device (no host read: capturable)."""
+        backward and the optimizer step, evaluated on the device (no host read: capturable).
+        ``distortion`` (BASELINE configs[4]; not in the reference): adds ``distortion * L_dist`` -- Mip-NeRF 360's distortion loss
+        (addtional.DistortionLoss) of the fine weights over the fine_pnum + 1 sorted fine depths in the normalised coordinate
+        s = (z - near) / (far - near) -- to the MipNeRF branch's loss, differentiated w.r.t. the weights; the term of the last iteration is
+        ``self.dist_loss``.  0 (default) leaves the iteration as it is."""
         if not isinstance(optimizer, Adam) or not optimizer.lr_on_device:
             raise ValueError("nerf_amd.training.TrainStep needs nerf_amd.optim.Adam(..., lr_on_device=True): the step must not read host state")
         self.prop_net, self.mip_net, self.opt = prop_net, mip_net, optimizer
@@ -62,6 +66,12 @@ class TrainStep:
         self.ipe_radius, self.contract = (None if ipe_radius is None else float(ipe_radius)), bool(contract)
         if self.is_ref and self.ipe_radius is not None:
             raise NotImplementedError("nerf_amd.training.TrainStep: the integrated PE is wired for the MipNeRF branch (the Ref-NeRF kernel encodes points)")
+        self.distortion = float(distortion)
+        if not self.distortion >= 0.0:
+            raise ValueError("nerf_amd.training.TrainStep: distortion must be >= 0")
+        if self.is_ref and self.distortion > 0.0:
+            raise NotImplementedError("nerf_amd.training.TrainStep: the distortion loss is wired for the MipNeRF branch (the Ref-NeRF step's merged "
+                                      "sample set has no closed last interval)")
         self.prop_normal = bool(prop_normal) and self.is_ref                              # (train.py: prop_normal only acts with a Ref-NeRF)
         dev = next(mip_net.parameters()).device
         H, W = image_hw
@@ -73,6 +83,9 @@ class TrainStep:
         self.seed = torch.full((1,), seed, dtype=torch.int64, device=dev)
         self.loss = torch.zeros((), dtype=torch.float32, device=dev)
         self.img_loss = torch.zeros((), dtype=torch.float32, device=dev)
+        self.dist_loss = torch.zeros((), dtype=torch.float32, device=dev)
+        # L_dist is 1-homogeneous in the depths: in s = (z - near) / (far - near) it is L_dist(z) / (far - near)
+        self.dist_fn = DistortionLoss(self.distortion / (self.far - self.near)) if self.distortion > 0.0 else None
         if self.is_ref:                                      # the bottle-neck perturbation keyed by this step's device-resident seed
             mip_net.__dict__["noise_seed_dev"] = self.seed   # (RefNeRF.forward, noise_rng "philox": a replayed graph draws fresh noise)
         self.prop_loss_fn = ProposalLoss()
@@ -139,6 +152,7 @@ class TrainStep:
                 picked = RefNeRF.coarse_grad_select(density_grad, sort_ids, self.coarse_pnum)
                 extra = extra + 4e-5 * WeightedNormalLoss()(prop_w, picked.detach(), coarse_grad)       # 4e-4 * 0.1 (:198)
         else:
+            edges = z_f                                          # the fine_pnum + 1 sorted fine depths: the intervals of L_dist
             if self.ipe_radius is not None:                      # the fine_pnum frusta between the fine_pnum + 1 sorted depths
                 rgbo = self.mip_net.forward_rays(rays, z_f, self.fine_pnum, ipe_radius=self.ipe_radius, contract=self.contract)
                 z_f = z_f[..., :-1].contiguous()
@@ -147,6 +161,8 @@ class TrainStep:
                 rgbo = (self.mip_net.forward_rays(rays, z_f, self.fine_pnum, contract=True) if self.contract
                         else self.mip_net.forward(NeRF.length2pts(rays, z_f)))                          # :189-190
             rendered, weights, _ = NeRF.render(rgbo, z_f, dirs, white_bkg=self.white_bkg)               # :191
+            if self.dist_fn is not None:
+                extra = self.dist_fn(weights, edges)
         bounds = getBounds(prop_w, below)                                                               # :192
         if self.flat_grads is not None:
             self.flat_grads.bind(); self.flat_grads.begin_step()                                        # (the kernels overwrite: no zeroing pass)
@@ -170,6 +186,8 @@ class TrainStep:
         ops.advance_seed(self.seed)
         self.loss.copy_(loss.detach())
         self.img_loss.copy_(img_loss.detach())
+        if self.dist_fn is not None:
+            self.dist_loss.copy_(extra.detach())
 
     # ---------------------------------------------------------------------------------------------------------------- driving it
     def set_image(self, img: torch.Tensor, pose: torch.Tensor) -> None:
