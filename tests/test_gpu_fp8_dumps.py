@@ -14,6 +14,7 @@ import torch
 import torch.nn.functional as F
 
 import weights as W
+from backward_ref import decode_f8_slot as _decode_f8_slot      # (shared with test_gpu_backward_layers.py)
 from oracle import nerf_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -40,20 +41,6 @@ def _nets(A, tag):
     prop.load_state_dict(W.proposal_state(tag))
     mip.load_state_dict(W.mip_state(tag))
     return prop.cuda().train(), mip.cuda().train()
-
-
-def _decode_f8_slot(dump, layer, layer_stride, n_sub, n_kg=16):
-    """host-side reading of one fp8 slot -> (n_sub * 32, 16 * n_kg) float32 rows (mlp_layout.h: 8 data blocks + scale exponents per subtile;
-    element e of K group kg in lane j + 32 h = feature 16 kg + 8 (e >> 2) + 4 h + (e & 3) of sample j)"""
-    raw = dump[layer * layer_stride: layer * layer_stride + n_sub * 9216].view(n_sub, 9216)
-    data = raw[:, :8192].reshape(n_sub, 8, 64, 2, 8)                       # [sub][fb][lane][kg & 1][e]
-    vals = data.view(torch.float8_e4m3fn).float()
-    ex = raw[:, 8192:].reshape(n_sub, 64, 16).float()                      # [sub][lane][kg]
-    scale = torch.exp2(ex - 127.0).permute(0, 2, 1).reshape(n_sub, 8, 2, 64).permute(0, 1, 3, 2)      # -> [sub][fb][lane][kg & 1]
-    vals = vals * scale[..., None]
-    v = vals.permute(0, 1, 3, 2, 4).reshape(n_sub, 16, 2, 32, 2, 4)        # [sub][kg][h][j][e >> 2][e & 3]
-    rows = v.permute(0, 3, 1, 4, 2, 5).reshape(n_sub * 32, 16 * 16)        # feature = 16 kg + 8 (e >> 2) + 4 h + (e & 3)
-    return rows[:, : 16 * n_kg]
 
 
 @pytest.mark.parametrize("tag", ["small", "he"])
