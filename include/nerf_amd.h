@@ -230,6 +230,21 @@ int nerf_amd_sample_training_rays_dev(const float* rgbs, const int64_t* coords, 
                                       float near, float far, int64_t N, int C, const uint64_t* seed_dev, float* pts, float* lengths,
                                       float* rgb, float* rays, void* stream);
 int nerf_amd_philox_uniforms(float* out, int64_t N, int K, uint64_t rng_seed, const uint64_t* seed_dev, void* stream);
+/* (added after ABI 125; additive) The same batch drawn uniformly over ALL training pixels of a scene in one launch: images (V,3,H,W) fp32
+ * planar and poses (V,3,4) fp32, both on the device and read in place (no pixel table, no coordinate table).  view_ids (K,) int64 on the
+ * device selects K of the V views (NULL: views 0..K-1; pass K = V for the whole stack; an entry outside [0, V) reads nothing: its rays come out NaN with index -1);
+ * the window x0 <= col < x1, y0 <= row < y1 is the centre crop of randomFromOneImage (0, W, 0, H = the whole image).  With
+ * wp = (y1-y0)(x1-x0) and P = K wp, ray n draws cell = floor(P * u64 / 2^64) from the SAME word of the same counter (n, 0, 'IX') as
+ * nerf_amd_sample_training_rays, then k = cell / wp, r = cell % wp, row = y0 + r / (x1-x0), col = x0 + r % (x1-x0), v = view_ids ?
+ * view_ids[k] : k -- all in 64-bit.  rgb (N,3) = images[v, :, row, col]; rays (N,6) = [poses[v][:,3] | R_v.(cx, cy, -1)] with
+ * cx = ((float)(col - W/2) + 0.5f) / fx, cy = ((float)(H/2 - row) + 0.5f) / fy (integer halves, the coordinate table's values);
+ * index (N) int64 = (v H + row) W + col, or NULL to skip; lengths (N,C) / pts (N,C,3) as in nerf_amd_sample_training_rays (stream 'TS'),
+ * skipped when lengths is NULL or C == 0 (pts without lengths is an error).  Key: rng_seed, or *seed_dev (device) when given.
+ * With K = 1 the outputs are bit-identical to nerf_amd_sample_training_rays_dev on randomFromOneImage(images[v]) with the same seed: the
+ * window is enumerated row-major like the table. */
+int nerf_amd_sample_scene_rays(const float* images, const float* poses, int64_t V, int H, int W, const int64_t* view_ids, int64_t K, int x0,
+                               int x1, int y0, int y1, float fx, float fy, float near, float far, int64_t N, int C, uint64_t rng_seed,
+                               const uint64_t* seed_dev, float* pts, float* lengths, float* rgb, float* rays, int64_t* index, void* stream);
 /* (ABI 121) Either Philox stream of the render kernels as a tensor, for rows that are GLOBAL rays ray_offset .. ray_offset + N - 1: the
  * uniforms the reference draws per tile with torch.rand (procedures.py:65 stratified jitter -> NERF_AMD_PHILOX_STRAT, K <= 64;
  * utils.py:115 inverse-CDF -> NERF_AMD_PHILOX_INV), bit-identical to what nerf_amd_render_rays draws in place for the same seed and ray

@@ -61,6 +61,8 @@ SIGNATURES = {
                                                c_void, c_void, c_void, c_void, c_void]),
     "nerf_amd_sample_training_rays_dev": (C.c_int, [c_void, c_void, i64, c_void, C.c_float, C.c_float, C.c_float, C.c_float, i64, C.c_int, c_void,
                                                    c_void, c_void, c_void, c_void, c_void]),
+    "nerf_amd_sample_scene_rays": (C.c_int, [c_void, c_void, i64, C.c_int, C.c_int, c_void, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
+                                            C.c_float, C.c_float, i64, C.c_int, C.c_uint64, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
     "nerf_amd_philox_uniforms": (C.c_int, [c_void, i64, C.c_int, C.c_uint64, c_void, c_void]),
     "nerf_amd_philox_stream": (C.c_int, [c_void, i64, C.c_int, C.c_uint64, c_void, i64, C.c_int, c_void]),
     "nerf_amd_advance_seed": (C.c_int, [c_void, c_void]),

@@ -59,6 +59,8 @@ int sk_dirs_norm(const float*, int64_t, float*, hipStream_t);
 int sk_dirs_norm_scratch(const float*, int64_t, float*, void*, hipStream_t);
 int sk_train_sampler(const float*, const int64_t*, int64_t, const float*, const float*, float, float, float, float, int64_t, int, uint64_t, const uint64_t*,
                      float*, float*, float*, float*, hipStream_t);
+int sk_scene_sampler(const float*, const float*, int64_t, int, int, const int64_t*, int64_t, int, int, int, int, float, float, float, float, int64_t, int,
+                     uint64_t, const uint64_t*, float*, float*, float*, float*, int64_t*, hipStream_t);
 int sk_philox_uniforms(float*, int64_t, int, uint64_t, const uint64_t*, int64_t, int, hipStream_t);
 int sk_philox_normal(float*, int64_t, uint64_t, const uint64_t*, float, int64_t, hipStream_t);
 size_t gk_gemm_workspace_bytes(int64_t, int64_t, int64_t);
@@ -336,6 +338,26 @@ int nerf_amd_sample_training_rays_dev(const float* rgbs, const int64_t* coords, 
     if ((pts == nullptr) != (lengths == nullptr) || (pts && C < 1)) return fail(NERF_AMD_EINVAL, "pts and lengths go together (C >= 1)");
     return hip_status(sk_train_sampler(rgbs, coords, n_pixels, nullptr, pose_dev, fx, fy, near, far, N, C, 0, seed_dev, pts, lengths, rgb, rays, S(stream)),
                       "nerf_amd_sample_training_rays_dev");
+}
+int nerf_amd_sample_scene_rays(const float* images, const float* poses, int64_t V, int H, int W, const int64_t* view_ids, int64_t K, int x0, int x1,
+                               int y0, int y1, float fx, float fy, float near, float far, int64_t N, int C, uint64_t rng_seed,
+                               const uint64_t* seed_dev, float* pts, float* lengths, float* rgb, float* rays, int64_t* index, void* stream) {
+    if (!images) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: images is NULL");
+    if (!poses) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: poses is NULL");
+    if (V < 1 || H < 1 || W < 1) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: V, H, W must be positive");
+    if (K < 1 || (!view_ids && K > V)) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: need 1 <= K (and K <= V without view_ids)");
+    if (x0 < 0 || x1 > W || x0 >= x1) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: window x0, x1 empty or outside the image (0 <= x0 < x1 <= W)");
+    if (y0 < 0 || y1 > H || y0 >= y1) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: window y0, y1 empty or outside the image (0 <= y0 < y1 <= H)");
+    if (N < 0) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: N is negative");
+    if (C < 0) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: C is negative");
+    if (pts && !lengths) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: pts given without lengths");
+    if (lengths && C > 0 && !pts) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: lengths given without pts");
+    if (!rgb) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: rgb is NULL");
+    if (!rays) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: rays is NULL");
+    if (N == 0) return NERF_AMD_OK;
+    return hip_status(sk_scene_sampler(images, poses, V, H, W, view_ids, K, x0, x1, y0, y1, fx, fy, near, far, N, C, rng_seed, seed_dev, pts, lengths, rgb,
+                                       rays, index, S(stream)),
+                      "nerf_amd_sample_scene_rays");
 }
 int nerf_amd_philox_uniforms(float* out, int64_t N, int K, uint64_t rng_seed, const uint64_t* seed_dev, void* stream) {
     if (N < 0 || K < 0) return fail(NERF_AMD_EINVAL, "negative size");

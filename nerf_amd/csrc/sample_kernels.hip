@@ -208,6 +208,42 @@ __global__ void stratified_points_kernel(const float* __restrict__ rays, const f
 // stream 'TS' (utils.py:87-89) and the sample positions o + d z (utils.py:90).  The reference draws both on the CPU generator and
 // copies them to the device every iteration (train.py:153-157).  One workgroup = 4 rays x C samples.
 constexpr uint32_t PHILOX_STREAM_INDEX = 0x4958u, PHILOX_STREAM_TRAIN = 0x5453u;
+// The per-ray and per-sample bodies, shared by train_sampler_kernel and scene_sampler_kernel (same words, same expression grouping: the
+// two kernels agree bit for bit where they overlap).
+// 64-bit word of counter (n, 0, 'IX'): floor(P * x / 2^64) is ray n's uniform draw in [0, P)
+DEVINL uint64_t sampler_index_word(int64_t n, uint64_t seed) {
+    const Philox4 r = philox4x32_10((uint32_t)n, (uint32_t)((uint64_t)n >> 32), 0u, PHILOX_STREAM_INDEX, (uint32_t)seed, (uint32_t)(seed >> 32));
+    return ((uint64_t)r.w[0] << 32) | r.w[1];
+}
+// ray through the pixel with integer coordinates (ix, iy) = (col - W//2, H//2 - row) (utils.py:78-85) -> q[6] (LDS) and rays[n]
+DEVINL void sampler_ray(const float* pose, float fx, float fy, float ix, float iy, float* q, float* __restrict__ ray_out) {
+    const float cx = (ix + 0.5f) / fx;                                                   // utils.py:78-81
+    const float cy = (iy + 0.5f) / fy;
+    q[0] = pose[3]; q[1] = pose[7]; q[2] = pose[11];
+    q[3] = (cx * pose[0] + cy * pose[1]) + (-1.0f) * pose[2];
+    q[4] = (cx * pose[4] + cy * pose[5]) + (-1.0f) * pose[6];
+    q[5] = (cx * pose[8] + cy * pose[9]) + (-1.0f) * pose[10];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) ray_out[k] = q[k];
+}
+// the stratified depths and positions of the (up to) 4 rays n0 .. n0+3 of a workgroup, 256 threads over 4 x C samples
+DEVINL void sampler_samples(int64_t n0, int64_t N, int C, uint64_t seed, float near, float res, const float (*ray_s)[6], float* __restrict__ lengths,
+                            float* __restrict__ pts) {
+    const int64_t cnt = ((N - n0 < 4) ? N - n0 : 4) * C;
+    for (int64_t i = threadIdx.x; i < cnt; i += 256) {
+        const int rl = (int)(i / C), sidx = (int)(i - (int64_t)rl * C);
+        const int64_t n = n0 + rl;
+        const Philox4 r = philox4x32_10((uint32_t)n, (uint32_t)((uint64_t)n >> 32), (uint32_t)(sidx >> 2), PHILOX_STREAM_TRAIN, (uint32_t)seed,
+                                        (uint32_t)(seed >> 32));
+        const int w = sidx & 3;
+        const float u = u01_from_bits(w == 0 ? r.w[0] : (w == 1 ? r.w[1] : (w == 2 ? r.w[2] : r.w[3])));
+        const float z = (near + (float)sidx * res) + u * res;                        // linspace(near, far - res, C)[s] + u res
+        lengths[n * C + sidx] = z;
+        const float* q = ray_s[rl];
+        float* o = pts + (n * C + sidx) * 3;
+        o[0] = q[0] + q[3] * z; o[1] = q[1] + q[4] * z; o[2] = q[2] + q[5] * z;
+    }
+}
 // `pose_dev` / `seed_dev` (both optional): the camera pose and the seed read from DEVICE memory instead of the launch arguments, so that
 // a captured hipGraph of the training step sees a new image pose and fresh random numbers on every replay.
 __global__ __launch_bounds__(256) void train_sampler_kernel(const float* __restrict__ rgbs, const int64_t* __restrict__ coords, int64_t P, Cam cam,
@@ -224,37 +260,59 @@ __global__ __launch_bounds__(256) void train_sampler_kernel(const float* __restr
         __syncthreads();
         if (threadIdx.x < 4 && n0 + threadIdx.x < N) {
             const int64_t n = n0 + threadIdx.x;
-            const Philox4 r = philox4x32_10((uint32_t)n, (uint32_t)((uint64_t)n >> 32), 0u, PHILOX_STREAM_INDEX, (uint32_t)seed, (uint32_t)(seed >> 32));
-            const uint64_t x = ((uint64_t)r.w[0] << 32) | r.w[1];
-            const int64_t idx = (int64_t)__umul64hi(x, (uint64_t)P);                     // uniform in [0, P)
-            const float cx = ((float)coords[idx * 2] + 0.5f) / cam.fx;                   // utils.py:78-81
-            const float cy = ((float)coords[idx * 2 + 1] + 0.5f) / cam.fy;
-            float* q = ray_s[threadIdx.x];
-            q[0] = cam.pose[3]; q[1] = cam.pose[7]; q[2] = cam.pose[11];
-            q[3] = (cx * cam.pose[0] + cy * cam.pose[1]) + (-1.0f) * cam.pose[2];
-            q[4] = (cx * cam.pose[4] + cy * cam.pose[5]) + (-1.0f) * cam.pose[6];
-            q[5] = (cx * cam.pose[8] + cy * cam.pose[9]) + (-1.0f) * cam.pose[10];
-#pragma unroll
-            for (int k = 0; k < 6; ++k) rays[n * 6 + k] = q[k];
+            const int64_t idx = (int64_t)__umul64hi(sampler_index_word(n, seed), (uint64_t)P);     // uniform in [0, P)
+            sampler_ray(cam.pose, cam.fx, cam.fy, (float)coords[idx * 2], (float)coords[idx * 2 + 1], ray_s[threadIdx.x], rays + n * 6);
 #pragma unroll
             for (int k = 0; k < 3; ++k) rgb[n * 3 + k] = rgbs[idx * 3 + k];
         }
         __syncthreads();
         if (lengths == nullptr) continue;
-        const int64_t cnt = ((N - n0 < 4) ? N - n0 : 4) * C;
-        for (int64_t i = threadIdx.x; i < cnt; i += 256) {
-            const int rl = (int)(i / C), sidx = (int)(i - (int64_t)rl * C);
-            const int64_t n = n0 + rl;
-            const Philox4 r = philox4x32_10((uint32_t)n, (uint32_t)((uint64_t)n >> 32), (uint32_t)(sidx >> 2), PHILOX_STREAM_TRAIN, (uint32_t)seed,
-                                            (uint32_t)(seed >> 32));
-            const int w = sidx & 3;
-            const float u = u01_from_bits(w == 0 ? r.w[0] : (w == 1 ? r.w[1] : (w == 2 ? r.w[2] : r.w[3])));
-            const float z = (near + (float)sidx * res) + u * res;                        // linspace(near, far - res, C)[s] + u res
-            lengths[n * C + sidx] = z;
-            const float* q = ray_s[rl];
-            float* o = pts + (n * C + sidx) * 3;
-            o[0] = q[0] + q[3] * z; o[1] = q[1] + q[4] * z; o[2] = q[2] + q[5] * z;
+        sampler_samples(n0, N, C, seed, near, res, ray_s, lengths, pts);
+    }
+}
+
+// The scene twin: the batch drawn uniformly over the window of K views of a planar image stack images (V,3,H,W), read in place -- no
+// (H W, 3) pixel table, no coordinate table -- with each ray's pose fetched from poses (V,3,4).  cell = floor(K wp * x / 2^64) with x the
+// word train_sampler_kernel draws; view slot k = cell / wp, and the remainder enumerates the window row-major like randomFromOneImage's
+// table, so K = 1 reproduces train_sampler_kernel on that table bit for bit.  Every index here is 64-bit by construction: K wp and
+// V H W are never assumed to fit 32 bits (a stack of that size cannot be allocated for a test).  A view id outside [0, V) (a device
+// tensor the host never saw) reads nothing: that ray is NaN with index -1.
+__global__ __launch_bounds__(256) void scene_sampler_kernel(const float* __restrict__ images, const float* __restrict__ poses, int64_t V, int H, int W,
+                                                            const int64_t* __restrict__ view_ids, int64_t K, int x0, int ww, int y0, int64_t wp,
+                                                            float fx, float fy, float near, float res, int64_t N, int C, uint64_t seed,
+                                                            const uint64_t* __restrict__ seed_dev, float* __restrict__ pts, float* __restrict__ lengths,
+                                                            float* __restrict__ rgb, float* __restrict__ rays, int64_t* __restrict__ index) {
+    __shared__ float ray_s[4][6];
+    if (seed_dev != nullptr) seed = seed_dev[0];
+    const uint64_t P = (uint64_t)K * (uint64_t)wp;
+    for (int64_t n0 = blockIdx.x * (int64_t)4; n0 < N; n0 += (int64_t)gridDim.x * 4) {
+        __syncthreads();
+        if (threadIdx.x < 4 && n0 + threadIdx.x < N) {
+            const int64_t n = n0 + threadIdx.x;
+            const int64_t cell = (int64_t)__umul64hi(sampler_index_word(n, seed), P);               // uniform in [0, K wp)
+            const int64_t k = cell / wp, r = cell - k * wp;
+            const int64_t wr = r / ww;
+            const int64_t row = y0 + wr, col = x0 + (r - wr * ww);
+            const int64_t v = view_ids != nullptr ? view_ids[k] : k;
+            float* q = ray_s[threadIdx.x];
+            if (v >= 0 && v < V) {
+                sampler_ray(poses + v * 12, fx, fy, (float)(col - W / 2), (float)(H / 2 - row), q, rays + n * 6);
+                const float* px = images + ((v * 3) * (int64_t)H + row) * W + col;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) rgb[n * 3 + c] = px[(int64_t)c * H * W];
+                if (index != nullptr) index[n] = (v * H + row) * W + col;
+            } else {
+                const float nan = __builtin_nanf("");
+#pragma unroll
+                for (int c = 0; c < 6; ++c) { q[c] = nan; rays[n * 6 + c] = nan; }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) rgb[n * 3 + c] = nan;
+                if (index != nullptr) index[n] = -1;
+            }
         }
+        __syncthreads();
+        if (lengths == nullptr) continue;
+        sampler_samples(n0, N, C, seed, near, res, ray_s, lengths, pts);
     }
 }
 
@@ -1596,6 +1654,18 @@ int sk_train_sampler(const float* rgbs, const int64_t* coords, int64_t P, const 
     for (int i = 0; i < 12; ++i) c.pose[i] = pose ? pose[i] : 0.0f;
     hipLaunchKernelGGL(train_sampler_kernel, dim3(blocks_for(N, 4)), dim3(256), 0, st, rgbs, coords, P, c, near, C > 0 ? (far - near) / (float)C : 0.0f, N, C, seed,
                        pts, lengths, rgb, rays, pose_dev, seed_dev);
+    return (int)hipGetLastError();
+}
+
+// window: x0 <= col < x1, y0 <= row < y1 (validated by the caller)
+int sk_scene_sampler(const float* images, const float* poses, int64_t V, int H, int W, const int64_t* view_ids, int64_t K, int x0, int x1, int y0, int y1,
+                     float fx, float fy, float near, float far, int64_t N, int C, uint64_t seed, const uint64_t* seed_dev, float* pts, float* lengths,
+                     float* rgb, float* rays, int64_t* index, hipStream_t st) {
+    if (N == 0) return 0;
+    const int ww = x1 - x0;
+    const int64_t wp = (int64_t)(y1 - y0) * ww;
+    hipLaunchKernelGGL(scene_sampler_kernel, dim3(blocks_for(N, 4)), dim3(256), 0, st, images, poses, V, H, W, view_ids, K, x0, ww, y0, wp, fx, fy, near,
+                       C > 0 ? (far - near) / (float)C : 0.0f, N, C, seed, seed_dev, pts, C > 0 ? lengths : nullptr, rgb, rays, index);
     return (int)hipGetLastError();
 }
 

@@ -462,6 +462,68 @@ def sample_training_rays_dev(rgbs: torch.Tensor, coords: torch.Tensor, pose_dev:
     return pts, z, rgb, rays
 
 
+def scene_view_ids(view_ids, n_views: int, device) -> Optional[torch.Tensor]:
+    """``view_ids`` of sample_scene_rays as the (K,) int64 device tensor the kernel reads (None stays None = every view): a list or CPU
+    tensor is range-checked against ``n_views`` and uploaded, a device tensor is only checked for its form."""
+    if view_ids is None:
+        return None
+    if isinstance(view_ids, torch.Tensor) and view_ids.is_cuda:
+        if view_ids.dtype != torch.int64 or view_ids.dim() != 1 or view_ids.shape[0] < 1 or not view_ids.is_contiguous() or view_ids.device != device:
+            raise ValueError("nerf_amd: a device 'view_ids' must be a contiguous, non-empty (K,) int64 tensor on the images' device")
+        return view_ids
+    ids = torch.as_tensor(view_ids, dtype=torch.int64).reshape(-1)
+    if ids.numel() < 1 or int(ids.min()) < 0 or int(ids.max()) >= n_views:
+        raise ValueError("nerf_amd: view_ids must name at least one view, each in [0, %d)" % n_views)
+    return ids.to(device)
+
+
+def sample_scene_rays(images: torch.Tensor, poses: torch.Tensor, fx: float, fy: float, near: float, far: float, n_rays: int, n_points: int,
+                      seed: int = 0, seed_dev: Optional[torch.Tensor] = None, window=None, view_ids=None, want_samples: bool = True,
+                      want_index: bool = True, index_out: Optional[torch.Tensor] = None):
+    """The training batch drawn uniformly over ALL pixels of a scene in one launch (nerf_amd_sample_scene_rays): images (V,3,H,W) fp32
+    planar and poses (V,3,4) fp32, contiguous device tensors read in place (they are never copied or converted: anything else raises).
+    ``window`` = (x0, x1, y0, y1), columns x0..x1-1 and rows y0..y1-1 of every view (None: the whole image); ``view_ids``: the views to
+    draw from (None: all V).  A list or CPU tensor is range-checked against V and uploaded; a DEVICE int64 tensor is taken as it is --
+    the caller vouches for its entries (an entry outside [0, V) yields NaN rays with index -1, nothing is read).  Key: ``seed``, or the
+    (1,) int64 device tensor ``seed_dev`` read when the kernel RUNS (replayable from a captured hipGraph).  ``index_out``: a persistent
+    (N,) int64 device tensor to write the indices into instead of a fresh one.
+    -> (pts (N,C,3) | None, lengths (N,C) | None, rgb (N,3), rays (N,6), index (N,) int64 = (v H + row) W + col | None)"""
+    for t, name, tail in ((images, "images", (3,)), (poses, "poses", (3, 4))):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise RuntimeError("nerf_amd: '%s' must live on the HIP device; there is no CPU path" % name)
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise ValueError("nerf_amd: '%s' must be a contiguous fp32 tensor (it is read in place)" % name)
+    if images.dim() != 4 or images.shape[1] != 3 or poses.dim() != 3 or tuple(poses.shape[1:]) != (3, 4) or poses.shape[0] != images.shape[0] \
+            or images.shape[0] < 1 or poses.device != images.device:
+        raise ValueError("nerf_amd: images (V,3,H,W) and poses (V,3,4) must agree in V and device (got %s and %s)" % (tuple(images.shape), tuple(poses.shape)))
+    V, _, H, W = images.shape
+    x0, x1, y0, y1 = (0, W, 0, H) if window is None else (int(a) for a in window)
+    dev = images.device
+    view_ids = scene_view_ids(view_ids, V, dev)
+    K = V if view_ids is None else view_ids.shape[0]
+    if seed_dev is not None and not (seed_dev.is_cuda and seed_dev.dtype == torch.int64 and seed_dev.numel() == 1):
+        raise RuntimeError("nerf_amd: seed_dev = one int64 on the device")
+    n_rays, n_points = int(n_rays), int(n_points)
+    samples = bool(want_samples) and n_points > 0
+    pts = torch.empty((n_rays, n_points, 3), dtype=torch.float32, device=dev) if samples else None
+    z = torch.empty((n_rays, n_points), dtype=torch.float32, device=dev) if samples else None
+    rgb = torch.empty((max(n_rays, 0), 3), dtype=torch.float32, device=dev)
+    rays = torch.empty((max(n_rays, 0), 6), dtype=torch.float32, device=dev)
+    index = torch.empty((max(n_rays, 0),), dtype=torch.int64, device=dev) if want_index and index_out is None else None
+    if index_out is not None:
+        if not (index_out.is_cuda and index_out.dtype == torch.int64 and index_out.is_contiguous() and tuple(index_out.shape) == (n_rays,)
+                and index_out.device == dev):
+            raise ValueError("nerf_amd: index_out must be a contiguous (n_rays,) int64 tensor on the images' device")
+        index = index_out
+    if n_rays == 0:                                           # (empty tensors have no address to hand over; the entry point launches nothing either)
+        return pts, z, rgb, rays, index
+    check(lib.nerf_amd_sample_scene_rays(_ptr(images), _ptr(poses), V, H, W, _ptr(view_ids), K, x0, x1, y0, y1, float(fx), float(fy), float(near),
+                                         float(far), n_rays, n_points if samples else 0, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(seed_dev), _ptr(pts),
+                                         _ptr(z), _ptr(rgb), _ptr(rays), _ptr(index), _stream()),
+          "nerf_amd_sample_scene_rays")
+    return pts, z, rgb, rays, index
+
+
 def philox_uniforms(shape, seed: int = 0, seed_dev: Optional[torch.Tensor] = None, device=None) -> torch.Tensor:
     """u (N,K) in [0,1): the kernels' inverse-CDF Philox stream as a tensor (key = seed, or *seed_dev read at run time)."""
     N, K = int(shape[0]), int(shape[1])

@@ -13,6 +13,16 @@ replayed: 0.9 ms instead of 1.7 ms per 512-ray step on one MI355X (bench.py ``tr
         lr_sch.update_opt_lr(cnt, optimizer)         # DecayLrScheduler as in train.py:218 -- picked up through the device-side lr
         loss, img_loss = step(img, pose)             # device scalars; read them (``.item()``) only when logging
 
+Scene mode -- every batch drawn uniformly over ALL training pixels of the scene, which ``CustomDataSet.get_dataset(to_cuda=True)`` holds
+in HBM as images (V,3,H,W) / poses (V,3,4): one kernel (``ops.sample_scene_rays``) reads the stack in place, so the step has no
+per-iteration input at all:
+
+    step = TrainStep(prop_net, mip_net, optimizer, image_hw=(800, 800), focal=f, near=2., far=6., ray_num=1024, scene=(images, poses))
+    step.capture()
+    for cnt in range(iterations):
+        lr_sch.update_opt_lr(cnt, optimizer)
+        loss, img_loss = step()                      # step.ray_index: the (v H + row) W + col of the rays just trained on
+
 Semantics are those of train.py:164-199: proposal forward -> softplus -> get_weights -> maxBlurFilter -> inverseSample(sort) ->
 MipNeRF forward -> render -> getBounds -> ProposalLoss + MSE -> backward -> Adam; with a RefNeRF as the fine network the
 ``is_ref_model`` branch (train.py:176-187: coarse/fine merge, density-gradient normals, normal and back-face losses, and with
@@ -30,14 +40,33 @@ from .addtional import DistortionLoss, ProposalLoss, ProposalNetwork, getBounds
 from .mip_methods import maxBlurFilter
 from .nerf_base import NeRF
 from .optim import Adam
-from .utils import _focal_xy, inverseSample, randomFromOneImage
+from .utils import _focal_xy, crop_window, inverseSample, randomFromOneImage
+
+_M62 = (1 << 62) - 1
+
+
+def rank_seed(seed: int, rank: int) -> int:
+    """The sampler seed of data-parallel rank ``rank`` in scene mode.  In image mode the ranks see different images; in scene mode equal
+    seeds would give every rank the SAME batch.  Rank 0 keeps ``seed`` unchanged; rank r > 0 gets seed XOR m(r) (62 bits), m a bijection
+    of [0, 2^62) that fixes 0 (xorshift / odd-multiply rounds) -- so distinct ranks get distinct seeds whatever the seed, and every
+    result is below 2^62 when the seed is.  Pure: no process group is consulted."""
+    seed, rank = int(seed), int(rank)
+    if not 0 <= rank <= _M62:
+        raise ValueError("nerf_amd.training.rank_seed: rank must be in [0, 2^62)")
+    if rank == 0:
+        return seed
+    x = rank
+    x = ((x ^ (x >> 31)) * 0xBF58476D1CE4E5B9) & _M62         # each step is invertible modulo 2^62 and maps 0 to 0
+    x = ((x ^ (x >> 29)) * 0x94D049BB133111EB) & _M62
+    x ^= x >> 32
+    return (seed & _M62) ^ x
 
 
 class TrainStep:
     def __init__(self, prop_net, mip_net, optimizer: Adam, image_hw: Tuple[int, int], focal, near: float, far: float, ray_num: int = 512,
                  coarse_pnum: int = 64, fine_pnum: int = 128, crop_xy=(1.0, 1.0), seed: Optional[int] = None, white_bkg: bool = False,
                  prop_normal: bool = False, grad_hook=None, ipe_radius: Optional[float] = None, contract: bool = False, flat_grads=None,
-                 grad_clip: float = -0.01, distortion: float = 0.0):
+                 *, scene=None, view_ids=None, grad_clip: float = -0.01, distortion: float = 0.0):
         """``grad_hook``: called between ``loss.backward()`` and ``optimizer.step()`` -- the place of ddp_train.py's gradient all-reduce
         (``lambda: parallel.allreduce_gradients([mip_net, prop_net])``).  An iteration with a hook runs eagerly (``capture`` refuses).
         ``ipe_radius`` (BASELINE configs[2]): the fine network encodes the conical frusta between consecutive fine depths with the
@@ -54,7 +83,17 @@ class TrainStep:
         ``distortion`` (BASELINE configs[4]; not in the reference): adds ``distortion * L_dist`` -- Mip-NeRF 360's distortion loss
         (addtional.DistortionLoss) of the fine weights over the fine_pnum + 1 sorted fine depths in the normalised coordinate
         s = (z - near) / (far - near) -- to the MipNeRF branch's loss, differentiated w.r.t. the weights; the term of the last iteration is
-        ``self.dist_loss``.  0 (default) leaves the iteration as it is."""
+        ``self.dist_loss``.  0 (default) leaves the iteration as it is.
+        ``scene`` = (images (V,3,H,W), poses (V,3,4)), contiguous fp32 device tensors with (H, W) == ``image_hw`` (not in the reference,
+        which trains on one image per iteration): every batch is drawn uniformly over the (cropped) pixels of all V views -- or of the
+        views ``view_ids`` (list / CPU tensor: range-checked once here; device int64 tensor: taken as it is) -- by one kernel that reads
+        the stack in place, keyed by the step's device seed.  The step then takes no image: ``step()``; ``set_image`` raises; no image
+        buffer is allocated; ``self.ray_index`` (ray_num,) int64 holds the drawn (v H + row) W + col of the last iteration.  The step
+        keeps references to both tensors (a captured graph holds their addresses): do not free or reallocate them, writing into them in
+        place is fine.  With V = 1 the iteration is bit-identical to the image-mode one on that image.  Data-parallel runs: with a
+        reducing ``flat_grads`` whose group has more than one rank, the seed becomes ``rank_seed(seed, rank)`` so that the ranks draw
+        different batches (rank 0 keeps the seed).
+        ``scene``, ``view_ids``, ``grad_clip`` and ``distortion`` are keyword-only."""
         if not isinstance(optimizer, Adam) or not optimizer.lr_on_device:
             raise ValueError("nerf_amd.training.TrainStep needs nerf_amd.optim.Adam(..., lr_on_device=True): the step must not read host state")
         self.prop_net, self.mip_net, self.opt = prop_net, mip_net, optimizer
@@ -75,11 +114,34 @@ class TrainStep:
         self.prop_normal = bool(prop_normal) and self.is_ref                              # (train.py: prop_normal only acts with a Ref-NeRF)
         dev = next(mip_net.parameters()).device
         H, W = image_hw
-        self.image = torch.zeros((3, H, W), dtype=torch.float32, device=dev)             # static inputs of the (captured) step
-        self.pose = torch.zeros((3, 4), dtype=torch.float32, device=dev)
+        self.image_hw = (int(H), int(W))
+        self.scene = None
+        if scene is None:
+            if view_ids is not None:
+                raise ValueError("nerf_amd.training.TrainStep: view_ids needs scene=(images, poses)")
+            self.image = torch.zeros((3, H, W), dtype=torch.float32, device=dev)         # static inputs of the (captured) step
+            self.pose = torch.zeros((3, 4), dtype=torch.float32, device=dev)
+        else:
+            images, poses = scene
+            for t, name in ((images, "images"), (poses, "poses")):
+                if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.device == dev):
+                    raise ValueError("nerf_amd.training.TrainStep: scene %s must be a contiguous fp32 tensor on the networks' device" % name)
+            if images.dim() != 4 or images.shape[1] != 3 or poses.dim() != 3 or tuple(poses.shape) != (images.shape[0], 3, 4):
+                raise ValueError("nerf_amd.training.TrainStep: scene = (images (V,3,H,W), poses (V,3,4)), got %s and %s"
+                                 % (tuple(images.shape), tuple(poses.shape)))
+            if tuple(images.shape[2:]) != self.image_hw:
+                raise ValueError("nerf_amd.training.TrainStep: image_hw %s is not the scene's %s" % (self.image_hw, tuple(images.shape[2:])))
+            self.scene = (images, poses)                                                  # (kept alive: a captured graph holds their addresses)
+            self.view_ids = ops.scene_view_ids(view_ids, images.shape[0], dev)
+            self.ray_index = torch.zeros((self.ray_num,), dtype=torch.int64, device=dev)
+            self.image = self.pose = None
         self.crop_xy = tuple(crop_xy)
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())                            # torch.manual_seed governs the whole run
+        if self.scene is not None and flat_grads is not None and flat_grads is not False:
+            import torch.distributed as dist
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size(flat_grads.group) > 1:
+                seed = rank_seed(seed, dist.get_rank(flat_grads.group))                   # the ranks of a data-parallel run draw different batches
         self.seed = torch.full((1,), seed, dtype=torch.int64, device=dev)
         self.loss = torch.zeros((), dtype=torch.float32, device=dev)
         self.img_loss = torch.zeros((), dtype=torch.float32, device=dev)
@@ -121,9 +183,14 @@ class TrainStep:
 
     # ---------------------------------------------------------------------------------------------------------------- the iteration
     def _body(self):
-        pixels, coords = randomFromOneImage(self.image, self.crop_xy)                     # pure indexing on the device (cached table)
-        pts, z_c, rgb_tgt, rays = ops.sample_training_rays_dev(pixels, coords, self.pose, self.fx, self.fy, self.near, self.far, self.ray_num,
-                                                               self.coarse_pnum, self.seed)            # train.py:160-162
+        if self.scene is not None:                                                        # one gather over the whole stack, read in place
+            pts, z_c, rgb_tgt, rays, _ = ops.sample_scene_rays(self.scene[0], self.scene[1], self.fx, self.fy, self.near, self.far, self.ray_num,
+                                                               self.coarse_pnum, seed_dev=self.seed, window=crop_window(*self.image_hw, self.crop_xy),
+                                                               view_ids=self.view_ids, index_out=self.ray_index)
+        else:
+            pixels, coords = randomFromOneImage(self.image, self.crop_xy)                 # pure indexing on the device (cached table)
+            pts, z_c, rgb_tgt, rays = ops.sample_training_rays_dev(pixels, coords, self.pose, self.fx, self.fy, self.near, self.far, self.ray_num,
+                                                                   self.coarse_pnum, self.seed)        # train.py:160-162
         dirs = rays[:, 3:]
         if self.prop_normal:
             pts.requires_grad_(True)                                                                    # train.py:165
@@ -192,6 +259,8 @@ class TrainStep:
     # ---------------------------------------------------------------------------------------------------------------- driving it
     def set_image(self, img: torch.Tensor, pose: torch.Tensor) -> None:
         """img (3,H,W) / (1,3,H,W), pose (3,4) / (1,3,4) -- device tensors; asynchronous device-to-device copies into the step's inputs"""
+        if self.scene is not None:
+            raise ValueError("nerf_amd.training.TrainStep: a scene-mode step draws from the whole stack and takes no image")
         self.image.copy_(img.reshape(self.image.shape), non_blocking=True)
         self.pose.copy_(pose.reshape(-1)[:12].reshape(3, 4), non_blocking=True)
 

@@ -53,6 +53,15 @@ def sample_pdf(bins, weights, N_samples, u: torch.Tensor = None):
 _COORD_TABLES = {}
 
 
+def crop_window(H: int, W: int, crop_xy: tuple):
+    """(x0, x1, y0, y1): the centre crop of utils.py:50-60 as column / row bounds (x0 <= col < x1, y0 <= row < y1); the whole image for a
+    crop factor of 1."""
+    hw, hh = W // 2, H // 2
+    x0, x1 = (int(hw * (1. - crop_xy[0])), int(hw + hw * crop_xy[0])) if crop_xy[0] < 9.9e-1 else (0, W)
+    y0, y1 = (int(hh * (1. - crop_xy[1])), int(hh + hh * crop_xy[1])) if crop_xy[1] < 9.9e-1 else (0, H)
+    return x0, x1, y0, y1
+
+
 def randomFromOneImage(img: torch.Tensor, crop_xy: tuple):
     """Flattened pixel table and integer (col - W//2, H//2 - row) coordinates, optionally centre-cropped
     (utils.py:47-69).  Pure indexing -- stays a torch gather on the image's device.  The coordinate table depends only on
@@ -62,8 +71,7 @@ def randomFromOneImage(img: torch.Tensor, crop_xy: tuple):
         img = img.squeeze(0)
     H, W = img.shape[1], img.shape[2]
     hw, hh = W // 2, H // 2
-    x0, x1 = (int(hw * (1. - crop_xy[0])), int(hw + hw * crop_xy[0])) if crop_xy[0] < 9.9e-1 else (0, W)
-    y0, y1 = (int(hh * (1. - crop_xy[1])), int(hh + hh * crop_xy[1])) if crop_xy[1] < 9.9e-1 else (0, H)
+    x0, x1, y0, y1 = crop_window(H, W, crop_xy)
     key = (H, W, x0, x1, y0, y1, str(img.device))
     hit = _COORD_TABLES.get(key)
     if hit is None:
@@ -103,6 +111,21 @@ def validSampler(rgbs: torch.Tensor, coords: torch.Tensor, cam_tf: torch.Tensor,
     u = torch.rand((ray_num, point_num)).to(dev)
     z, pts = ops.stratified_points(rays, base, u, res)
     return pts, z, rgb, rays
+
+
+def sceneSampler(images: torch.Tensor, poses: torch.Tensor, ray_num: int, point_num: int, focal, near: float, far: float, crop_xy=(1., 1.),
+                 view_ids=None, output_samples=True):
+    """The scene twin of ``validSampler(rng="philox")`` (an addition; the reference samples one image per iteration): random training
+    rays drawn uniformly over the (centre-cropped, ``crop_xy`` as in randomFromOneImage) pixels of ALL views of images (V,3,H,W) / poses
+    (V,3,4) -- or of the views ``view_ids`` names -- in ONE kernel launch that reads the stack in place, from a seed taken off torch's
+    CPU generator (reproducible under torch.manual_seed).
+    -> (pts (N,C,3), lengths (N,C), rgb (N,3), rays (N,6)) or (rgb, rays)."""
+    fx, fy = _focal_xy(focal)
+    seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+    pts, z, rgb, rays, _ = ops.sample_scene_rays(images, poses, fx, fy, near, far, ray_num, point_num if output_samples else 0, seed=seed,
+                                                 window=crop_window(images.shape[-2], images.shape[-1], crop_xy), view_ids=view_ids,
+                                                 want_samples=bool(output_samples), want_index=False)
+    return (pts, z, rgb, rays) if output_samples else (rgb, rays)
 
 
 def fov2Focal(fov, img_size):
