@@ -209,7 +209,48 @@ DEVINL void f8_flush_scales(char* sub_base, int lane, uint32_t scale_rec) {
 // stricter wait, never a weaker one).  Retired experiments, logs under profiles/: a vmcnt(0) "safe" stream (round 2), M0 declared
 // clobbered + power-of-two slot wrap (r03_lean_ring_ab.log: 169 fewer SALU per layer, no time), a store-aware wait ladder
 // (r04_store_aware_wait_ab.log: the waves do not wait for their stores), explicit sched_group_barrier interleaves.
-template <class P, int NSLOT = MLP_NSLOT>
+//
+// Resident fragments ("resident prefix"): a policy R names fragments of the consumption order that are loaded into LDS
+// ONCE per workgroup (behind everything else, at RES_LDS) instead of streamed through the ring in every tile.  Everything is decided at
+// compile time from the fragment index: next<F>() reads a resident fragment with the same ds_read_b128 from its fixed address and a
+// streamed one from the ring, whose cyclic stream is simply shorter; the order of the MFMAs and their operands does not change.
+//   resident(f)  fragment f of the consumption order stays in LDS        slot(f)    its index inside the resident area
+//   stream(f)    index of a streamed fragment inside the shortened cyclic stream
+// A code instance shared by several layers (the layer loops) evaluates these at the indices of ONE of them, so such layers -- and the
+// DEPTH fragments behind each, which the instance's last next<>() calls prefetch -- must be streamed and agree in stream(f) mod 2 FPC.
+struct NoResident {
+    static constexpr int N = 0;
+    static constexpr bool resident(int) { return false; }
+    static constexpr int slot(int) { return 0; }
+    static constexpr int stream(int f) { return f; }
+};
+// Resident: the first PRE and the last SUF fragments of the NFRAGS-fragment network (adjacent in the cyclic order) and HOLE_N fragments
+// from HOLE_A on.  The streamed rest is read from the packed blob where it lies: fragments PRE .. NFRAGS-SUF-1, skipping the hole.
+template <int NFRAGS, int PRE, int SUF, int HOLE_A = 0, int HOLE_N = 0>
+struct ResidentSet {
+    static constexpr int N = PRE + HOLE_N + SUF, N_STREAM = NFRAGS - N;
+    static constexpr int FIRST = PRE;                                  // first streamed fragment of the blob
+    static constexpr int HOLE_AT = HOLE_A - PRE;                       // stream index at which the hole is skipped
+    static constexpr int HOLE_FRAGS = HOLE_N;
+    static constexpr int wrap(int f) { return f >= NFRAGS ? f - NFRAGS : f; }      // (the last layer prefetches the next tile's first fragments)
+    static constexpr bool in_hole(int f) { return f >= HOLE_A && f < HOLE_A + HOLE_N; }
+    static constexpr bool resident(int f) { return wrap(f) < PRE || in_hole(wrap(f)) || wrap(f) >= NFRAGS - SUF; }
+    static constexpr int slot(int f) { return wrap(f) < PRE ? wrap(f) : (in_hole(wrap(f)) ? PRE + wrap(f) - HOLE_A : PRE + HOLE_N + wrap(f) - (NFRAGS - SUF)); }
+    static constexpr int stream(int f) { return wrap(f) - PRE - (wrap(f) >= HOLE_A + HOLE_N ? HOLE_N : 0); }
+    // blob fragment held by resident slot k
+    static constexpr int frag_of_slot(int k) { return k < PRE ? k : (k < PRE + HOLE_N ? HOLE_A + k - PRE : NFRAGS - SUF + k - PRE - HOLE_N); }
+    static_assert(PRE % 4 == 0 && SUF % 4 == 0 && HOLE_A % 4 == 0 && HOLE_N % 4 == 0, "resident runs start and end on prefetch-queue boundaries");
+    static_assert(HOLE_N == 0 || (HOLE_A >= PRE && HOLE_A + HOLE_N <= NFRAGS - SUF), "the hole lies inside the streamed range");
+};
+// layers [code, code + n) and [real, real + n) may share a code instance (n = the layer's fragments + the DEPTH prefetched behind it)
+template <class R, int FPC>
+constexpr bool same_stream_shape(int code, int real, int n) {
+    for (int i = 0; i < n; ++i)
+        if (R::resident(code + i) || R::resident(real + i) || R::stream(code + i) % (2 * FPC) != R::stream(real + i) % (2 * FPC)) return false;
+    return true;
+}
+
+template <class P, int NSLOT = MLP_NSLOT, class R = NoResident, uint32_t RES_LDS = 0>
 struct WeightStream {
     static constexpr int LPW = (MLP_CHUNK_BYTES / 1024) / P::NW;     // 1 KiB glds pieces per wave per chunk
     const char* src;        // packed stream + this lane's offset inside a chunk
@@ -224,6 +265,9 @@ struct WeightStream {
     template <class T> static DEVINL void dummy_sink(const T& d) { asm volatile("" ::"v"(d.lo), "v"(d.hi)); }
     DEVINL void issue() {
         const char* g = src + (size_t)load_idx * MLP_CHUNK_BYTES;
+        if constexpr (R::N > 0) {                                            // (a scalar select: load_idx is wave-uniform)
+            if constexpr (R::HOLE_FRAGS > 0) g += (load_idx >= (uint32_t)(R::HOLE_AT / P::FPC)) ? R::HOLE_FRAGS * P::FRAG_BYTES : 0;
+        }
         const uint32_t dst = __builtin_amdgcn_readfirstlane(load_slot * MLP_CHUNK_BYTES + wave_lds);
         // global -> LDS DMA (16 B/lane, lane-linear).  Issued through inline asm on purpose: hipcc's waitcnt pass treats
         // the builtin form as a "flat" access that may touch LDS and from then on turns EVERY s_waitcnt lgkmcnt(N) of
@@ -263,28 +307,62 @@ struct WeightStream {
     static constexpr int INFLIGHT = (TWO_GROUPS ? NSLOT - 5 : NSLOT - 4) * LPW;
     uint32_t late;
 
+    // queue slot I <- fragment I of the first tile
+    template <int I = 0>
+    DEVINL void preload() {
+        if constexpr (I < P::DEPTH) {
+            if constexpr (R::resident(I)) q[I] = P::load_a(RES_LDS + R::slot(I) * P::FRAG_BYTES + lane_id() * 16);
+            else q[I] = P::load_a(cur + R::stream(I) * P::FRAG_BYTES);
+            preload<I + 1>();
+        }
+    }
+    // the resident fragments: wave w fetches slots w, w + NW, ... (1 KiB pieces, the same LDS-DMA as issue()), once per workgroup
+    template <int K = 0>
+    DEVINL void load_resident(const char* blob_lane, int wave) {
+        if constexpr (K < R::N) {
+            const char* g = blob_lane + (size_t)(R::frag_of_slot(K) + wave) * 1024;     // (runs are multiples of NW: slots K .. K+NW-1 are one run)
+            const uint32_t dst = __builtin_amdgcn_readfirstlane(RES_LDS + (K + wave) * 1024);
+            unsigned keep;
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                         : "=&s"(keep)
+                         : "v"(g), "s"(dst)
+                         : "memory");
+            load_resident<K + P::NW>(blob_lane, wave);
+        }
+    }
     DEVINL void init(const void* packed, uint32_t nchunks) {
         static_assert(NSLOT >= 6, "the protocol needs at least 6 ring slots");
         const int lane = lane_id();
         const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
         src = reinterpret_cast<const char*>(packed) + (size_t)wave * LPW * 1024 + lane * 16;
+        if constexpr (R::N > 0) {
+            static_assert(P::FRAG_BYTES == 1024 && P::NW == 4 && R::N % P::NW == 0, "resident fragments: the bf16 four-wave tile");
+            static_assert(R::FIRST >= P::DEPTH, "a tile starts on resident fragments (boundary 0 is left to next<>())");
+            static_assert(R::N_STREAM % (2 * P::FPC) == 0 && R::HOLE_AT % P::FPC == 0, "the shortened stream: an even number of chunks, the hole between two chunks");
+            load_resident(reinterpret_cast<const char*>(packed) + lane * 16, wave);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // landed before the ring's pieces are counted; the barrier below publishes them
+            src += (size_t)R::FIRST * P::FRAG_BYTES;
+        }
         wave_lds = wave * LPW * 1024;
         n_chunks = nchunks;
         load_idx = 0; load_slot = 0;
-        cur_slot = 0;
-        cur = lane * 16;
+        // (resident first fragments: the register prefetch has not entered chunk 0 yet -- next<>() of the first streamed fragment runs
+        //  boundary 0 like every later tile's, stepping from the last ring slot to slot 0)
+        cur_slot = (R::N > 0) ? NSLOT - 1 : 0;
+        cur = cur_slot * MLP_CHUNK_BYTES + lane * 16;
         late = __builtin_amdgcn_readfirstlane((P::NW > 4 && wave >= P::NW / 2) ? 1 : 0);
 #pragma unroll
         for (int i = 0; i < NSLOT - 2; ++i) issue();                         // chunks 0 .. NSLOT-3
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(INFLIGHT) : "memory");   // my pieces of chunks 0..2 have landed ...
         __builtin_amdgcn_s_barrier();                                        // ... and everybody else's
         asm volatile("" ::: "memory");
-#pragma unroll
-        for (int i = 0; i < P::DEPTH; ++i) q[i] = P::load_a(cur + i * P::FRAG_BYTES);
-        if (!late) {                                                         // boundary 0 of the early waves
-            __builtin_amdgcn_s_barrier();                                    // barrier 0 (late waves: at their boundary 1)
-            asm volatile("" ::: "memory");
-            issue();                                                         // chunk NSLOT-2
+        preload();
+        if constexpr (R::N == 0) {
+            if (!late) {                                                     // boundary 0 of the early waves
+                __builtin_amdgcn_s_barrier();                                // barrier 0 (late waves: at their boundary 1)
+                asm volatile("" ::: "memory");
+                issue();                                                     // chunk NSLOT-2
+            }
         }
     }
     // Fragment F of the stream (compile-time index, F mod DEPTH == queue slot): hand out its registers and
@@ -293,13 +371,17 @@ struct WeightStream {
     template <int F>
     DEVINL typename P::AReg next() {
         const typename P::AReg a = q[F % P::DEPTH];
-        constexpr int G = F + P::DEPTH;
-        if (G % P::FPC == 0) {
-            cur_slot = (cur_slot + 1 == NSLOT) ? 0u : cur_slot + 1;
-            cur = cur_slot * MLP_CHUNK_BYTES + lane_id() * 16;
-            boundary<(G / P::FPC) & 1>();
+        if constexpr (R::resident(F + P::DEPTH)) {                // resident: a fixed LDS address, the ring does not move
+            q[F % P::DEPTH] = P::load_a(RES_LDS + R::slot(F + P::DEPTH) * P::FRAG_BYTES + lane_id() * 16);
+        } else {
+            constexpr int G = R::stream(F + P::DEPTH);
+            if (G % P::FPC == 0) {
+                cur_slot = (cur_slot + 1 == NSLOT) ? 0u : cur_slot + 1;
+                cur = cur_slot * MLP_CHUNK_BYTES + lane_id() * 16;
+                boundary<(G / P::FPC) & 1>();
+            }
+            q[F % P::DEPTH] = P::load_a(cur + (G % P::FPC) * P::FRAG_BYTES);
         }
-        q[F % P::DEPTH] = P::load_a(cur + (G % P::FPC) * P::FRAG_BYTES);
         return a;
     }
     template <int PARITY>

@@ -254,6 +254,61 @@ template <class P> constexpr uint32_t lds_dir() { return LDS_STASH + P::NW * P::
 template <class P> constexpr uint32_t lds_tile() { return lds_dir<P>() + P::NW * P::NT * 1024; }            // fused compositing: (tile samples) x 2 float4, segment totals, tickets
 template <class P> constexpr uint32_t lds_total() { return lds_tile<P>() + P::NW * P::NT * 32 * 32 + P::NW * P::NT * 8 + 64; }   // records, segment totals, tickets
 
+// ------------------------------------------------------------------------------------------------
+// Resident weights (mlp_core.h ResidentSet): the two inference kernels of the bf16 render path --
+// proposal_kernel<PBF16W, false> and mip_kernel<PBF16W, false, false, false, false> -- keep a part of the network in LDS for the whole
+// launch and stream the rest.  Every other instantiation (fp32, training, IPE, fused compositing, the narrow and Ref-NeRF kernels) keeps
+// the plain stream and the LDS map above.  -DMLP_RESIDENT=0 (or per kernel -DMLP_RESIDENT_PROP=0 / -DMLP_RESIDENT_MIP=0) restores the
+// plain kernels for A/B runs (Makefile: variant_tu).
+//   proposal  resident: layers.0 (fragments 0..31) + 64 fragments of layers.4 (168..231); stream 336 fragments = 42 chunks.
+//             LDS: ring 6 x 8 | biases 9 | resident 96                                              = 153 KiB
+//   MipNeRF   resident: lin_block1.0 (0..31) + the network's last 32 fragments (896..927: the end of rgb_layer.0' and rgb_layer.2);
+//             stream 864 fragments = 108 chunks.
+//             LDS: ring 6 x 8 | biases 7.75 | encoding stash 32 | direction 8 | resident 64         = 159.75 KiB
+// The layers that share a code instance (and the four fragments behind each, which the instance prefetches) are streamed and keep
+// their chunk parity in stream space -- asserted in the kernels.
+// ------------------------------------------------------------------------------------------------
+#ifndef MLP_RESIDENT
+#define MLP_RESIDENT 1
+#endif
+#ifndef MLP_RESIDENT_PROP
+#define MLP_RESIDENT_PROP MLP_RESIDENT
+#endif
+#ifndef MLP_RESIDENT_MIP
+#define MLP_RESIDENT_MIP MLP_RESIDENT
+#endif
+#ifndef MLP_RES_PROP_NSLOT
+#define MLP_RES_PROP_NSLOT 6
+#endif
+#ifndef MLP_RES_PROP_HOLE
+#define MLP_RES_PROP_HOLE 64         /* resident fragments of layers.4, from fragment 168 on (a multiple of 16; at most 48 with 8 ring slots) */
+#endif
+#ifndef MLP_RES_MIP_NSLOT
+#define MLP_RES_MIP_NSLOT 6
+#endif
+#ifndef MLP_RES_MIP_TAIL
+#define MLP_RES_MIP_TAIL 32          /* resident fragments at the end of the network (0 or 16 with 8 ring slots, 32 with 6) */
+#endif
+template <class A, class B> struct same_type { static constexpr bool value = false; };
+template <class A> struct same_type<A, A> { static constexpr bool value = true; };
+template <bool C, class A, class B> struct conditional_type { using type = A; };
+template <class A, class B> struct conditional_type<false, A, B> { using type = B; };
+
+struct PropResident {
+    using R = ResidentSet<PropLayout::N_FRAGS, 32, 0, 168, MLP_RES_PROP_HOLE>;
+    static constexpr int NSLOT = MLP_RES_PROP_NSLOT;
+    static constexpr uint32_t RING = NSLOT * MLP_CHUNK_BYTES, BIAS = RING, RES = RING + 9216, TOTAL = RES + R::N * 1024;
+    static_assert(TOTAL <= 160 * 1024, "LDS");
+};
+struct MipResident {
+    using R = ResidentSet<MipLayout::N_FRAGS, 32, MLP_RES_MIP_TAIL>;
+    static constexpr int NSLOT = MLP_RES_MIP_NSLOT;
+    // (no fused-compositing records; the bias table is exactly MipLayout::N_BIAS floats)
+    static constexpr uint32_t RING = NSLOT * MLP_CHUNK_BYTES, BIAS = RING, STASH = BIAS + MipLayout::N_BIAS * 4, DIR = STASH + 4 * 2 * 4 * 1024,
+                              RES = DIR + 4 * 2 * 1024, TOTAL = RES + R::N * 1024;
+    static_assert(TOTAL <= 160 * 1024, "LDS");
+};
+
 DEVINL void load_biases(const void* packed, size_t stream_bytes, int n_bias, uint32_t lds_off = MLP_RING_BYTES) {
     const float* b = reinterpret_cast<const float*>(reinterpret_cast<const char*>(packed) + stream_bytes);
     float* dst = reinterpret_cast<float*>(smem + lds_off);
@@ -356,15 +411,18 @@ __global__ __launch_bounds__(P::NW * 64) void proposal_kernel(const void* __rest
     using L = PropLayout;
     using BReg = typename P::BReg;
     constexpr int FPC = P::FPC;
-    load_biases(packed, L::stream_bytes(P::PREC), L::N_BIAS);
-    WeightStream<P, MLP_NSLOT> ws;
-    ws.init(packed, L::N_FRAGS / FPC);
+    constexpr bool RES = MLP_RESIDENT_PROP && same_type<P, PBF16W>::value && !TRAIN;        // resident weights: see PropResident
+    using R = typename conditional_type<RES, PropResident::R, NoResident>::type;
+    using WS = typename conditional_type<RES, WeightStream<P, PropResident::NSLOT, R, PropResident::RES>, WeightStream<P, MLP_NSLOT>>::type;
+    constexpr uint32_t bias0 = RES ? PropResident::BIAS : MLP_RING_BYTES;
+    load_biases(packed, L::stream_bytes(P::PREC), L::N_BIAS, bias0);
+    WS ws;
+    ws.init(packed, (L::N_FRAGS - R::N) / FPC);
     const int lane = lane_id(), h = lane >> 5, j = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (wave-uniform: lets address arithmetic on it run on the scalar unit)
     constexpr int NT = P::NT;
     constexpr int TS = P::NW * NT * 32;
     const int64_t n_tiles = (s.M + TS - 1) / TS;
-    const uint32_t bias0 = MLP_RING_BYTES;
     const uint32_t macc = lds_maskacc<P>() + wave * 2 * NT * 1024;      // TRAIN: this wave's ReLU bit-mask records
     const uint32_t sacc = lds_scaleacc<P>() + wave * 2 * NT * 1024;     // F8: this wave's scale-exponent records
     if constexpr (TRAIN) mask_acc_init<P>(macc, lane);
@@ -421,7 +479,7 @@ __global__ __launch_bounds__(P::NW * 64) void proposal_kernel(const void* __rest
             [&](int kg, int t) -> BReg { return enc[t][kg]; }, OA, NoPrev{});
         // layers.2/4/6 ping-pong between the two register buffers (a -> b -> a -> b): no copies; the two a->b layers
         // share one code instance through the loop (same chunk parity, asserted)
-        static_assert(L::START[1] % (2 * FPC) == L::START[3] % (2 * FPC), "chunk parity");
+        static_assert(same_stream_shape<R, FPC>(L::START[1], L::START[3], 128 + P::DEPTH), "chunk parity (in stream space) of the shared a -> b instance");
         auto IN_B = [&](int kg, int t) -> BReg { return b[t][kg]; };
 #pragma unroll 1
         for (int r = 0; r < 2; ++r) {
@@ -534,21 +592,25 @@ __global__ __launch_bounds__(P::NW * 64) void mip_kernel(const void* __restrict_
     const uint64_t probe_c0 = __builtin_readcyclecounter(), probe_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
     if constexpr (FUSED) { if (threadIdx.x < 16) reinterpret_cast<unsigned*>(smem + lds_tile<P>() + P::NW * P::NT * 32 * 32 + P::NW * P::NT * 8)[threadIdx.x] = 0u; }  // ray tickets
-    load_biases(packed, L::stream_bytes(P::PREC), L::N_BIAS);
-    WeightStream<P, MLP_NSLOT> ws;
-    ws.init(packed, L::N_FRAGS / FPC);
+    constexpr bool RES = MLP_RESIDENT_MIP && same_type<P, PBF16W>::value && !TRAIN && !IPE && !F8 && !FUSED;   // resident weights: see MipResident
+    using R = typename conditional_type<RES, MipResident::R, NoResident>::type;
+    using WS = typename conditional_type<RES, WeightStream<P, MipResident::NSLOT, R, MipResident::RES>, WeightStream<P, MLP_NSLOT>>::type;
+    constexpr uint32_t bias0 = RES ? MipResident::BIAS : LDS_BIAS;
+    constexpr uint32_t stash_lds = RES ? MipResident::STASH : LDS_STASH, dirs_lds = RES ? MipResident::DIR : lds_dir<P>();
+    load_biases(packed, L::stream_bytes(P::PREC), L::N_BIAS, bias0);
+    WS ws;
+    ws.init(packed, (L::N_FRAGS - R::N) / FPC);
     const int lane = lane_id(), h = lane >> 5, j = lane & 31;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (wave-uniform: lets address arithmetic on it run on the scalar unit)
     constexpr int NT = P::NT;
     constexpr int TS = P::NW * NT * 32;
     const int64_t n_tiles = (s.M + TS - 1) / TS;
-    const uint32_t bias0 = LDS_BIAS;
     const uint32_t macc = lds_maskacc<P>() + wave * 2 * NT * 1024;      // TRAIN: this wave's ReLU bit-mask records
     const uint32_t sacc = lds_scaleacc<P>() + wave * 2 * NT * 1024;     // F8: this wave's scale-exponent records
     if constexpr (TRAIN) mask_acc_init<P>(macc, lane);
     // per 32-sample column tile ("subtile" sub = wave*NT + t) LDS slots
-    const uint32_t enc_lds0 = LDS_STASH + wave * NT * 4 * P::BREG_LDS + lane * 16;
-    const uint32_t dir_lds0 = lds_dir<P>() + wave * NT * 1024 + lane * 16;
+    const uint32_t enc_lds0 = stash_lds + wave * NT * 4 * P::BREG_LDS + lane * 16;
+    const uint32_t dir_lds0 = dirs_lds + wave * NT * 1024 + lane * 16;
     auto enc_lds = [&](int t) -> uint32_t { return enc_lds0 + t * 4 * P::BREG_LDS; };
     auto dir_lds = [&](int t) -> uint32_t { return dir_lds0 + t * 1024; };
 
@@ -645,8 +707,8 @@ __global__ __launch_bounds__(P::NW * 64) void mip_kernel(const void* __restrict_
         // so nothing is ever copied; three loop rounds of (a->b layer, then the skip layer or a b->a layer) keep it at three code
         // instances.  A loop may only reuse an instance for layers whose first chunk has the same parity (the early/late
         // barrier assignment is compiled in) and whose biases are evenly spaced -- asserted.
-        static_assert(L::START[1] % (2 * FPC) == L::START[3] % (2 * FPC) && L::START[1] % (2 * FPC) == L::START[5] % (2 * FPC) &&
-                      L::START[2] % (2 * FPC) == L::START[6] % (2 * FPC) && L::BIAS_OFF[6] == 6 * 256, "uniform layer loop");
+        static_assert(same_stream_shape<R, FPC>(L::START[1], L::START[3], 128 + P::DEPTH) && same_stream_shape<R, FPC>(L::START[1], L::START[5], 128 + P::DEPTH) &&
+                      same_stream_shape<R, FPC>(L::START[2], L::START[6], 128 + P::DEPTH) && L::BIAS_OFF[6] == 6 * 256, "uniform layer loop (chunk parity in stream space)");
         auto IN_B = [&](int kg, int t) -> BReg { return b[t][kg]; };
 #pragma unroll 1
         for (int r = 0; r < 3; ++r) {
@@ -1234,12 +1296,13 @@ int grid_for(int64_t n_tiles) {
 // Dynamic LDS above 64 KiB is an opt-in per KERNEL FUNCTION and device (host_common.h)
 int allow_dynamic_lds(const void* fn, size_t lds) { return nerf_host::allow_dynamic_lds(fn, lds); }
 
-template <class P, class Lay, bool TRAIN = false, bool F8 = false, class K, class... Extra>
+// LDS_FIXED: the LDS map of an instantiation with resident weights (PropResident / MipResident), 0 = the common map
+template <class P, class Lay, bool TRAIN = false, bool F8 = false, size_t LDS_FIXED = 0, class K, class... Extra>
 int launch(K kernel, const void* packed, const nerf_amd_samples& s, float* out, hipStream_t st, Extra... extra) {
     constexpr int TS = P::NW * P::NT * 32;
     const int64_t n_tiles = (s.M + TS - 1) / TS;
     if (n_tiles == 0) return 0;
-    const size_t lds = F8 ? lds_total_train_f8<P>() : (TRAIN ? lds_total_train<P>() : lds_total<P>());
+    const size_t lds = LDS_FIXED ? LDS_FIXED : (F8 ? lds_total_train_f8<P>() : (TRAIN ? lds_total_train<P>() : lds_total<P>()));
     if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds)) return e;
     hipLaunchKernelGGL(kernel, dim3(grid_for(n_tiles)), dim3(P::NW * 64), lds, st, packed, s, out, extra...);
     return (int)hipGetLastError();
@@ -1259,7 +1322,8 @@ using PB16 = PBF16W;
 #endif
 #if MLP_TU == 0 || MLP_TU == 1
 int mlp_launch_proposal(const void* packed, int precision, const nerf_amd_samples& s, float* density, hipStream_t st) {
-    if (precision == NERF_AMD_BF16) return launch<PB16, PropLayout>(proposal_kernel<PB16, false>, packed, s, density, st, NO_DUMP);
+    if (precision == NERF_AMD_BF16)
+        return launch<PB16, PropLayout, false, false, (MLP_RESIDENT_PROP ? PropResident::TOTAL : 0)>(proposal_kernel<PB16, false>, packed, s, density, st, NO_DUMP);
     return launch<PF32, PropLayout>(proposal_kernel<PF32, false>, packed, s, density, st, NO_DUMP);
 }
 #endif
@@ -1270,7 +1334,8 @@ int mlp_launch_mip(const void* packed, int precision, const nerf_amd_samples& s,
         if (precision == NERF_AMD_BF16) return launch<PB16, MipLayout>(mip_kernel<PB16, false, true>, packed, s, rgbo, st, off, NO_DUMP);
         return launch<PF32, MipLayout>(mip_kernel<PF32, false, true>, packed, s, rgbo, st, off, NO_DUMP);
     }
-    if (precision == NERF_AMD_BF16) return launch<PB16, MipLayout>(mip_kernel<PB16, false>, packed, s, rgbo, st, off, NO_DUMP);
+    if (precision == NERF_AMD_BF16)
+        return launch<PB16, MipLayout, false, false, (MLP_RESIDENT_MIP ? MipResident::TOTAL : 0)>(mip_kernel<PB16, false>, packed, s, rgbo, st, off, NO_DUMP);
     return launch<PF32, MipLayout>(mip_kernel<PF32, false>, packed, s, rgbo, st, off, NO_DUMP);
 }
 // packed = nerf_amd_pack_weights(NERF_AMD_NET_MIP_128, ...); point PE only (the C-ABI refuses s.ipe with this layout)
