@@ -483,6 +483,49 @@ int    nerf_amd_render_rays(const void* packed_prop, const void* packed_mip, int
                             float near, float far, int white_bkg,
                             float* rgb, float* depth, float* weights, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Disparity ray spacing for unbounded scenes (Mip-NeRF 360, Barron et al. 2022, section 3 and eq. 11-13 with g(x) = 1/x).  Not in the
+ * reference: like the contraction this is the build's own definition, parity unpinned.  Samples are drawn and
+ * resampled in the normalised distance s in [0, 1], which is uniform in disparity; networks, weights and compositing see metric depths.
+ *   constants  gn = fp32(1/near), gf = fp32(1/far): each computed in double and rounded once by the entry point; 0 < near < far
+ *   warp       W(s)    = 1 / ((1 - sb) gn + sb gf),   sb = clamp(s, 0, 1)
+ *   inverse    W^-1(z) = (1/zb - gn) / (gf - gn),     zb = clamp(z, near, far)
+ *              every operation one fp32 rounding in exactly this order (no FMA), IEEE division
+ *   coarse     s_j = (float)j r + u r, r = fp32(1/C), j = 0..C-1 (the training sampler's expression at near = 0, far = 1; the reference
+ *              render's jitter quirk (far - near)/sample_num is NOT carried into s: it would push s past 1, the warp's pole side)
+ *   resample   bins = mid-points of s_c, pdf = maxBlur(get_weights(density, W(s_c) |d|))[1:-1] + 1e-5, K sorted draws s_f, z_f = W(s_f);
+ *              `below` keeps its meaning (nerf_amd_get_bounds is untouched)
+ *   depth      W^-1(sum w z |d|) in [0, 1]
+ * `spacing` must be NERF_AMD_SPACING_DISPARITY in every entry point below (anything else: NERF_AMD_EINVAL); linear spacing is what all
+ * the other entry points do and never reaches this code.
+ * ------------------------------------------------------------------------------------------------ */
+#define NERF_AMD_SPACING_LINEAR    0
+#define NERF_AMD_SPACING_DISPARITY 1
+/* Elementwise over in (N,S), N >= 0, S >= 1: out = W(in), or with inverse != 0 out = W^-1(in).  pts (N,S,3) = o + out d from rays (N,6)
+ * with the arithmetic of nerf_amd_stratified_points, or NULL to skip (forward only). */
+int nerf_amd_warp_depths(const float* in, const float* rays, int64_t N, int S, int inverse, int spacing, float near, float far,
+                         float* out, float* pts, void* stream);
+/* The coarse draw: u (N,C) -- or NULL: word 0 of the 'RS' Philox block of global ray n + rng_ray_offset, the stratified stream of
+ * nerf_amd_samples -- -> s_c (N,C), z_c (N,C) = W(s_c), pts (N,C,3) = o + z_c d or NULL.  3 <= C <= 256 (C <= 64 with u == NULL: the
+ * stream's 64 slots). */
+int nerf_amd_warped_stratified(const float* rays, const float* u, int64_t N, int C, uint64_t rng_seed, int64_t rng_ray_offset, int spacing,
+                               float near, float far, float* s_c, float* z_c, float* pts, void* stream);
+/* nerf_amd_resample's twin (one wavefront per ray, the same device functions for weights and inverse sampling): density (N,C) and
+ * s_c (N,C) -> z_fine (N,K) = W(s_fine), optional s_fine (N,K) sorted, below (N,K) int64, w_prop (N,C).  u_inv (N,K), or NULL: words
+ * 1..3 of the 'RS' blocks as in nerf_amd_resample.  3 <= C <= 256, 1 <= K <= 1024 and 4 (5 C + 4 K + 1280) floats of LDS <= 64 KiB. */
+int nerf_amd_warped_resample(const float* density, const float* s_c, const float* dirs, int dirs_stride, const float* u_inv, int64_t N, int C,
+                             int K, int softplus_density, float blur_alpha, int spacing, float near, float far, uint64_t rng_seed,
+                             int64_t rng_ray_offset, float* z_fine, float* s_fine, int64_t* below, float* w_prop, void* stream);
+/* nerf_amd_render_rays under disparity spacing (non-Ref), six launches: coarse draw -> proposal MLP (explicit z_c) -> warped resample
+ * -> fine MLP (explicit z_fine; contract / ipe carried by `camera` as in nerf_amd_render_rays) -> composite -> depth = W^-1(sum w z |d|).
+ * Arguments as nerf_amd_render_rays without z_base; every argument is validated before the first launch.  n_fine <= 623: the LDS bound of
+ * nerf_amd_warped_resample at C = 64, K = n_fine + 1. */
+size_t nerf_amd_render_warped_workspace_bytes(int64_t N, int n_fine);
+int    nerf_amd_render_rays_warped(const void* packed_prop, const void* packed_mip, int precision, const float* rays,
+                                   const nerf_amd_samples* camera, int64_t ray_offset, const float* u_strat, const float* u_inv, int64_t N,
+                                   int n_fine, int spacing, float near, float far, int white_bkg, float* rgb, float* depth, float* weights,
+                                   void* workspace, void* stream);
+
 /* The same tile body for a Ref-NeRF fine network (procedures.py:64-85 with the is_ref_model branch, lines 71-74): proposal pass,
  * resampling, the n_fine+1 fine and 64 coarse depths merged (the last one dropped), Ref-NeRF MLP on the n_fine+64 samples,
  * compositing with sigma -> softplus(sigma + 0.5).  normal_img (N) and cam_dir (3 floats on the device: render_pose[:, -2]) are

@@ -17,6 +17,8 @@ NET_PROPOSAL, NET_MIP, NET_REF, NET_PROPOSAL_128, NET_MIP_128 = 0, 1, 2, 3, 4
 FINE_W128 = 0x200     # layout flag: the fine-network blob is a NET_MIP_128 blob
 PROP_W128 = 0x100     # layout flag OR-ed into `precision`: packed_prop is a NET_PROPOSAL_128 blob
 ACT_RELU, ACT_IDENTITY, ACT_SOFTPLUS = 0, 1, 2
+SPACING_LINEAR, SPACING_DISPARITY = 0, 1   # NERF_AMD_SPACING_*: "disparity" = the Mip-NeRF 360 s-space entry points (nerf_amd_warp*)
+SPACINGS = {"linear": SPACING_LINEAR, "disparity": SPACING_DISPARITY}
 
 c_float_p = C.POINTER(C.c_float)
 c_void = C.c_void_p
@@ -120,6 +122,13 @@ SIGNATURES = {
     "nerf_amd_render_workspace_bytes": (C.c_size_t, [i64, C.c_int]),
     "nerf_amd_render_rays": (C.c_int, [c_void, c_void, C.c_int, c_void, C.POINTER(Samples), i64, c_void, c_void, c_void, i64,
                                        C.c_int, C.c_float, C.c_float, C.c_int, c_void, c_void, c_void, c_void, c_void]),
+    "nerf_amd_warp_depths": (C.c_int, [c_void, c_void, i64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, c_void, c_void, c_void]),
+    "nerf_amd_warped_stratified": (C.c_int, [c_void, c_void, i64, C.c_int, C.c_uint64, i64, C.c_int, C.c_float, C.c_float, c_void, c_void, c_void, c_void]),
+    "nerf_amd_warped_resample": (C.c_int, [c_void, c_void, c_void, C.c_int, c_void, i64, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, C.c_float,
+                                           C.c_float, C.c_uint64, i64, c_void, c_void, c_void, c_void, c_void]),
+    "nerf_amd_render_warped_workspace_bytes": (C.c_size_t, [i64, C.c_int]),
+    "nerf_amd_render_rays_warped": (C.c_int, [c_void, c_void, C.c_int, c_void, C.POINTER(Samples), i64, c_void, c_void, i64, C.c_int, C.c_int,
+                                              C.c_float, C.c_float, C.c_int, c_void, c_void, c_void, c_void, c_void]),
     "nerf_amd_gemm_workspace_bytes": (C.c_size_t, [i64, i64, i64]),
     "nerf_amd_gemm": (C.c_int, [C.c_int, i64, i64, i64, c_void, i64, i64, c_void, i64, i64, c_void, i64, c_void, C.c_int, c_void, i64, c_void, c_void]),
     "nerf_amd_sigmoid_backward": (C.c_int, [c_void, i64, c_void, i64, i64, C.c_int, c_void, i64, c_void]),

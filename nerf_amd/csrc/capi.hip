@@ -91,6 +91,11 @@ int sk_resample(const float*, const float*, const float*, const float*, float, c
 int sk_composite(const float*, const float*, int, const float*, int, int64_t, int, int, int, float, float, float, const float*,
                  const float*, float*, float*, float*, float*, hipStream_t);
 int sk_get_bounds(const float*, const int64_t*, int64_t, int, int, float*, hipStream_t);
+int sk_warp_depths(const float*, const float*, int64_t, int, int, float, float, float, float, float*, float*, hipStream_t);
+int sk_warped_stratified(const float*, const float*, int64_t, int, uint64_t, int64_t, float, float, float, float, float*, float*, float*, hipStream_t);
+size_t sk_warped_resample_lds_bytes(int, int);
+int sk_warped_resample(const float*, const float*, const float*, int, const float*, int64_t, int, int, int, float, float, float, float, float, uint64_t,
+                       int64_t, float*, float*, int64_t*, float*, hipStream_t);
 int sk_weights_backward(const float*, int, int, const float*, int, const float*, int, int64_t, int, int, int, float, const float*, const float*,
                         const float*, const float*, int, float, float, float*, int, int, float*, hipStream_t);
 int sk_max_blur_backward(const float*, const float*, int64_t, int, float*, hipStream_t);
@@ -136,6 +141,22 @@ int check_distortion(int64_t N, int Sn, int mode) {
     if (N < 0) return fail(NERF_AMD_EINVAL, "negative ray count");
     if (mode != 0 && mode != 1) return fail(NERF_AMD_EINVAL, "unknown mode (0: Regularizer, 1: Mip-NeRF 360 L_dist)");
     if (Sn < 2 || Sn > NERF_AMD_DISTORTION_MAX_S) return fail(NERF_AMD_EINVAL, "bad size (S must be 2..1024 depths per row: a ray's rows live in LDS)");
+    return NERF_AMD_OK;
+}
+// disparity ray spacing: 0 < near < far, the only kind the warped entry points accept; gn = fp32(1/near), gf = fp32(1/far), each computed in
+// double and rounded once
+int check_spacing(int spacing, float near, float far, float* gn, float* gf) {
+    if (spacing != NERF_AMD_SPACING_DISPARITY) return fail(NERF_AMD_EINVAL, "unknown spacing (the warped entry points take NERF_AMD_SPACING_DISPARITY only)");
+    if (!(near > 0.0f)) return fail(NERF_AMD_EINVAL, "disparity spacing needs near > 0");
+    if (!(far > near) || !(far <= 3.0e38f)) return fail(NERF_AMD_EINVAL, "disparity spacing needs near < far (finite)");
+    *gn = (float)(1.0 / (double)near);
+    *gf = (float)(1.0 / (double)far);
+    if (!(*gf < *gn)) return fail(NERF_AMD_EINVAL, "disparity spacing: 1/near and 1/far coincide in fp32");
+    return NERF_AMD_OK;
+}
+int check_warped_resample_shape(int C, int K) {
+    if (C < 3 || C > 256 || K < 1 || K > 1024) return fail(NERF_AMD_EINVAL, "need 3 <= C <= 256 and 1 <= K <= 1024");
+    if (sk_warped_resample_lds_bytes(C, K) > 65536) return fail(NERF_AMD_EINVAL, "C and K too large: the per-ray rows of four rays must fit 64 KiB of LDS");
     return NERF_AMD_OK;
 }
 }  // namespace
@@ -767,6 +788,115 @@ int nerf_amd_render_rays(const void* packed_prop, const void* packed_mip, int pr
     const int flags = 1 | (white_bkg ? 2 : 0);              // row 10
     if (int e = sk_composite(rgbo, z_fine, n_fine + 1, rays + 3, 6, N, n_fine, flags, NERF_AMD_ACT_RELU, 0.0f, near, far, nullptr,
                              nullptr, rgb, weights, depth, nullptr, st)) return hip_status(e, "composite");
+    return NERF_AMD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ disparity ray spacing
+int nerf_amd_warp_depths(const float* in, const float* rays, int64_t N, int Sn, int inverse, int spacing, float near, float far, float* out, float* pts,
+                         void* stream) {
+    float gn, gf;
+    if (int e = check_spacing(spacing, near, far, &gn, &gf)) return e;
+    if (N < 0 || Sn < 1) return fail(NERF_AMD_EINVAL, "need N >= 0 and S >= 1");
+    if (N && (!in || !out || (pts && !rays))) return fail(NERF_AMD_EINVAL, "NULL argument");
+    if (pts && inverse) return fail(NERF_AMD_EINVAL, "pts are positions o + z d: not with inverse");
+    return hip_status(sk_warp_depths(in, rays, N, Sn, inverse ? 1 : 0, near, far, gn, gf, out, pts, S(stream)), "nerf_amd_warp_depths");
+}
+
+int nerf_amd_warped_stratified(const float* rays, const float* u, int64_t N, int C, uint64_t rng_seed, int64_t rng_ray_offset, int spacing, float near,
+                               float far, float* s_c, float* z_c, float* pts, void* stream) {
+    float gn, gf;
+    if (int e = check_spacing(spacing, near, far, &gn, &gf)) return e;
+    if (N < 0 || C < 3 || C > 256) return fail(NERF_AMD_EINVAL, "need N >= 0 and 3 <= C <= 256");
+    if (!u && C > 64) return fail(NERF_AMD_EINVAL, "the stratified Philox stream has 64 slots per ray: pass u for C > 64");
+    if (N && (!s_c || !z_c || (pts && !rays))) return fail(NERF_AMD_EINVAL, "NULL argument");
+    return hip_status(sk_warped_stratified(rays, u, N, C, rng_seed, rng_ray_offset, near, far, gn, gf, s_c, z_c, pts, S(stream)), "nerf_amd_warped_stratified");
+}
+
+int nerf_amd_warped_resample(const float* density, const float* s_c, const float* dirs, int dirs_stride, const float* u_inv, int64_t N, int C, int K,
+                             int softplus_density, float blur_alpha, int spacing, float near, float far, uint64_t rng_seed, int64_t rng_ray_offset,
+                             float* z_fine, float* s_fine, int64_t* below, float* w_prop, void* stream) {
+    float gn, gf;
+    if (int e = check_spacing(spacing, near, far, &gn, &gf)) return e;
+    if (N < 0) return fail(NERF_AMD_EINVAL, "negative ray count");
+    if (int e = check_warped_resample_shape(C, K)) return e;
+    if (dirs_stride < 3) return fail(NERF_AMD_EINVAL, "dirs_stride < 3");
+    if (N && (!density || !s_c || !dirs || !z_fine)) return fail(NERF_AMD_EINVAL, "NULL argument");
+    return hip_status(sk_warped_resample(density, s_c, dirs, dirs_stride, u_inv, N, C, K, softplus_density, blur_alpha, near, far, gn, gf, rng_seed,
+                                         rng_ray_offset, z_fine, s_fine, below, w_prop, S(stream)), "nerf_amd_warped_resample");
+}
+
+// workspace: density (N,64) | s_c (N,64) | z_c (N,64) | z_fine (N, n_fine+1) | rgbo (N, n_fine, 4) | raw depth (N) | rays (N, 6)
+static size_t ws256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
+size_t nerf_amd_render_warped_workspace_bytes(int64_t N, int n_fine) {
+    if (N < 0 || n_fine < 1) return 0;
+    return 3 * ws256((size_t)N * 64 * 4) + ws256((size_t)N * (n_fine + 1) * 4) + ws256((size_t)N * n_fine * 16) + ws256((size_t)N * 4) + ws256((size_t)N * 24) + 512;
+}
+
+int nerf_amd_render_rays_warped(const void* packed_prop, const void* packed_mip, int precision, const float* rays, const nerf_amd_samples* camera,
+                                int64_t ray_offset, const float* u_strat, const float* u_inv, int64_t N, int n_fine, int spacing, float near, float far,
+                                int white_bkg, float* rgb, float* depth, float* weights, void* workspace, void* stream) {
+    const int lflags = precision & ~0xff;
+    precision &= 0xff;
+    float gn, gf;
+    if (int e = check_spacing(spacing, near, far, &gn, &gf)) return e;
+    if (bad_prec(precision) || (lflags & ~(NERF_AMD_PROP_W128 | NERF_AMD_FINE_W128))) return fail(NERF_AMD_EINVAL, "unknown precision");
+    if ((lflags & NERF_AMD_FINE_W128) && camera && camera->ipe) return fail(NERF_AMD_EINVAL, "the 128-wide fine layout has no integrated-PE kernel: pack the network 256-wide");
+    if (N < 0 || n_fine < 1 || n_fine > 1023) return fail(NERF_AMD_EINVAL, "bad N or n_fine");
+    constexpr int C = 64;                                   // procedures.py:22 RENDER_COARSE_PNUM
+    if (int e = check_warped_resample_shape(C, n_fine + 1)) return e;
+    if (N == 0) return NERF_AMD_OK;
+    if (!packed_prop || !packed_mip || !rgb || !workspace) return fail(NERF_AMD_EINVAL, "NULL argument");
+    if ((u_strat == nullptr) != (u_inv == nullptr)) return fail(NERF_AMD_EINVAL, "u_strat and u_inv are both given or both NULL (in-kernel uniforms)");
+    if (!u_strat && !camera) return fail(NERF_AMD_EINVAL, "in-kernel uniforms need the descriptor (rng_seed, rng_ray_offset)");
+    if (!rays && !camera) return fail(NERF_AMD_EINVAL, "need rays or camera");
+    const bool ipe = camera && camera->ipe;
+    if (ipe && !(camera->ipe_radius > 0.0f)) return fail(NERF_AMD_EINVAL, "integrated PE needs a positive ipe_radius");
+    if (ipe && !rays) return fail(NERF_AMD_EINVAL, "integrated PE needs an explicit ray table");
+    if (!rays && (camera->H <= 0 || camera->W <= 0 || ray_offset < 0 || ray_offset + N > (int64_t)camera->H * camera->W))
+        return fail(NERF_AMD_EINVAL, "ray range outside the camera image");
+    const uint64_t seed = camera ? camera->rng_seed : 0;
+    const int64_t ray0 = camera ? camera->rng_ray_offset : 0;
+    char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    auto take = [&](size_t bytes) { float* p = reinterpret_cast<float*>(ws); ws += ws256(bytes); return p; };
+    float* density = take((size_t)N * C * 4);
+    float* s_c = take((size_t)N * C * 4);
+    float* z_c = take((size_t)N * C * 4);
+    float* z_fine = take((size_t)N * (n_fine + 1) * 4);
+    float* rgbo = take((size_t)N * n_fine * 16);
+    float* depth_raw = take((size_t)N * 4);
+    float* gen = take((size_t)N * 24);
+    float* dir_norm = reinterpret_cast<float*>(ws);
+    hipStream_t st = S(stream);
+    if (!rays) {
+        if (int e = sk_generate_rays(camera->pose, camera->H, camera->W, camera->fx, camera->fy, ray_offset, N, gen, st))
+            return hip_status(e, "ray generation");
+        rays = gen;
+    }
+    if (ipe) {                                              // as in nerf_amd_render_rays (the density buffer is scratch until the proposal pass)
+        if (camera->ipe_dir_norm) dir_norm = const_cast<float*>(camera->ipe_dir_norm);
+        else if (int e = (N >= 8) ? sk_dirs_norm_scratch(rays, N, dir_norm, density, st) : sk_dirs_norm(rays, N, dir_norm, st))
+            return hip_status(e, "direction norm");
+    }
+    // the coarse draw in s and its metric depths (no position tensor: the proposal MLP forms o + z d itself)
+    if (int e = sk_warped_stratified(rays, u_strat, N, C, seed, ray0, near, far, gn, gf, s_c, z_c, nullptr, st)) return hip_status(e, "warped stratified draw");
+    nerf_amd_samples sc{};
+    sc.mode = 1; sc.rays = rays; sc.S = C; sc.M = N * C; sc.z = z_c; sc.z_stride = C;
+    sc.contract = camera ? camera->contract : 0;
+    if (int e = launch_proposal_any(lflags, packed_prop, precision, sc, density, st)) return hip_status(e, "proposal MLP");
+    if (int e = sk_warped_resample(density, s_c, rays + 3, 6, u_inv, N, C, n_fine + 1, 0, 0.01f, near, far, gn, gf, seed, ray0, z_fine, nullptr, nullptr,
+                                   nullptr, st)) return hip_status(e, "warped resample");
+    nerf_amd_samples sf{};
+    sf.mode = 1; sf.rays = rays; sf.S = n_fine; sf.M = N * n_fine; sf.z = z_fine; sf.z_stride = n_fine + 1;
+    sf.contract = sc.contract;
+    if (ipe) { sf.ipe = 1; sf.ipe_radius = camera->ipe_radius; sf.ipe_dir_norm = dir_norm; }
+    if (int e = launch_mip_any(lflags, packed_mip, precision, sf, rgbo, st)) return hip_status(e, "fine MLP");
+    const int flags = 1 | (white_bkg ? 2 : 0);
+    // near = 0, far = 1: the composite kernel's depth is then the raw expected metric depth sum w z |d|
+    if (int e = sk_composite(rgbo, z_fine, n_fine + 1, rays + 3, 6, N, n_fine, flags, NERF_AMD_ACT_RELU, 0.0f, 0.0f, 1.0f, nullptr, nullptr, rgb, weights,
+                             depth ? depth_raw : nullptr, nullptr, st)) return hip_status(e, "composite");
+    if (depth) {
+        if (int e = sk_warp_depths(depth_raw, nullptr, N, 1, 1, near, far, gn, gf, depth, nullptr, st)) return hip_status(e, "depth un-warp");
+    }
     return NERF_AMD_OK;
 }
 

@@ -688,6 +688,119 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RS_BLOCKS_P
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Disparity ray spacing (Mip-NeRF 360, Barron et al. 2022, section 3 / eq. 11-13 with g(x) = 1/x; not in the reference -- the build's
+// own definition).  Samples are drawn and resampled in the normalised distance s in [0, 1], uniform in disparity:
+//   W(s)    = 1 / ((1 - sb) gn + sb gf),  sb = clamp(s, 0, 1)       gn = fp32(1/near), gf = fp32(1/far) (rounded once on the host)
+//   W^-1(z) = (1/zb - gn) / (gf - gn),    zb = clamp(z, near, far)
+// every operation a separate fp32 rounding in exactly this order (-ffp-contract=off), IEEE division.  None of the linear-spacing
+// kernels above reads any of this.
+// ------------------------------------------------------------------------------------------------
+struct WarpConsts { float near, far, gn, gf; };
+DEVINL float warp_s_to_z(float s, const WarpConsts& c) {
+    const float sb = fminf(fmaxf(s, 0.0f), 1.0f);
+    return 1.0f / ((1.0f - sb) * c.gn + sb * c.gf);
+}
+DEVINL float warp_z_to_s(float z, const WarpConsts& c) {
+    const float zb = fminf(fmaxf(z, c.near), c.far);
+    return (1.0f / zb - c.gn) / (c.gf - c.gn);
+}
+
+// elementwise s -> z = W(s) (inverse: z -> s) over (N,S), optionally pts (N,S,3) = o + z d with the arithmetic of stratified_points_kernel
+__global__ void warp_depths_kernel(const float* __restrict__ in, const float* __restrict__ rays, int64_t N, int S, int inverse, WarpConsts c,
+                                   float* __restrict__ out, float* __restrict__ pts) {
+    const int64_t total = N * S;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const float zv = inverse ? warp_z_to_s(in[i], c) : warp_s_to_z(in[i], c);
+        out[i] = zv;
+        if (pts) {
+            const float* r = rays + (i / S) * 6;
+            pts[i * 3] = r[0] + r[3] * zv; pts[i * 3 + 1] = r[1] + r[4] * zv; pts[i * 3 + 2] = r[2] + r[5] * zv;
+        }
+    }
+}
+
+// the coarse draw in s: s_j = (float)j r + u r with r = fp32(1/C) -- sampler_samples' expression at near = 0, res = 1/C -- then
+// z = W(s) and pts = o + z d.  u: explicit (N,C), or word 0 of the 'RS' Philox block of global ray n + ray_offset (philox_u_strat).
+__global__ void warped_stratified_kernel(const float* __restrict__ rays, const float* __restrict__ u, int64_t N, int C, float res, uint64_t seed,
+                                         int64_t ray_offset, WarpConsts c, float* __restrict__ s_out, float* __restrict__ z_out,
+                                         float* __restrict__ pts) {
+    const int64_t total = N * C;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t n = i / C;
+        const int j = (int)(i - n * C);
+        const float uu = u ? u[i] : philox_u_strat(seed, n + ray_offset, j);
+        const float sv = (float)j * res + uu * res;
+        const float zv = warp_s_to_z(sv, c);
+        s_out[i] = sv;
+        z_out[i] = zv;
+        if (pts) {
+            const float* r = rays + n * 6;
+            pts[i * 3] = r[0] + r[3] * zv; pts[i * 3 + 1] = r[1] + r[4] * zv; pts[i * 3 + 2] = r[2] + r[5] * zv;
+        }
+    }
+}
+
+// The fused per-ray step between the two MLP kernels under disparity spacing: weights from the METRIC depths W(s_c) |d|, max-blur,
+// inverse sampling over the mid-points of s_c (wave_inverse_sample fed other bin coordinates: its arithmetic is shared with
+// resample_kernel and inverse_sample_kernel), then z_fine = W(s_fine).  One wavefront per ray; a kernel of its own so that
+// resample_kernel's code, register budget and occupancy stay exactly as they are.
+struct WarpedResampleArgs {
+    const float* density; const float* s_c; const float* dirs; int dirs_stride; const float* u_inv; int64_t N; int C; int K; int softplus;
+    float alpha; WarpConsts c; float* z_fine; float* s_fine; int64_t* below; float* w_prop; uint64_t rng_seed; int64_t rng_ray_offset;
+};
+// LDS floats per wave: the rows of inverse_sample_kernel | zl[C] wraw[C] | sf[K] uu[K]
+DEVINL size_t warped_lds_floats(int C, int K) { return inv_lds_floats(C, K) + (size_t)2 * C + (size_t)2 * K; }
+
+__global__ __launch_bounds__(256) void warped_resample_kernel(WarpedResampleArgs a) {
+    const int C = a.C, K = a.K;
+    float* base = reinterpret_cast<float*>(smem) + wave_in_block() * warped_lds_floats(C, K);
+    float* pw = base; float* bins = pw + C; float* cdf = bins + C; float* samp = cdf + C;
+    int* bel = reinterpret_cast<int*>(samp + K);
+    int* sortbuf = bel + K;
+    float* zl = reinterpret_cast<float*>(sortbuf + SORT_LDS_FLOATS);
+    float* wraw = zl + C;
+    float* sf = wraw + C;
+    float* uu = sf + K;
+    const int lane = lane_id();
+    const WarpConsts c = a.c;
+    for (int64_t n = blockIdx.x * (int64_t)WAVES_PER_BLOCK + wave_in_block(); n < a.N; n += (int64_t)gridDim.x * WAVES_PER_BLOCK) {
+        lds_wave_sync();
+        const float* dd = a.dirs + n * a.dirs_stride;
+        const float nrm = norm3(dd[0], dd[1], dd[2]);
+        const float* sc = a.s_c + n * C;
+        for (int j = lane; j < C; j += 64) zl[j] = warp_s_to_z(sc[j], c);
+        const int64_t nn = n + a.rng_ray_offset;
+        for (int k = lane; k < K; k += 64) uu[k] = a.u_inv ? a.u_inv[n * K + k] : philox_u_inv(a.rng_seed, nn, k);   // words 1..3 of the 'RS' blocks
+        lds_wave_sync();
+        const float* sg = a.density + n * C;
+        const int soft = a.softplus;
+        wave_sigma_to_weights(C, NERF_AMD_ACT_RELU,
+                              [=](int s) { const float d = sg[s]; return soft ? softplus_f(d) : d; },
+                              [=](int s) { return zl[s] * nrm; },
+                              [=](int s, float wv, float) { wraw[s] = wv; });
+        lds_wave_sync();
+        for (int j = lane; j < C; j += 64) {                                   // max-blur (mip_methods.py:61-66)
+            const float cw = wraw[j];
+            const float front = (j == 0) ? cw : fmaxf(wraw[j - 1], cw);
+            const float rear = (j == C - 1) ? cw : fmaxf(cw, wraw[j + 1]);
+            const float wb = 0.5f * (front + rear) + a.alpha;
+            if (j >= 1 && j <= C - 2) pw[j - 1] = wb;                          // pdf over weights[1:-1]
+            if (a.w_prop) a.w_prop[n * C + j] = wb;
+        }
+        for (int j = lane; j < C - 1; j += 64) bins[j] = 0.5f * (sc[j + 1] + sc[j]);   // mid-points of s_c
+        lds_wave_sync();
+        wave_inverse_sample(pw, bins, C - 2, cdf, samp, bel, sortbuf, [=](int, int k) { return uu[k]; }, K, 1, sf,
+                            a.below ? a.below + n * K : nullptr, nullptr);
+        lds_wave_sync();
+        for (int k = lane; k < K; k += 64) {
+            const float sv = sf[k];
+            if (a.s_fine) a.s_fine[n * K + k] = sv;
+            a.z_fine[n * K + k] = warp_s_to_z(sv, c);
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------- row 10
 struct CompositeArgs {
     const float* rgbo; const float* z; int z_stride; const float* dirs; int dirs_stride; int64_t N; int S;
@@ -1778,6 +1891,30 @@ int sk_resample(const float* density, const float* z, const float* z_base, const
     const int64_t resident = (int64_t)nerf_host::cu_count() * RS_BLOCKS_PER_CU;
     if (blocks > resident) blocks = resident;
     hipLaunchKernelGGL(resample_kernel, dim3((unsigned)blocks), dim3(256), lds, st, a);
+    return (int)hipGetLastError();
+}
+// ---- disparity ray spacing (near, far, gn = fp32(1/near), gf = fp32(1/far): validated and rounded by the caller) ----
+int sk_warp_depths(const float* in, const float* rays, int64_t N, int S, int inverse, float near, float far, float gn, float gf, float* out, float* pts,
+                   hipStream_t st) {
+    if (N * S == 0) return 0;
+    hipLaunchKernelGGL(warp_depths_kernel, dim3(blocks_for(N * S, 256)), dim3(256), 0, st, in, rays, N, S, inverse, WarpConsts{near, far, gn, gf}, out, pts);
+    return (int)hipGetLastError();
+}
+int sk_warped_stratified(const float* rays, const float* u, int64_t N, int C, uint64_t seed, int64_t ray_offset, float near, float far, float gn, float gf,
+                         float* s_out, float* z_out, float* pts, hipStream_t st) {
+    if (N * C == 0) return 0;
+    hipLaunchKernelGGL(warped_stratified_kernel, dim3(blocks_for(N * C, 256)), dim3(256), 0, st, rays, u, N, C, 1.0f / (float)C, seed, ray_offset,
+                       WarpConsts{near, far, gn, gf}, s_out, z_out, pts);
+    return (int)hipGetLastError();
+}
+size_t sk_warped_resample_lds_bytes(int C, int K) { return WAVES_PER_BLOCK * ((size_t)5 * C + 4 * K + SORT_LDS_FLOATS) * 4; }
+int sk_warped_resample(const float* density, const float* s_c, const float* dirs, int dirs_stride, const float* u_inv, int64_t N, int C, int K, int softplus,
+                       float alpha, float near, float far, float gn, float gf, uint64_t rng_seed, int64_t rng_ray_offset, float* z_fine, float* s_fine,
+                       int64_t* below, float* w_prop, hipStream_t st) {
+    if (N == 0) return 0;
+    WarpedResampleArgs a{density, s_c, dirs, dirs_stride, u_inv, N, C, K, softplus, alpha, WarpConsts{near, far, gn, gf}, z_fine, s_fine, below, w_prop,
+                         rng_seed, rng_ray_offset};
+    hipLaunchKernelGGL(warped_resample_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), sk_warped_resample_lds_bytes(C, K), st, a);
     return (int)hipGetLastError();
 }
 int sk_composite(const float* rgbo, const float* z, int z_stride, const float* dirs, int dirs_stride, int64_t N, int S, int flags,

@@ -770,6 +770,107 @@ def render_rays(packed_prop, packed_mip, precision, rays, z_base, u_strat, u_inv
     return rgb, depth, w, workspace
 
 
+# ------------------------------------------------------------------------------------------------ disparity ray spacing (Mip-NeRF 360 s-space)
+def _spacing_kind(spacing) -> int:
+    """'disparity' -> SPACING_DISPARITY.  The warped entry points take no other kind ('linear' is every other op of this module)."""
+    from ._lib import SPACINGS
+    if spacing not in SPACINGS:
+        raise ValueError("nerf_amd: spacing must be 'linear' or 'disparity' (got %r)" % (spacing,))
+    return SPACINGS[spacing]
+
+
+def warp_depths(s: torch.Tensor, near: float, far: float, rays: Optional[torch.Tensor] = None, *, inverse: bool = False, spacing: str = "disparity"):
+    """s (N,S) -> z = W(s) = 1 / ((1 - s) / near + s / far) (include/nerf_amd.h, disparity spacing), or with ``inverse`` z -> s.
+    With ``rays`` (N,6) also pts (N,S,3) = o + z d.  -> (out (N,S), pts | None)"""
+    s = _dev(s, "depths")
+    if s.dim() != 2:
+        raise ValueError("nerf_amd: warp_depths takes (N,S) depths")
+    N, S = s.shape
+    out = torch.empty_like(s)
+    pts = None
+    if rays is not None:
+        rays = _dev(rays, "rays")
+        pts = torch.empty((N, S, 3), dtype=torch.float32, device=s.device)
+    check(lib.nerf_amd_warp_depths(_ptr(s), _ptr(rays), N, S, int(bool(inverse)), _spacing_kind(spacing), float(near), float(far), _ptr(out), _ptr(pts),
+                                   _stream()), "nerf_amd_warp_depths")
+    return out, pts
+
+
+def warped_stratified(rays: torch.Tensor, u: Optional[torch.Tensor], near: float, far: float, *, n_points: Optional[int] = None, seed: int = 0,
+                      ray_offset: int = 0, want_pts: bool = True, spacing: str = "disparity"):
+    """The coarse draw in s: s_j = j / C + u / C -> (s_c (N,C), z_c (N,C) = W(s_c), pts (N,C,3) | None).  ``u`` (N,C), or None with
+    ``n_points`` = C: the render kernels' stratified Philox stream for (seed, ray + ray_offset), like ops.philox_stream(strat=True)."""
+    rays = _dev(rays, "rays")
+    N = rays.shape[0]
+    if u is not None:
+        u = _dev(u, "u")
+        Cn = u.shape[-1]
+    else:
+        Cn = int(n_points)
+    s_c = torch.empty((N, Cn), dtype=torch.float32, device=rays.device)
+    z_c = torch.empty((N, Cn), dtype=torch.float32, device=rays.device)
+    pts = torch.empty((N, Cn, 3), dtype=torch.float32, device=rays.device) if want_pts else None
+    check(lib.nerf_amd_warped_stratified(_ptr(rays), _ptr(u), N, Cn, int(seed) & 0xFFFFFFFFFFFFFFFF, int(ray_offset), _spacing_kind(spacing), float(near),
+                                         float(far), _ptr(s_c), _ptr(z_c), _ptr(pts), _stream()), "nerf_amd_warped_stratified")
+    return s_c, z_c, pts
+
+
+def warped_resample(density: torch.Tensor, s_c: torch.Tensor, rays: torch.Tensor, u_inv: Optional[torch.Tensor], near: float, far: float, *,
+                    K: Optional[int] = None, softplus: bool = False, alpha: float = 0.01, want_s: bool = True, want_below: bool = True,
+                    want_w: bool = True, seed: int = 0, ray_offset: int = 0, spacing: str = "disparity"):
+    """ops.resample under disparity spacing: density (N,C), s_c (N,C), rays (N,6) -> (z_fine (N,K), s_fine | None, below | None,
+    w_prop | None).  ``u_inv`` (N,K), or None with ``K``: the inverse-CDF Philox stream of (seed, ray + ray_offset)."""
+    density, s_c, rays = _dev(density, "density"), _dev(s_c, "s_c"), _dev(rays, "rays")
+    N, Cn = density.shape
+    if u_inv is not None:
+        u_inv = _dev(u_inv, "u_inv")
+        K = u_inv.shape[-1]
+    K = int(K)
+    dev = density.device
+    z_fine = torch.empty((N, K), dtype=torch.float32, device=dev)
+    s_fine = torch.empty((N, K), dtype=torch.float32, device=dev) if want_s else None
+    below = torch.empty((N, K), dtype=torch.int64, device=dev) if want_below else None
+    w = torch.empty((N, Cn), dtype=torch.float32, device=dev) if want_w else None
+    dirs_ptr = C.c_void_p(rays.data_ptr() + 12) if N else None
+    check(lib.nerf_amd_warped_resample(_ptr(density), _ptr(s_c), dirs_ptr, 6, _ptr(u_inv), N, Cn, K, int(softplus), float(alpha), _spacing_kind(spacing),
+                                       float(near), float(far), int(seed) & 0xFFFFFFFFFFFFFFFF, int(ray_offset), _ptr(z_fine), _ptr(s_fine), _ptr(below),
+                                       _ptr(w), _stream()), "nerf_amd_warped_resample")
+    return z_fine, s_fine, below, w
+
+
+def render_rays_warped(packed_prop, packed_mip, precision, rays, u_strat, u_inv, n_fine, near, far, white_bkg, *, want_depth=True, want_weights=False,
+                       workspace: Optional[torch.Tensor] = None, contract: bool = False, ipe_radius: Optional[float] = None, seed: Optional[int] = None,
+                       rng_ray_offset: int = 0, ipe_dir_norm: Optional[torch.Tensor] = None, spacing: str = "disparity"):
+    """ops.render_rays under disparity spacing (nerf_amd_render_rays_warped): explicit rays (N,6); ``depth`` is W^-1 of the expected
+    metric depth, in [0, 1].  u_strat = u_inv = None with ``seed``: in-kernel Philox uniforms, as in render_rays.  n_fine <= 623 (the
+    resampling kernel's LDS rows, include/nerf_amd.h)."""
+    in_kernel_rng = u_strat is None
+    if in_kernel_rng and (u_inv is not None or seed is None):
+        raise ValueError("nerf_amd: u_strat and u_inv are both tensors, or both None with a `seed`")
+    rays = _dev(rays, "rays")
+    dev = rays.device
+    N = rays.shape[0]
+    camera = Samples()                                       # carries only the flags next to explicit rays
+    camera.contract = int(bool(contract))
+    if ipe_radius is not None:
+        camera.ipe, camera.ipe_radius = 1, float(ipe_radius)
+        camera.ipe_dir_norm = _dev(ipe_dir_norm, "ipe_dir_norm").data_ptr() if ipe_dir_norm is not None else None
+    if in_kernel_rng:
+        camera.rng_seed, camera.rng_ray_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(rng_ray_offset)
+    else:
+        u_strat, u_inv = _dev(u_strat, "u_strat"), _dev(u_inv, "u_inv")
+    need = lib.nerf_amd_render_warped_workspace_bytes(N, n_fine)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    rgb = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    depth = torch.empty((N,), dtype=torch.float32, device=dev) if want_depth else None
+    w = torch.empty((N, n_fine), dtype=torch.float32, device=dev) if want_weights else None
+    check(lib.nerf_amd_render_rays_warped(_ptr(packed_prop), _ptr(packed_mip), _prop_prec(packed_prop, precision, packed_mip), _ptr(rays),
+                                          C.byref(camera), 0, _ptr(u_strat), _ptr(u_inv), N, int(n_fine), _spacing_kind(spacing), float(near), float(far),
+                                          int(white_bkg), _ptr(rgb), _ptr(depth), _ptr(w), _ptr(workspace), _stream()), "nerf_amd_render_rays_warped")
+    return rgb, depth, w, workspace
+
+
 def render_rays_ref(packed_prop, packed_ref, precision, rays, z_base, u_strat, u_inv, n_fine, near, far, white_bkg,
                     want_depth=True, cam_dir: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
                     camera: Optional[Samples] = None, ray_offset: int = 0, n_rays: Optional[int] = None, flags: int = 0,

@@ -49,12 +49,15 @@ GENERIC_CHUNK_RAYS = 4096
 
 def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, render_depth, chunk: Optional[int] = None,
                           is_ref_model: bool = False, cam_dir=None, seed: Optional[int] = None, ray_offset: int = 0, contract: bool = False,
-                          ipe_radius: Optional[float] = None, ipe_dir_norm=None):
+                          ipe_radius: Optional[float] = None, ipe_dir_norm=None, *, spacing: str = "linear"):
     """The tile body of procedures.py:62-85 as the reference writes it -- stratified depths, ProposalNetwork.forward, get_weights,
     maxBlurFilter, inverseSample, NeRF.length2pts, network.forward, NeRF.render -- on chunks of rays: the route of networks the fused
     render entry (nerf_amd_render_rays) has no packed layout for.  Every call is a HIP kernel of this package; uniforms that were not
     given are the render kernels' own Philox streams for `seed` and the chunk's global ray indices (ops.philox_stream): the image of a
-    seeded render does not depend on whether a network runs fused or layer by layer."""
+    seeded render does not depend on whether a network runs fused or layer by layer.
+    ``spacing="disparity"`` (Mip-NeRF 360's s-space, include/nerf_amd.h): the coarse draw and the resampling happen in the normalised
+    distance s, everything else -- weights, coarseFineMerge (W is monotone: the order is that of s), encodings, compositing -- on the metric
+    depths W(s); the depth is W^-1 of the expected metric depth."""
     from .mip_methods import maxBlurFilter
     from .utils import inverseSample
     N = rays.shape[0]
@@ -63,15 +66,23 @@ def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sampl
     depth = torch.empty((N,), dtype=torch.float32, device=rays.device) if render_depth else None
     normal_px = torch.empty((N,), dtype=torch.float32, device=rays.device) if cam_dir is not None else None
     resolution = (far - near) / sample_num                                           # procedures.py:57
+    warped = _check_spacing(spacing, near, far)
     for s in range(0, N, chunk):
         r = rays[s: s + chunk].contiguous()
         n = r.shape[0]
         u1 = u_strat[s: s + n] if u_strat is not None else ops.philox_stream((n, RENDER_COARSE_PNUM), seed, ray_offset + s, strat=True, device=rays.device)
         u2 = u_inv[s: s + n] if u_inv is not None else ops.philox_stream((n, sample_num + 1), seed, ray_offset + s, device=rays.device)
-        z, pts = ops.stratified_points(r, z_base, u1.contiguous(), resolution)      # :65-66
+        if warped:
+            s_c, z, pts = ops.warped_stratified(r, u1.contiguous(), near, far, spacing=spacing)
+        else:
+            z, pts = ops.stratified_points(r, z_base, u1.contiguous(), resolution)  # :65-66
         density = prop_net.forward(pts, contract=True) if contract else prop_net.forward(pts)
         prop_w = maxBlurFilter(ProposalNetwork.get_weights(density, z, r[:, 3:]), 0.01)
-        fine, _ = inverseSample(prop_w, z, sample_num + 1, sort=True, u=u2.contiguous())
+        if warped:                                                                   # resample in s, then back to metric depths
+            s_f, _ = inverseSample(prop_w, s_c, sample_num + 1, sort=True, u=u2.contiguous())
+            fine = ops.warp_depths(s_f, near, far, spacing=spacing)[0]
+        else:
+            fine, _ = inverseSample(prop_w, z, sample_num + 1, sort=True, u=u2.contiguous())
         normal = None
         if is_ref_model:                                                             # :71-74
             samples, fine = NeRF.coarseFineMerge(r, z, fine)
@@ -84,20 +95,32 @@ def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sampl
             fine = fine[..., :-1].contiguous()
             rgbo = network.forward(NeRF.length2pts(r, fine), contract=True) if contract else network.forward(NeRF.length2pts(r, fine))
         part, _, extras = NeRF.render(rgbo, fine, r[:, 3:], white_bkg=white_bkg, density_act=torch.nn.functional.relu,
-                                      render_depth=(near, far) if render_depth else None,
+                                      render_depth=((0.0, 1.0) if warped else (near, far)) if render_depth else None,
                                       normal_info=(normal, cam_dir) if cam_dir is not None else None)
         rgb[s: s + n] = part
         if render_depth:
-            depth[s: s + n] = extras["depth_img"].reshape(-1)
+            d = extras["depth_img"].reshape(n, 1)
+            depth[s: s + n] = (ops.warp_depths(d, near, far, inverse=True, spacing=spacing)[0] if warped else d).reshape(-1)
         if cam_dir is not None:
             normal_px[s: s + n] = extras["normal_img"].reshape(-1)
     return rgb, depth, normal_px
 
 
+def _check_spacing(spacing, near, far) -> bool:
+    """True for "disparity", False for "linear" (which must not reach any of the warped code); anything else raises."""
+    if spacing == "linear":
+        return False
+    if spacing != "disparity":
+        raise ValueError("nerf_amd: spacing must be 'linear' or 'disparity' (got %r)" % (spacing,))
+    if not 0.0 < float(near) < float(far):
+        raise ValueError("nerf_amd: spacing='disparity' needs 0 < near < far")
+    return True
+
+
 def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Tensor, image_size, focal,
                  near: float, far: float, sample_num: int = 128, white_bkg: bool = False, render_depth=False,
                  render_normal=False, rng: str = "philox", contract: bool = False, ipe=False, seed: Optional[int] = None,
-                 _shard=None) -> dict:
+                 _shard=None, *, spacing: str = "linear") -> dict:
     """Whole-image inference (procedures.py:34-97) -> {"rgb" (3,H,W) [, "depth_img" (3,H,W)]} on
     ``render_pose.device``.  The caller provides ``no_grad``/``eval()`` like for the reference.
     ``rng``, ``contract`` and ``ipe`` are additions.  ``rng``: where the stratified / inverse-CDF uniforms come from --
@@ -116,7 +139,14 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
     config 3): the fine network reads the integrated positional encoding of the conical frustum between consecutive fine depths
     (mip_methods.py:15-58: [mu | ipe_feature]) instead of the point encoding; True = the pixel radius 2/sqrt(12) pixel widths of
     Mip-NeRF, a float = that radius.  The reference holds `ipe_feature` but never calls it: its use inside the loop is this build's
-    definition (oracle.render_rays(ipe_radius=...)), parity of the function itself is pinned by golden G12."""
+    definition (oracle.render_rays(ipe_radius=...)), parity of the function itself is pinned by golden G12.
+    ``spacing`` (keyword-only; an addition for unbounded scenes, BASELINE config 5): "linear" (default) = the reference's depths, spaced
+    evenly between near and far; "disparity" = Mip-NeRF 360's normalised distance s (include/nerf_amd.h): the 64 coarse samples and the
+    inverse-CDF resampling are uniform in 1/z, so near = 0.2, far = 1e6 spends its samples near the camera and still reaches the
+    background; ``depth_img`` is then W^-1 of the expected depth, in [0, 1].  The compiled-shape MipNeRF goes through
+    nerf_amd_render_rays_warped; Ref-NeRF and layer-by-layer networks through the call-by-call route, on the same Philox streams.
+    The disparity resampling kernel keeps four rays' rows in 64 KiB of LDS: ``sample_num`` <= 623 under "disparity" (a larger count
+    raises; "linear" takes up to 1023)."""
     if not isinstance(image_size, Iterable):
         image_size = (image_size, image_size)
     is_ref_model = type(network).__name__ == "RefNeRF"
@@ -161,14 +191,24 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
             raise NotImplementedError("nerf_amd: the integrated PE is wired for the MipNeRF render path only")
         ipe_radius = (2.0 / (12.0 ** 0.5) / fx) if ipe is True else float(ipe)
     generic = network._generic() or prop_net._generic()
-    if generic:
+    warped = _check_spacing(spacing, near, far)
+    if warped and is_ref_model and not generic:
+        # the fused Ref-NeRF entry point has no disparity twin: the call-by-call tile body on the packed kernels, same Philox streams
+        rgb, depth, normal_px = _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, bool(render_depth),
+                                                      is_ref_model=True, cam_dir=render_pose[:, -2].contiguous() if render_normal else None, seed=seed,
+                                                      ray_offset=off, contract=contract, spacing=spacing)
+    elif warped and not generic:
+        rgb, depth, _, _ = ops.render_rays_warped(prop_net.packed(prec), network.packed(prec, wide=bool(ipe)), prec, rays, u_strat, u_inv, sample_num, near,
+                                                  far, white_bkg, want_depth=bool(render_depth), contract=contract, ipe_radius=ipe_radius, seed=seed,
+                                                  rng_ray_offset=off, ipe_dir_norm=ipe_dir_norm, spacing=spacing)
+    elif generic:
         # a network LARGER than the fused kernels' compiled shapes (hidden width > 256, > 10 octaves): the reference's tile body
         # (procedures.py:62-85) call by call on the mirrored ops -- the networks run layer by layer (nerf_amd/generic_path.py)
         rgb, depth, normal_px = _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, bool(render_depth),
                                                       is_ref_model=is_ref_model,
                                                       cam_dir=render_pose[:, -2].contiguous() if (render_normal and is_ref_model) else None, seed=seed,
                                                       ray_offset=off, contract=contract, ipe_radius=ipe_radius,
-                                                      ipe_dir_norm=ipe_dir_norm)
+                                                      ipe_dir_norm=ipe_dir_norm, spacing=spacing)
     elif not is_ref_model:
         # (a narrow fine network has no integrated-PE kernel: with ipe its 256-wide -- zero-padded -- blob is used)
         rgb, depth, _, _ = ops.render_rays(prop_net.packed(prec), network.packed(prec, wide=bool(ipe)), prec, rays, z_base, u_strat, u_inv,

@@ -66,7 +66,7 @@ class TrainStep:
     def __init__(self, prop_net, mip_net, optimizer: Adam, image_hw: Tuple[int, int], focal, near: float, far: float, ray_num: int = 512,
                  coarse_pnum: int = 64, fine_pnum: int = 128, crop_xy=(1.0, 1.0), seed: Optional[int] = None, white_bkg: bool = False,
                  prop_normal: bool = False, grad_hook=None, ipe_radius: Optional[float] = None, contract: bool = False, flat_grads=None,
-                 *, scene=None, view_ids=None, grad_clip: float = -0.01, distortion: float = 0.0):
+                 *, scene=None, view_ids=None, spacing: str = "linear", grad_clip: float = -0.01, distortion: float = 0.0):
         """``grad_hook``: called between ``loss.backward()`` and ``optimizer.step()`` -- the place of ddp_train.py's gradient all-reduce
         (``lambda: parallel.allreduce_gradients([mip_net, prop_net])``).  An iteration with a hook runs eagerly (``capture`` refuses).
         ``ipe_radius`` (BASELINE configs[2]): the fine network encodes the conical frusta between consecutive fine depths with the
@@ -93,7 +93,11 @@ class TrainStep:
         place is fine.  With V = 1 the iteration is bit-identical to the image-mode one on that image.  Data-parallel runs: with a
         reducing ``flat_grads`` whose group has more than one rank, the seed becomes ``rank_seed(seed, rank)`` so that the ranks draw
         different batches (rank 0 keeps the seed).
-        ``scene``, ``view_ids``, ``grad_clip`` and ``distortion`` are keyword-only."""
+        ``spacing`` (BASELINE configs[4]; not in the reference): "linear" (default) leaves the iteration as it is; "disparity" draws the
+        coarse samples and resamples in Mip-NeRF 360's normalised distance s (include/nerf_amd.h): the samplers are called with near = 0,
+        far = 1 so that their ``lengths`` are s_c, positions and every weight use the metric depths W(s), inverseSample runs on s_c, and
+        L_dist is evaluated on the sorted s_f directly (no 1 / (far - near) rescale).  Needs 0 < near < far.
+        ``scene``, ``view_ids``, ``spacing``, ``grad_clip`` and ``distortion`` are keyword-only (their order carries no meaning)."""
         if not isinstance(optimizer, Adam) or not optimizer.lr_on_device:
             raise ValueError("nerf_amd.training.TrainStep needs nerf_amd.optim.Adam(..., lr_on_device=True): the step must not read host state")
         self.prop_net, self.mip_net, self.opt = prop_net, mip_net, optimizer
@@ -105,6 +109,8 @@ class TrainStep:
         self.ipe_radius, self.contract = (None if ipe_radius is None else float(ipe_radius)), bool(contract)
         if self.is_ref and self.ipe_radius is not None:
             raise NotImplementedError("nerf_amd.training.TrainStep: the integrated PE is wired for the MipNeRF branch (the Ref-NeRF kernel encodes points)")
+        from .procedures import _check_spacing
+        self.spacing, self.warped = spacing, _check_spacing(spacing, near, far)
         self.distortion = float(distortion)
         if not self.distortion >= 0.0:
             raise ValueError("nerf_amd.training.TrainStep: distortion must be >= 0")
@@ -147,7 +153,8 @@ class TrainStep:
         self.img_loss = torch.zeros((), dtype=torch.float32, device=dev)
         self.dist_loss = torch.zeros((), dtype=torch.float32, device=dev)
         # L_dist is 1-homogeneous in the depths: in s = (z - near) / (far - near) it is L_dist(z) / (far - near)
-        self.dist_fn = DistortionLoss(self.distortion / (self.far - self.near)) if self.distortion > 0.0 else None
+        # (disparity spacing: the depths handed to it ARE s)
+        self.dist_fn = DistortionLoss(self.distortion / (1.0 if self.warped else self.far - self.near)) if self.distortion > 0.0 else None
         if self.is_ref:                                      # the bottle-neck perturbation keyed by this step's device-resident seed
             mip_net.__dict__["noise_seed_dev"] = self.seed   # (RefNeRF.forward, noise_rng "philox": a replayed graph draws fresh noise)
         self.prop_loss_fn = ProposalLoss()
@@ -183,15 +190,19 @@ class TrainStep:
 
     # ---------------------------------------------------------------------------------------------------------------- the iteration
     def _body(self):
+        near, far = (0.0, 1.0) if self.warped else (self.near, self.far)                  # disparity spacing: the samplers' lengths are s_c
         if self.scene is not None:                                                        # one gather over the whole stack, read in place
-            pts, z_c, rgb_tgt, rays, _ = ops.sample_scene_rays(self.scene[0], self.scene[1], self.fx, self.fy, self.near, self.far, self.ray_num,
+            pts, z_c, rgb_tgt, rays, _ = ops.sample_scene_rays(self.scene[0], self.scene[1], self.fx, self.fy, near, far, self.ray_num,
                                                                self.coarse_pnum, seed_dev=self.seed, window=crop_window(*self.image_hw, self.crop_xy),
                                                                view_ids=self.view_ids, index_out=self.ray_index)
         else:
             pixels, coords = randomFromOneImage(self.image, self.crop_xy)                 # pure indexing on the device (cached table)
-            pts, z_c, rgb_tgt, rays = ops.sample_training_rays_dev(pixels, coords, self.pose, self.fx, self.fy, self.near, self.far, self.ray_num,
+            pts, z_c, rgb_tgt, rays = ops.sample_training_rays_dev(pixels, coords, self.pose, self.fx, self.fy, near, far, self.ray_num,
                                                                    self.coarse_pnum, self.seed)        # train.py:160-162
         dirs = rays[:, 3:]
+        if self.warped:
+            s_c = z_c
+            z_c, pts = ops.warp_depths(s_c, self.near, self.far, rays, spacing=self.spacing)           # metric depths and o + z d
         if self.prop_normal:
             pts.requires_grad_(True)                                                                    # train.py:165
         density = self.prop_net.forward(pts, contract=True) if self.contract else self.prop_net.forward(pts)
@@ -201,7 +212,11 @@ class TrainStep:
         density = F.softplus(density)                                                                   # :169
         prop_w = maxBlurFilter(ProposalNetwork.get_weights(density, z_c, dirs), 0.01)                   # :170-171
         u = ops.philox_uniforms((self.ray_num, self.fine_pnum + 1), seed_dev=self.seed)
-        z_f, below = inverseSample(prop_w, z_c, self.fine_pnum + 1, sort=True, u=u)                     # :174
+        if self.warped:                                                                                 # resample in s, back to metric depths
+            s_f, below = inverseSample(prop_w, s_c, self.fine_pnum + 1, sort=True, u=u)
+            z_f = ops.warp_depths(s_f, self.near, self.far, spacing=self.spacing)[0]
+        else:
+            z_f, below = inverseSample(prop_w, z_c, self.fine_pnum + 1, sort=True, u=u)                 # :174
         extra = 0.0
         if self.is_ref:                                                                                 # :175-187
             from .ref_model import BackFaceLoss, RefNeRF, WeightedNormalLoss
@@ -219,7 +234,7 @@ class TrainStep:
                 picked = RefNeRF.coarse_grad_select(density_grad, sort_ids, self.coarse_pnum)
                 extra = extra + 4e-5 * WeightedNormalLoss()(prop_w, picked.detach(), coarse_grad)       # 4e-4 * 0.1 (:198)
         else:
-            edges = z_f                                          # the fine_pnum + 1 sorted fine depths: the intervals of L_dist
+            edges = s_f if self.warped else z_f                  # the fine_pnum + 1 sorted fine depths: the intervals of L_dist
             if self.ipe_radius is not None:                      # the fine_pnum frusta between the fine_pnum + 1 sorted depths
                 rgbo = self.mip_net.forward_rays(rays, z_f, self.fine_pnum, ipe_radius=self.ipe_radius, contract=self.contract)
                 z_f = z_f[..., :-1].contiguous()

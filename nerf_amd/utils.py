@@ -43,6 +43,21 @@ def inverseSample(weights: torch.Tensor, coarse_depth: torch.Tensor, sample_pnum
     return z
 
 
+def warp_depths(s: torch.Tensor, near: float, far: float, spacing: str = "disparity"):
+    """Normalised ray distance s in [0, 1] -> metric depth (an addition: Mip-NeRF 360's s-space).  "disparity": z = 1 / ((1 - s) / near + s / far),
+    uniform in 1/z (include/nerf_amd.h states the fp32 evaluation); "linear": z = near + s (far - near), plain torch."""
+    if spacing == "linear":
+        return near + s * (far - near)
+    return ops.warp_depths(s.reshape(-1, s.shape[-1]), near, far, spacing=spacing)[0].view(s.shape)
+
+
+def unwarp_depths(z: torch.Tensor, near: float, far: float, spacing: str = "disparity"):
+    """The inverse of ``warp_depths``: metric depth (clamped to [near, far]) -> s in [0, 1]."""
+    if spacing == "linear":
+        return (z - near) / (far - near)
+    return ops.warp_depths(z.reshape(-1, z.shape[-1]), near, far, inverse=True, spacing=spacing)[0].view(z.shape)
+
+
 def sample_pdf(bins, weights, N_samples, u: torch.Tensor = None):
     """utils.py:108-133 -> (samples, below, above)."""
     if u is None:
