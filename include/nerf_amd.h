@@ -329,6 +329,30 @@ int nerf_amd_distortion_loss(const float* w, const float* t, int64_t N, int S, i
 int nerf_amd_distortion_loss_backward(const float* w, const float* t, int64_t N, int S, int mode, float scale, const float* g, float* d_w,
                                       float* d_t, void* stream);
 
+/* (added after ABI 125; additive) Mip-NeRF 360's interlevel loss L_prop (Barron et al. 2022, eq. 13), not in the reference: the fine histogram (w, t) is bounded from above
+ * by the proposal histogram (w_prop, t_prop) -- each fine weight by the proposal mass whose intervals geometrically overlap its interval.
+ * Unlike getBounds + ProposalLoss (bin indices of ONE sampler call) it needs no relation between the two sample sets, so a histogram the
+ * fine samples were not drawn from directly can be supervised as well.  All fp32 contiguous, rows ascending, 1 <= M, K <= NERF_AMD_INTERLEVEL_MAX:
+ *   w (N, M) fine weights (constants), t (N, M + 1) fine edges, w_prop (N, K), t_prop (N, Kp) with Kp = K + 1 (closed: the K + 1 edges) or
+ *   Kp = K (open: the K depths of point samples; interval j = [t_j, t_j+1), the last one open to +inf, as get_weights composites it).
+ * With e the K + 1 proposal edges (+inf appended in the open form) and c the exclusive prefix sum of w_prop (c_0 = 0, K + 1 entries):
+ *   lo(v) = max{ j : e_j <= v } (0 if none),  hi(v) = min{ j : e_j > v } (K if none),  bound_i = c[hi(t_i+1)] - c[lo(t_i)]
+ *   out[0] = scale * sum_n sum_i relu(w_i - bound_i)^2 / (w_i + 1e-8)                   (a sum over rays, eps 1e-8: as ProposalLoss)
+ * -- a proposal interval that merely touches a fine one counts as overlapping; a fine interval wholly outside the proposal's span has
+ * bound 0.  bounds_out (N, M) may be NULL (not written).  One wavefront per ray, the edge rows and the fp64 prefix sums in LDS; prefix
+ * sums, bounds, per-ray partials and the cross-ray sum are fp64 in a fixed order, only the stored values are rounded to fp32
+ * (deterministic; no host synchronisation, so capturable).  workspace: NERF_AMD_INTERLEVEL_WORKSPACE_FLOATS floats.
+ * Backward: g = d loss / d out (ONE float in device memory) -> d_w_prop (N, K):
+ *   d_w_prop[j] = g scale sum_{i : lo(t_i) <= j < hi(t_i+1)} -2 relu(w_i - bound_i) / (w_i + 1e-8)
+ * -- the i of one j are a contiguous range (t_i < e_j+1 and t_i+1 >= e_j): two binary searches and a difference of an fp64 prefix sum,
+ * no atomics.  The loss is piecewise constant in the edges and w is a constant: there is no other gradient. */
+#define NERF_AMD_INTERLEVEL_MAX 1024
+#define NERF_AMD_INTERLEVEL_WORKSPACE_FLOATS 2048
+int nerf_amd_interlevel_loss(const float* w, const float* t, const float* w_prop, const float* t_prop, int64_t N, int M, int K, int Kp, float scale,
+                             float* out, float* bounds_out, float* workspace, void* stream);
+int nerf_amd_interlevel_loss_backward(const float* w, const float* t, const float* w_prop, const float* t_prop, int64_t N, int M, int K, int Kp,
+                                      float scale, const float* g, float* d_w_prop, void* stream);
+
 /* Measurement aid, no reference counterpart (the roofline's denominator checked on the box): `workgroups` workgroups of four
  * waves (one per SIMD; 160 KiB of LDS each, so one workgroup per CU) issue iters * 64 v_mfma_f32_32x32x16_bf16 per wave and nothing else;
  * timed by the caller, 32 768 flop per MFMA and wave.  mode 0: constant operands (optimistic: the datapath does not toggle); 1: a rotating

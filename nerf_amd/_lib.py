@@ -87,6 +87,8 @@ SIGNATURES = {
     "nerf_amd_weighted_dot_loss_backward": (C.c_int, [c_void, c_void, c_void, c_void, i64, C.c_int, C.c_float, c_void, c_void, c_void, c_void]),
     "nerf_amd_distortion_loss": (C.c_int, [c_void, c_void, i64, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void]),
     "nerf_amd_distortion_loss_backward": (C.c_int, [c_void, c_void, i64, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void, c_void]),
+    "nerf_amd_interlevel_loss": (C.c_int, [c_void, c_void, c_void, c_void, i64, C.c_int, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void, c_void]),
+    "nerf_amd_interlevel_loss_backward": (C.c_int, [c_void, c_void, c_void, c_void, i64, C.c_int, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void]),
     "nerf_amd_get_bounds": (C.c_int, [c_void, c_void, i64, C.c_int, C.c_int, c_void, c_void]),
     "nerf_amd_train_dump_bytes": (C.c_size_t, [C.c_int, C.c_int, i64]),
     "nerf_amd_proposal_forward_train": (C.c_int, [c_void, C.c_int, C.POINTER(Samples), c_void, c_void, c_void]),

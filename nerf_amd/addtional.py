@@ -72,6 +72,47 @@ class DistortionLoss(nn.Module):
         return _distortion(weights, edges, 1, self.scale, expr)
 
 
+class InterlevelLoss(nn.Module):
+    """Mip-NeRF 360's interlevel loss L_prop (Barron et al. 2022, eq. 13), not in the reference: the fine weights w (N, M) over their
+    ascending edges t (N, M + 1) are bounded by the proposal mass that geometrically overlaps each fine interval,
+    scale * sum relu(w - bound)^2 / (w + 1e-8)  (the sum and eps of ProposalLoss: the two are interchangeable in magnitude).
+    ``prop_edges`` holds the K + 1 edges of the K proposal weights, or -- (N, K) -- the K depths of point samples, the last interval then
+    open to +inf as get_weights composites it.  Unlike getBounds it needs no bin indices: any histogram can be supervised, not only the
+    one the fine samples were drawn from.  ``weights`` is detached; the gradient goes to ``prop_weights`` alone (the loss is piecewise
+    constant in the edges)."""
+
+    def __init__(self, scale: float = 1.0) -> None:
+        super().__init__()
+        self.scale = float(scale)
+
+    @staticmethod
+    def bounds(edges: torch.Tensor, prop_weights: torch.Tensor, prop_edges: torch.Tensor) -> torch.Tensor:
+        """The specification: bound_i = c[hi(t_i+1)] - c[lo(t_i)] with c the exclusive prefix sum of prop_weights, lo(v) the last
+        proposal edge <= v (0 if none) and hi(v) the first one > v (K if none)."""
+        K = prop_weights.shape[-1]
+        if prop_edges.shape[-1] == K:
+            prop_edges = torch.cat((prop_edges, torch.full_like(prop_edges[..., :1], float("inf"))), -1)
+        c = torch.cat((torch.zeros_like(prop_weights[..., :1]), torch.cumsum(prop_weights, -1)), -1)
+        cnt = torch.searchsorted(prop_edges.contiguous(), edges.contiguous(), right=True)              # proposal edges <= each fine edge
+        lo = (cnt[..., :-1] - 1).clamp(min=0)
+        hi = cnt[..., 1:].clamp(max=K)
+        return torch.gather(c, -1, hi) - torch.gather(c, -1, lo)
+
+    def forward(self, weights: torch.Tensor, edges: torch.Tensor, prop_weights: torch.Tensor, prop_edges: torch.Tensor) -> torch.Tensor:
+        weights, edges, prop_edges = weights.detach(), edges.detach(), prop_edges.detach()
+        if not weights.is_cuda:
+            bound = self.bounds(edges, prop_weights, prop_edges)
+            return torch.sum(F.relu(weights - bound) ** 2 / (weights + 1e-8)) * self.scale
+        if max(weights.shape[-1], prop_weights.shape[-1]) > ops.INTERLEVEL_MAX:
+            ab.unsupported("an interlevel loss over rows of %d and %d intervals (the kernels stage a ray's rows in LDS: <= %d)"
+                           % (weights.shape[-1], prop_weights.shape[-1], ops.INTERLEVEL_MAX))
+        scale = self.scale
+        if not ab.needs_grad(prop_weights):
+            return ops.interlevel_loss(weights, edges, prop_weights, prop_edges, scale)
+        return ab.HipOp.apply(lambda p: ops.interlevel_loss(weights, edges, p, prop_edges, scale),
+                              lambda g, p: (ops.interlevel_loss_backward(g, weights, edges, p, prop_edges, scale),), 1, prop_weights)
+
+
 class SoftL1Loss(nn.Module):
     def __init__(self, epsilon=0.001) -> None:
         super().__init__()

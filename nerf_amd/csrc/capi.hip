@@ -27,6 +27,8 @@ int sk_weighted_dot_loss(const float*, const float*, const float*, int64_t, int,
 int sk_weighted_dot_loss_backward(const float*, const float*, const float*, const float*, int64_t, int, float, float*, float*, float*, hipStream_t);
 int sk_distortion_loss(const float*, const float*, int64_t, int, int, float, float*, float*, hipStream_t);
 int sk_distortion_loss_backward(const float*, const float*, int64_t, int, int, float, const float*, float*, float*, hipStream_t);
+int sk_interlevel_loss(const float*, const float*, const float*, const float*, int64_t, int, int, int, float, float*, float*, float*, hipStream_t);
+int sk_interlevel_loss_backward(const float*, const float*, const float*, const float*, int64_t, int, int, int, float, const float*, float*, hipStream_t);
 int sk_encode_rows(const float*, int, int64_t, int, int, int, void*, hipStream_t);
 int sk_frag_rows_mask_blocks();
 int sk_frag_rows_mask(const void*, int, int64_t, int, int64_t, void*, void*, float*, hipStream_t);
@@ -141,6 +143,13 @@ int check_distortion(int64_t N, int Sn, int mode) {
     if (N < 0) return fail(NERF_AMD_EINVAL, "negative ray count");
     if (mode != 0 && mode != 1) return fail(NERF_AMD_EINVAL, "unknown mode (0: Regularizer, 1: Mip-NeRF 360 L_dist)");
     if (Sn < 2 || Sn > NERF_AMD_DISTORTION_MAX_S) return fail(NERF_AMD_EINVAL, "bad size (S must be 2..1024 depths per row: a ray's rows live in LDS)");
+    return NERF_AMD_OK;
+}
+int check_interlevel(int64_t N, int M, int K, int Kp) {
+    if (N < 0) return fail(NERF_AMD_EINVAL, "negative ray count");
+    if (M < 1 || M > NERF_AMD_INTERLEVEL_MAX || K < 1 || K > NERF_AMD_INTERLEVEL_MAX)
+        return fail(NERF_AMD_EINVAL, "bad size (M and K must be 1..1024 intervals per row: a ray's rows live in LDS)");
+    if (Kp != K && Kp != K + 1) return fail(NERF_AMD_EINVAL, "bad size (t_prop has K + 1 edges per row, or K depths: the last interval open)");
     return NERF_AMD_OK;
 }
 // disparity ray spacing: 0 < near < far, the only kind the warped entry points accept; gn = fp32(1/near), gf = fp32(1/far), each computed in
@@ -475,6 +484,20 @@ int nerf_amd_distortion_loss_backward(const float* w, const float* t, int64_t N,
     if (int e = check_distortion(N, Sn, mode)) return e;
     if (N && (!w || !t || !g)) return fail(NERF_AMD_EINVAL, "NULL argument");
     return hip_status(sk_distortion_loss_backward(w, t, N, Sn, mode, scale, g, d_w, d_t, S(stream)), "nerf_amd_distortion_loss_backward");
+}
+
+int nerf_amd_interlevel_loss(const float* w, const float* t, const float* w_prop, const float* t_prop, int64_t N, int M, int K, int Kp, float scale,
+                             float* out, float* bounds_out, float* workspace, void* stream) {
+    if (int e = check_interlevel(N, M, K, Kp)) return e;
+    if (!out || !workspace || (N && (!w || !t || !w_prop || !t_prop))) return fail(NERF_AMD_EINVAL, "NULL argument");
+    return hip_status(sk_interlevel_loss(w, t, w_prop, t_prop, N, M, K, Kp, scale, out, bounds_out, workspace, S(stream)), "nerf_amd_interlevel_loss");
+}
+
+int nerf_amd_interlevel_loss_backward(const float* w, const float* t, const float* w_prop, const float* t_prop, int64_t N, int M, int K, int Kp,
+                                      float scale, const float* g, float* d_w_prop, void* stream) {
+    if (int e = check_interlevel(N, M, K, Kp)) return e;
+    if (N && (!w || !t || !w_prop || !t_prop || !g || !d_w_prop)) return fail(NERF_AMD_EINVAL, "NULL argument");
+    return hip_status(sk_interlevel_loss_backward(w, t, w_prop, t_prop, N, M, K, Kp, scale, g, d_w_prop, S(stream)), "nerf_amd_interlevel_loss_backward");
 }
 
 int nerf_amd_mfma_stream(int iters, int workgroups, int mode, float* sink, void* stream) {

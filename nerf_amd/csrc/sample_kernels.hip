@@ -1723,6 +1723,139 @@ __global__ __launch_bounds__(256) void distortion_loss_backward_kernel(const flo
     }
 }
 
+// ---------------------------------------------------------------------------------------- interlevel loss L_prop (include/nerf_amd.h)
+// One wavefront per ray.  Per wave in LDS: c[K+1] (fp64 exclusive prefix sum of w_prop), F[M+1] (backward only: fp64 prefix sum of the
+// per-interval factors), tf[M+1] (fine edges), te[K+1] (proposal edges, +inf appended in the open form): 12 (M + K + 2) bytes at most,
+// 24.6 KB at M = K = 1024.  Up to IL_WAVE_BUDGET per wave the workgroup holds four waves (64 KiB of LDS), above it two (il_waves).
+// Every search is a binary search over an ascending LDS row whose result is clamped into the row, so rows that are not ascending
+// (or NaN) give some bound, never an access outside the row.
+constexpr int IL_BLOCKS = 1024;                      // forward grid cap: the workspace's fp64 partials (NERF_AMD_INTERLEVEL_WORKSPACE_FLOATS / 2)
+constexpr size_t IL_WAVE_BUDGET = 16 * 1024;
+static inline __host__ __device__ size_t il_wave_bytes(int M, int K, bool bwd) {
+    const size_t b = (size_t)8 * (K + 1) + (bwd ? (size_t)8 * (M + 1) : 0) + (size_t)4 * (M + K + 2);
+    return (b + 7) & ~(size_t)7;
+}
+static inline int il_waves(int M, int K, bool bwd) { return il_wave_bytes(M, K, bwd) <= IL_WAVE_BUDGET ? 4 : 2; }
+struct IlRows { double* c; double* F; float* tf; float* te; };
+DEVINL IlRows il_rows(int M, int K, bool bwd) {
+    IlRows r;
+    r.c = reinterpret_cast<double*>(smem + (size_t)wave_in_block() * il_wave_bytes(M, K, bwd));
+    r.F = r.c + (K + 1);
+    r.tf = reinterpret_cast<float*>(r.F + (bwd ? M + 1 : 0));
+    r.te = r.tf + (M + 1);
+    return r;
+}
+DEVINL int il_count_le(const float* a, int n, float v) {                                     // #{k < n : a_k <= v}, a ascending
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] <= v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+DEVINL int il_count_lt(const float* a, int n, float v) {                                     // #{k < n : a_k < v}
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+// the wave's rows of ray n: edges as they are, c by a wave scan per 64 columns with the running total carried over (a fixed order)
+DEVINL void il_stage(const float* __restrict__ t, const float* __restrict__ w_prop, const float* __restrict__ t_prop, int64_t n, int M, int K, int Kp,
+                     const IlRows& r) {
+    const int lane = lane_id();
+    const float* tn = t + n * (M + 1);
+    const float* en = t_prop + n * Kp;
+    const float* pn = w_prop + n * K;
+    for (int i = lane; i <= M; i += 64) r.tf[i] = tn[i];
+    for (int j = lane; j <= K; j += 64) r.te[j] = j < Kp ? en[j] : __builtin_inff();
+    if (lane == 0) r.c[0] = 0.0;
+    double carry = 0.0;
+    for (int base = 0; base < K; base += 64) {
+        const int j = base + lane;
+        const double v = wave_incl_scan_add(j < K ? (double)pn[j] : 0.0) + carry;
+        if (j < K) r.c[j + 1] = v;
+        carry = wave_last(v);
+    }
+}
+DEVINL double il_bound(const IlRows& r, int K, int i) {
+    const int cl = il_count_le(r.te, K + 1, r.tf[i]), ch = il_count_le(r.te, K + 1, r.tf[i + 1]);
+    return r.c[ch < K ? ch : K] - r.c[cl > 0 ? cl - 1 : 0];                                  // c[hi(t_i+1)] - c[lo(t_i)]
+}
+
+__global__ __launch_bounds__(256) void interlevel_loss_kernel(const float* __restrict__ w, const float* __restrict__ t, const float* __restrict__ w_prop,
+                                                              const float* __restrict__ t_prop, int64_t N, int M, int K, int Kp,
+                                                              double* __restrict__ partial, float* __restrict__ bounds_out) {
+    const int waves = (int)(blockDim.x >> 6), lane = lane_id();
+    const IlRows r = il_rows(M, K, false);
+    double acc = 0.0;
+    for (int64_t n = blockIdx.x * (int64_t)waves + wave_in_block(); n < N; n += (int64_t)gridDim.x * waves) {
+        lds_wave_sync();
+        il_stage(t, w_prop, t_prop, n, M, K, Kp, r);
+        lds_wave_sync();
+        const float* wn = w + n * M;
+        for (int i = lane; i < M; i += 64) {
+            const double b = il_bound(r, K, i), wi = (double)wn[i];
+            const double d = wi - b > 0.0 ? wi - b : 0.0;
+            acc += d * d / (wi + 1e-8);
+            if (bounds_out) bounds_out[n * M + i] = (float)b;
+        }
+    }
+    acc = wave_sum_d(acc);
+    __syncthreads();                                                                         // (the rows' LDS becomes the block's reduction slots)
+    double* red = reinterpret_cast<double*>(smem);
+    if (lane == 0) red[wave_in_block()] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double s = red[0];
+        for (int k = 1; k < waves; ++k) s += red[k];
+        partial[blockIdx.x] = s;
+    }
+}
+__global__ __launch_bounds__(256) void interlevel_loss_final_kernel(const double* __restrict__ partial, int n, float scale, float* __restrict__ out) {
+    double p = 0.0;
+    for (int i = threadIdx.x; i < n; i += 256) p += partial[i];
+    p = wave_sum_d(p);
+    double* red = reinterpret_cast<double*>(smem);
+    if (lane_id() == 0) red[wave_in_block()] = p;
+    __syncthreads();
+    if (threadIdx.x == 0) out[0] = (float)((((red[0] + red[1]) + red[2]) + red[3]) * (double)scale);
+}
+__global__ __launch_bounds__(256) void interlevel_loss_backward_kernel(const float* __restrict__ w, const float* __restrict__ t,
+                                                                       const float* __restrict__ w_prop, const float* __restrict__ t_prop, int64_t N,
+                                                                       int M, int K, int Kp, float scale, const float* __restrict__ g,
+                                                                       float* __restrict__ d_w_prop) {
+    const int waves = (int)(blockDim.x >> 6), lane = lane_id();
+    const IlRows r = il_rows(M, K, true);
+    const double gs = (double)g[0] * (double)scale;
+    for (int64_t n = blockIdx.x * (int64_t)waves + wave_in_block(); n < N; n += (int64_t)gridDim.x * waves) {
+        lds_wave_sync();
+        il_stage(t, w_prop, t_prop, n, M, K, Kp, r);
+        lds_wave_sync();
+        const float* wn = w + n * M;
+        if (lane == 0) r.F[0] = 0.0;                                                         // F_i = sum_{i' < i} -2 relu(w_i' - bound_i') / (w_i' + 1e-8)
+        double carry = 0.0;
+        for (int base = 0; base < M; base += 64) {
+            const int i = base + lane;
+            double f = 0.0;
+            if (i < M) {
+                const double wi = (double)wn[i], d = wi - il_bound(r, K, i);
+                if (d > 0.0) f = -2.0 * d / (wi + 1e-8);
+            }
+            f = wave_incl_scan_add(f) + carry;
+            if (i < M) r.F[i + 1] = f;
+            carry = wave_last(f);
+        }
+        lds_wave_sync();
+        for (int j = lane; j < K; j += 64) {                                                 // the fine intervals over proposal interval j: [i0, i1)
+            const int i1 = il_count_lt(r.tf, M, r.te[j + 1]);                                //   t_i < e_j+1
+            const int i0 = il_count_lt(r.tf + 1, M, r.te[j]);                                //   t_i+1 >= e_j
+            d_w_prop[n * K + j] = (float)(i1 > i0 ? gs * (r.F[i1] - r.F[i0]) : 0.0);
+        }
+    }
+}
+
 int blocks_for(int64_t work, int per_block) {
     int64_t b = (work + per_block - 1) / per_block;
     const int64_t cap = 256 * 8;
@@ -2041,6 +2174,27 @@ int sk_distortion_loss_backward(const float* w, const float* t, int64_t N, int S
         if (int e = nerf_host::allow_dynamic_lds(reinterpret_cast<const void*>(distortion_loss_backward_kernel<0>), lds)) return e;
     if (mode == 0) hipLaunchKernelGGL(distortion_loss_backward_kernel<0>, grid, block, lds, st, w, t, N, S, scale, g, d_w, d_t);
     else hipLaunchKernelGGL(distortion_loss_backward_kernel<1>, grid, block, lds, st, w, t, N, S, scale, g, d_w, d_t);
+    return (int)hipGetLastError();
+}
+// 1 <= M, K <= 1024 (checked by the C-ABI): four waves x <= 16 KiB or two waves x <= 24.6 KB of rows, always within the default 64 KiB
+int sk_interlevel_loss(const float* w, const float* t, const float* w_prop, const float* t_prop, int64_t N, int M, int K, int Kp, float scale, float* out,
+                       float* bounds_out, float* workspace, hipStream_t st) {
+    const int waves = il_waves(M, K, false);
+    int64_t nb = (N + waves - 1) / waves;
+    const int blocks = (int)(nb > IL_BLOCKS ? IL_BLOCKS : (nb < 1 ? 1 : nb));
+    size_t lds = (size_t)waves * il_wave_bytes(M, K, false);
+    if (lds < 64) lds = 64;                                                                  // (the block reduction's doubles)
+    double* partial = reinterpret_cast<double*>(workspace);
+    hipLaunchKernelGGL(interlevel_loss_kernel, dim3(blocks), dim3(64 * waves), lds, st, w, t, w_prop, t_prop, N, M, K, Kp, partial, bounds_out);
+    hipLaunchKernelGGL(interlevel_loss_final_kernel, dim3(1), dim3(256), 64, st, partial, blocks, scale, out);
+    return (int)hipGetLastError();
+}
+int sk_interlevel_loss_backward(const float* w, const float* t, const float* w_prop, const float* t_prop, int64_t N, int M, int K, int Kp, float scale,
+                                const float* g, float* d_w_prop, hipStream_t st) {
+    if (N == 0) return 0;
+    const int waves = il_waves(M, K, true);
+    hipLaunchKernelGGL(interlevel_loss_backward_kernel, dim3(blocks_for(N, waves)), dim3(64 * waves), (size_t)waves * il_wave_bytes(M, K, true), st, w, t,
+                       w_prop, t_prop, N, M, K, Kp, scale, g, d_w_prop);
     return (int)hipGetLastError();
 }
 int sk_encode_rows(const float* x, int x_stride, int64_t M, int L, int normalize, int elem_bytes, void* out, hipStream_t st) {

@@ -683,6 +683,42 @@ def distortion_loss_backward(g: torch.Tensor, w: torch.Tensor, t: torch.Tensor, 
     return d_w, d_t
 
 
+INTERLEVEL_MAX = 1024                      # NERF_AMD_INTERLEVEL_MAX: intervals per row of either histogram
+INTERLEVEL_WORKSPACE_FLOATS = 2048
+
+
+def _interlevel_args(w: torch.Tensor, t: torch.Tensor, w_prop: torch.Tensor, t_prop: torch.Tensor):
+    w, t, w_prop, t_prop = _dev(w, "weights"), _dev(t, "t"), _dev(w_prop, "prop_weights"), _dev(t_prop, "prop_edges")
+    ok = w.dim() == t.dim() == w_prop.dim() == t_prop.dim() == 2 and w.shape[0] == t.shape[0] == w_prop.shape[0] == t_prop.shape[0]
+    if not (ok and t.shape[1] == w.shape[1] + 1 and t_prop.shape[1] - w_prop.shape[1] in (0, 1)):
+        raise ValueError("nerf_amd: interlevel_loss needs weights (N, M), t (N, M + 1), prop_weights (N, K) and prop_edges (N, K + 1) or (N, K); "
+                         "got %s, %s, %s, %s" % (tuple(w.shape), tuple(t.shape), tuple(w_prop.shape), tuple(t_prop.shape)))
+    return w, t, w_prop, t_prop, w.shape[0], w.shape[1], w_prop.shape[1], t_prop.shape[1]
+
+
+def interlevel_loss(w: torch.Tensor, t: torch.Tensor, w_prop: torch.Tensor, t_prop: torch.Tensor, scale: float, want_bounds: bool = False):
+    """scale * Mip-NeRF 360 interlevel loss -> 0-dim tensor (with want_bounds: (loss, bounds (N, M))): the fine histogram w (N, M) over the
+    ascending edges t (N, M + 1) against the proposal histogram w_prop (N, K) over t_prop (N, K + 1), or over the K sample depths
+    t_prop (N, K) with the last interval open to +inf (include/nerf_amd.h)"""
+    w, t, w_prop, t_prop, N, M, K, Kp = _interlevel_args(w, t, w_prop, t_prop)
+    out = torch.empty((1,), dtype=torch.float32, device=t.device)
+    ws = torch.empty((INTERLEVEL_WORKSPACE_FLOATS,), dtype=torch.float32, device=t.device)
+    bounds = torch.empty((N, M), dtype=torch.float32, device=t.device) if want_bounds else None
+    check(lib.nerf_amd_interlevel_loss(_ptr(w), _ptr(t), _ptr(w_prop), _ptr(t_prop), N, M, K, Kp, float(scale), _ptr(out), _ptr(bounds), _ptr(ws),
+                                       _stream()), "nerf_amd_interlevel_loss")
+    return (out.reshape(()), bounds) if want_bounds else out.reshape(())
+
+
+def interlevel_loss_backward(g: torch.Tensor, w: torch.Tensor, t: torch.Tensor, w_prop: torch.Tensor, t_prop: torch.Tensor, scale: float) -> torch.Tensor:
+    """gradient of interlevel_loss w.r.t. w_prop (N, K) for the upstream gradient g (a 0-dim device tensor); it has no other gradient"""
+    w, t, w_prop, t_prop, N, M, K, Kp = _interlevel_args(w, t, w_prop, t_prop)
+    g = _dev(g, "g").reshape(1)
+    d_w_prop = torch.empty_like(w_prop)
+    check(lib.nerf_amd_interlevel_loss_backward(_ptr(w), _ptr(t), _ptr(w_prop), _ptr(t_prop), N, M, K, Kp, float(scale), _ptr(g), _ptr(d_w_prop),
+                                                _stream()), "nerf_amd_interlevel_loss_backward")
+    return d_w_prop
+
+
 def merge_depths(z_fine: torch.Tensor, z_coarse: torch.Tensor) -> torch.Tensor:
     """sort(cat(z_fine, z_coarse))[..., :-1] (the render path of coarseFineMerge): a merge when both sets are ascending, which they
     normally are; rays with an out-of-order input are sorted first."""

@@ -49,7 +49,8 @@ GENERIC_CHUNK_RAYS = 4096
 
 def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, render_depth, chunk: Optional[int] = None,
                           is_ref_model: bool = False, cam_dir=None, seed: Optional[int] = None, ray_offset: int = 0, contract: bool = False,
-                          ipe_radius: Optional[float] = None, ipe_dir_norm=None, *, spacing: str = "linear"):
+                          ipe_radius: Optional[float] = None, ipe_dir_norm=None, *, spacing: str = "linear", prop_rounds: int = 1,
+                          prop_pnum: Optional[int] = None):
     """The tile body of procedures.py:62-85 as the reference writes it -- stratified depths, ProposalNetwork.forward, get_weights,
     maxBlurFilter, inverseSample, NeRF.length2pts, network.forward, NeRF.render -- on chunks of rays: the route of networks the fused
     render entry (nerf_amd_render_rays) has no packed layout for.  Every call is a HIP kernel of this package; uniforms that were not
@@ -57,7 +58,11 @@ def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sampl
     seeded render does not depend on whether a network runs fused or layer by layer.
     ``spacing="disparity"`` (Mip-NeRF 360's s-space, include/nerf_amd.h): the coarse draw and the resampling happen in the normalised
     distance s, everything else -- weights, coarseFineMerge (W is monotone: the order is that of s), encodings, compositing -- on the metric
-    depths W(s); the depth is W^-1 of the expected metric depth."""
+    depths W(s); the depth is W^-1 of the expected metric depth.
+    ``prop_rounds=2`` (Mip-NeRF 360's two proposal rounds; Philox uniforms only): between the proposal pass and the fine resampling,
+    ``prop_pnum`` sorted depths are resampled from the first histogram, the proposal network is evaluated there and the fine depths are
+    drawn from that second histogram.  The ray's inverse-CDF stream then has prop_pnum + sample_num + 1 columns: the first prop_pnum feed
+    the second round, the rest the fine resampling."""
     from .mip_methods import maxBlurFilter
     from .utils import inverseSample
     N = rays.shape[0]
@@ -71,13 +76,26 @@ def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sampl
         r = rays[s: s + chunk].contiguous()
         n = r.shape[0]
         u1 = u_strat[s: s + n] if u_strat is not None else ops.philox_stream((n, RENDER_COARSE_PNUM), seed, ray_offset + s, strat=True, device=rays.device)
-        u2 = u_inv[s: s + n] if u_inv is not None else ops.philox_stream((n, sample_num + 1), seed, ray_offset + s, device=rays.device)
+        if prop_rounds == 2:
+            u12 = ops.philox_stream((n, prop_pnum + sample_num + 1), seed, ray_offset + s, device=rays.device)
+            u_mid, u2 = u12[:, :prop_pnum].contiguous(), u12[:, prop_pnum:]
+        else:
+            u2 = u_inv[s: s + n] if u_inv is not None else ops.philox_stream((n, sample_num + 1), seed, ray_offset + s, device=rays.device)
         if warped:
             s_c, z, pts = ops.warped_stratified(r, u1.contiguous(), near, far, spacing=spacing)
         else:
             z, pts = ops.stratified_points(r, z_base, u1.contiguous(), resolution)  # :65-66
         density = prop_net.forward(pts, contract=True) if contract else prop_net.forward(pts)
         prop_w = maxBlurFilter(ProposalNetwork.get_weights(density, z, r[:, 3:]), 0.01)
+        if prop_rounds == 2:                                                         # the second histogram: the same network at depths drawn from the first
+            if warped:
+                s_c, _ = inverseSample(prop_w, s_c, prop_pnum, sort=True, u=u_mid)
+                z, pts = ops.warp_depths(s_c, near, far, r, spacing=spacing)
+            else:
+                z, _ = inverseSample(prop_w, z, prop_pnum, sort=True, u=u_mid)
+                pts = NeRF.length2pts(r, z)[..., :3].contiguous()
+            density = prop_net.forward(pts, contract=True) if contract else prop_net.forward(pts)
+            prop_w = maxBlurFilter(ProposalNetwork.get_weights(density, z, r[:, 3:]), 0.01)
         if warped:                                                                   # resample in s, then back to metric depths
             s_f, _ = inverseSample(prop_w, s_c, sample_num + 1, sort=True, u=u2.contiguous())
             fine = ops.warp_depths(s_f, near, far, spacing=spacing)[0]
@@ -120,7 +138,7 @@ def _check_spacing(spacing, near, far) -> bool:
 def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Tensor, image_size, focal,
                  near: float, far: float, sample_num: int = 128, white_bkg: bool = False, render_depth=False,
                  render_normal=False, rng: str = "philox", contract: bool = False, ipe=False, seed: Optional[int] = None,
-                 _shard=None, *, spacing: str = "linear") -> dict:
+                 _shard=None, *, spacing: str = "linear", prop_rounds: int = 1, prop_pnum: Optional[int] = None) -> dict:
     """Whole-image inference (procedures.py:34-97) -> {"rgb" (3,H,W) [, "depth_img" (3,H,W)]} on
     ``render_pose.device``.  The caller provides ``no_grad``/``eval()`` like for the reference.
     ``rng``, ``contract`` and ``ipe`` are additions.  ``rng``: where the stratified / inverse-CDF uniforms come from --
@@ -146,7 +164,22 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
     background; ``depth_img`` is then W^-1 of the expected depth, in [0, 1].  The compiled-shape MipNeRF goes through
     nerf_amd_render_rays_warped; Ref-NeRF and layer-by-layer networks through the call-by-call route, on the same Philox streams.
     The disparity resampling kernel keeps four rays' rows in 64 KiB of LDS: ``sample_num`` <= 623 under "disparity" (a larger count
-    raises; "linear" takes up to 1023)."""
+    raises; "linear" takes up to 1023).
+    ``prop_rounds`` (keyword-only; an addition): 2 = Mip-NeRF 360's two proposal rounds, for a model trained with
+    ``TrainStep(prop_rounds=2)``: ``prop_pnum`` (default: the 64 coarse samples' count) sorted depths are resampled from the first proposal
+    histogram, the same proposal network is evaluated there, and the fine depths are drawn from that second histogram.  Every network
+    then takes the call-by-call route (no fused two-round entry point: well below the fused rate, profiles/interlevel_summary.md);
+    ``rng="philox"`` only -- each ray's inverse-CDF stream simply has prop_pnum more columns, still a pure function of (seed, global ray
+    index), so shards reproduce the whole image bit for bit; not available for Ref-NeRF."""
+    if prop_rounds not in (1, 2):
+        raise ValueError("nerf_amd.render_image: prop_rounds must be 1 or 2 (got %r)" % (prop_rounds,))
+    if prop_pnum is not None and int(prop_pnum) < 1:
+        raise ValueError("nerf_amd.render_image: prop_pnum must be positive")
+    if prop_rounds == 2 and rng != "philox":
+        raise ValueError("nerf_amd.render_image: prop_rounds=2 needs rng='philox' (the second round's uniforms are further columns of the ray's Philox stream)")
+    if prop_rounds == 2 and type(network).__name__ == "RefNeRF":
+        raise NotImplementedError("nerf_amd.render_image: the second proposal round is wired for the MipNeRF render path only")
+    prop_pnum = RENDER_COARSE_PNUM if prop_pnum is None else int(prop_pnum)
     if not isinstance(image_size, Iterable):
         image_size = (image_size, image_size)
     is_ref_model = type(network).__name__ == "RefNeRF"
@@ -192,7 +225,12 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
         ipe_radius = (2.0 / (12.0 ** 0.5) / fx) if ipe is True else float(ipe)
     generic = network._generic() or prop_net._generic()
     warped = _check_spacing(spacing, near, far)
-    if warped and is_ref_model and not generic:
+    if prop_rounds == 2:
+        # no fused two-round entry point: the tile body call by call for every network, on the Philox streams of the global ray index
+        rgb, depth, _ = _render_rays_by_calls(network, prop_net, rays, z_base, None, None, sample_num, near, far, white_bkg, bool(render_depth),
+                                              seed=seed, ray_offset=off, contract=contract, ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm,
+                                              spacing=spacing, prop_rounds=2, prop_pnum=prop_pnum)
+    elif warped and is_ref_model and not generic:
         # the fused Ref-NeRF entry point has no disparity twin: the call-by-call tile body on the packed kernels, same Philox streams
         rgb, depth, normal_px = _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, bool(render_depth),
                                                       is_ref_model=True, cam_dir=render_pose[:, -2].contiguous() if render_normal else None, seed=seed,

@@ -36,7 +36,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .addtional import DistortionLoss, ProposalLoss, ProposalNetwork, getBounds
+from .addtional import DistortionLoss, InterlevelLoss, ProposalLoss, ProposalNetwork, getBounds
 from .mip_methods import maxBlurFilter
 from .nerf_base import NeRF
 from .optim import Adam
@@ -66,7 +66,8 @@ class TrainStep:
     def __init__(self, prop_net, mip_net, optimizer: Adam, image_hw: Tuple[int, int], focal, near: float, far: float, ray_num: int = 512,
                  coarse_pnum: int = 64, fine_pnum: int = 128, crop_xy=(1.0, 1.0), seed: Optional[int] = None, white_bkg: bool = False,
                  prop_normal: bool = False, grad_hook=None, ipe_radius: Optional[float] = None, contract: bool = False, flat_grads=None,
-                 *, scene=None, view_ids=None, spacing: str = "linear", grad_clip: float = -0.01, distortion: float = 0.0):
+                 *, scene=None, view_ids=None, spacing: str = "linear", prop_loss: str = "reference", prop_rounds: int = 1,
+                 prop_pnum: Optional[int] = None, grad_clip: float = -0.01, distortion: float = 0.0):
         """``grad_hook``: called between ``loss.backward()`` and ``optimizer.step()`` -- the place of ddp_train.py's gradient all-reduce
         (``lambda: parallel.allreduce_gradients([mip_net, prop_net])``).  An iteration with a hook runs eagerly (``capture`` refuses).
         ``ipe_radius`` (BASELINE configs[2]): the fine network encodes the conical frusta between consecutive fine depths with the
@@ -97,7 +98,17 @@ class TrainStep:
         coarse samples and resamples in Mip-NeRF 360's normalised distance s (include/nerf_amd.h): the samplers are called with near = 0,
         far = 1 so that their ``lengths`` are s_c, positions and every weight use the metric depths W(s), inverseSample runs on s_c, and
         L_dist is evaluated on the sorted s_f directly (no 1 / (far - near) rescale).  Needs 0 < near < far.
-        ``scene``, ``view_ids``, ``spacing``, ``grad_clip`` and ``distortion`` are keyword-only (their order carries no meaning)."""
+        ``prop_loss`` (BASELINE configs[4]; not in the reference): "reference" (default) = getBounds + ProposalLoss on the sampler's bin
+        indices; "interlevel" = Mip-NeRF 360's L_prop (addtional.InterlevelLoss) between the fine histogram -- the fine weights over the
+        fine_pnum + 1 sorted fine depths, the edges of L_dist -- and the proposal histogram -- the proposal weights over the coarse depths,
+        the last interval open --, by geometric overlap; under "disparity" both edge rows are the s rows (the warp is monotone).  The term of
+        the last iteration is ``self.prop_loss_value`` (written under "interlevel" only: the default iteration launches nothing new).
+        ``prop_rounds`` = 2 (needs "interlevel"): Mip-NeRF 360's two proposal rounds from the one proposal network -- round 1 as before
+        gives w1 over z_c; ``prop_pnum`` (default ``coarse_pnum``) depths z_2 are resampled from it (sorted; in s under "disparity"), the
+        same network is evaluated there and gives w2 over z_2, the fine depths are drawn from (w2, z_2); the loss term is
+        L(w_fine, z_f; w1, z_c) + L(w_fine, z_f; w2, z_2).  The two resamplings use disjoint columns of one Philox draw for the step's seed.
+        ``scene``, ``view_ids``, ``spacing``, ``grad_clip``, ``distortion``, ``prop_loss``, ``prop_rounds`` and ``prop_pnum`` are
+        keyword-only (their order carries no meaning)."""
         if not isinstance(optimizer, Adam) or not optimizer.lr_on_device:
             raise ValueError("nerf_amd.training.TrainStep needs nerf_amd.optim.Adam(..., lr_on_device=True): the step must not read host state")
         self.prop_net, self.mip_net, self.opt = prop_net, mip_net, optimizer
@@ -117,6 +128,20 @@ class TrainStep:
         if self.is_ref and self.distortion > 0.0:
             raise NotImplementedError("nerf_amd.training.TrainStep: the distortion loss is wired for the MipNeRF branch (the Ref-NeRF step's merged "
                                       "sample set has no closed last interval)")
+        if prop_loss not in ("reference", "interlevel"):
+            raise ValueError("nerf_amd.training.TrainStep: prop_loss must be 'reference' or 'interlevel' (got %r)" % (prop_loss,))
+        if prop_rounds not in (1, 2):
+            raise ValueError("nerf_amd.training.TrainStep: prop_rounds must be 1 or 2 (got %r)" % (prop_rounds,))
+        if prop_rounds == 2 and prop_loss != "interlevel":
+            raise ValueError("nerf_amd.training.TrainStep: prop_rounds=2 needs prop_loss='interlevel' (the reference's bound reads the bin "
+                             "indices of the one sampler call that produced the fine depths)")
+        if prop_pnum is not None and int(prop_pnum) < 1:
+            raise ValueError("nerf_amd.training.TrainStep: prop_pnum must be positive")
+        if self.is_ref and (prop_loss != "reference" or prop_rounds != 1):
+            raise NotImplementedError("nerf_amd.training.TrainStep: the interlevel loss and the second proposal round are wired for the MipNeRF "
+                                      "branch (the Ref-NeRF step's merged sample set is a different histogram)")
+        self.prop_loss, self.prop_rounds = prop_loss, int(prop_rounds)
+        self.prop_pnum = self.coarse_pnum if prop_pnum is None else int(prop_pnum)
         self.prop_normal = bool(prop_normal) and self.is_ref                              # (train.py: prop_normal only acts with a Ref-NeRF)
         dev = next(mip_net.parameters()).device
         H, W = image_hw
@@ -158,6 +183,8 @@ class TrainStep:
         if self.is_ref:                                      # the bottle-neck perturbation keyed by this step's device-resident seed
             mip_net.__dict__["noise_seed_dev"] = self.seed   # (RefNeRF.forward, noise_rng "philox": a replayed graph draws fresh noise)
         self.prop_loss_fn = ProposalLoss()
+        self.interlevel_fn = InterlevelLoss() if self.prop_loss == "interlevel" else None
+        self.prop_loss_value = torch.zeros((), dtype=torch.float32, device=dev)
         self.grad_hook = grad_hook
         # an explicitly passed FlatGradients is a request for data-parallel averaging; the default one only holds the gradients (ranks of a
         # model-averaging run, model_average.py, train independently: no implicit collective)
@@ -211,7 +238,21 @@ class TrainStep:
             coarse_grad = -RefNeRF.get_grad(density, pts)                                               # :167-168
         density = F.softplus(density)                                                                   # :169
         prop_w = maxBlurFilter(ProposalNetwork.get_weights(density, z_c, dirs), 0.01)                   # :170-171
-        u = ops.philox_uniforms((self.ray_num, self.fine_pnum + 1), seed_dev=self.seed)
+        if self.prop_rounds == 2:
+            # one draw, split by column: the two resamplings get independent uniforms (not a shared prefix of one stream)
+            u12 = ops.philox_uniforms((self.ray_num, self.prop_pnum + self.fine_pnum + 1), seed_dev=self.seed)
+            u = u12[:, self.prop_pnum:].contiguous()
+            w1, e1 = prop_w, (s_c if self.warped else z_c)
+            if self.warped:
+                s_c = inverseSample(w1, e1, self.prop_pnum, sort=True, u=u12[:, :self.prop_pnum].contiguous())[0].detach()
+                z_c, pts = ops.warp_depths(s_c, self.near, self.far, rays, spacing=self.spacing)
+            else:
+                z_c = inverseSample(w1, e1, self.prop_pnum, sort=True, u=u12[:, :self.prop_pnum].contiguous())[0].detach()
+                pts = NeRF.length2pts(rays, z_c)[..., :3].contiguous()
+            density = F.softplus(self.prop_net.forward(pts, contract=True) if self.contract else self.prop_net.forward(pts))
+            prop_w = maxBlurFilter(ProposalNetwork.get_weights(density, z_c, dirs), 0.01)               # w2 over z_2: what the fine depths come from
+        else:
+            u = ops.philox_uniforms((self.ray_num, self.fine_pnum + 1), seed_dev=self.seed)
         if self.warped:                                                                                 # resample in s, back to metric depths
             s_f, below = inverseSample(prop_w, s_c, self.fine_pnum + 1, sort=True, u=u)
             z_f = ops.warp_depths(s_f, self.near, self.far, spacing=self.spacing)[0]
@@ -245,13 +286,20 @@ class TrainStep:
             rendered, weights, _ = NeRF.render(rgbo, z_f, dirs, white_bkg=self.white_bkg)               # :191
             if self.dist_fn is not None:
                 extra = self.dist_fn(weights, edges)
-        bounds = getBounds(prop_w, below)                                                               # :192
+        if self.interlevel_fn is None:
+            bounds = getBounds(prop_w, below)                                                           # :192
         if self.flat_grads is not None:
             self.flat_grads.bind(); self.flat_grads.begin_step()                                        # (the kernels overwrite: no zeroing pass)
         else:
             self.opt.zero_grad(set_to_none=True)
         img_loss = torch.mean((rendered - rgb_tgt) ** 2)                                                # :194 (nn.MSELoss)
-        loss = self.prop_loss_fn(bounds, weights.detach()) + img_loss + extra                           # :196-198
+        if self.interlevel_fn is None:
+            l_prop = self.prop_loss_fn(bounds, weights.detach())
+        else:
+            l_prop = self.interlevel_fn(weights, edges, prop_w, s_c if self.warped else z_c)
+            if self.prop_rounds == 2:
+                l_prop = self.interlevel_fn(weights, edges, w1, e1) + l_prop
+        loss = l_prop + img_loss + extra                                                                # :196-198
         loss.backward()
         if self._reduce:
             self.flat_grads.all_reduce()                                                                # ddp_train.py:98, as one collective
@@ -270,6 +318,8 @@ class TrainStep:
         self.img_loss.copy_(img_loss.detach())
         if self.dist_fn is not None:
             self.dist_loss.copy_(extra.detach())
+        if self.interlevel_fn is not None:
+            self.prop_loss_value.copy_(l_prop.detach())
 
     # ---------------------------------------------------------------------------------------------------------------- driving it
     def set_image(self, img: torch.Tensor, pose: torch.Tensor) -> None:
