@@ -29,6 +29,7 @@
 #include <type_traits>
 
 #include "mlp_core.h"
+#include "launchers.h"
 
 namespace {
 
@@ -1382,7 +1383,9 @@ int bwd_grid(int64_t n_tiles) {
 // TU 3 (round 4): the Ref-NeRF DIRECTIONAL chain alone, compiled WITHOUT -amdgpu-mfma-vgpr-form: with the bit-mask functor hipcc's
 // AGPR-copy rewrite pass segfaults on this one kernel (AMDGPURewriteAGPRCopyMFMA, eliminateSpillsOfReassignedVGPRs); without the flag it
 // compiles with 65 spilled registers (91 in round 3's activation-mask form with the flag).
+}  // namespace
 #if BWD_TU == 3 || BWD_TU == 0
+namespace {
 template <class P>
 int launch_dir_chain_t(const char* stream, int64_t M, const char* masks, size_t ms, char* dlt, size_t ls, float* rows, hipStream_t st) {
     constexpr int TS = P::NW * P::NT * 32;
@@ -1395,20 +1398,13 @@ int launch_dir_chain_t(const char* stream, int64_t M, const char* masks, size_t 
     return (int)hipGetLastError();
 }
 }  // namespace
-int bwd_launch_dir_chain(int precision, const char* stream, int64_t M, const char* masks, size_t ms, char* dlt, size_t ls, float* rows, hipStream_t st) {
+int nk::bwd_launch_dir_chain(int precision, const char* stream, int64_t M, const char* masks, size_t ms, char* dlt, size_t ls, float* rows, hipStream_t st) {
     if (precision == NERF_AMD_BF16) return launch_dir_chain_t<PB16>(stream, M, masks, ms, dlt, ls, rows, st);
     return launch_dir_chain_t<PF32>(stream, M, masks, ms, dlt, ls, rows, st);
 }
-#if BWD_TU != 3
-namespace {
-#endif
-#endif
-#if BWD_TU == 2
-}  // namespace
-int bwd_launch_dir_chain(int precision, const char* stream, int64_t M, const char* masks, size_t ms, char* dlt, size_t ls, float* rows, hipStream_t st);
-namespace {
 #endif
 #if BWD_TU != 1 && BWD_TU != 3
+namespace {
 template <class P>
 int launch_chain_t(int which, const char* stream, int64_t M, const char* act, char* dlt, size_t ls, size_t ms, float* rows, hipStream_t st) {
     // the forward's ReLU bit-mask records sit behind the activation slots of its dump (17 slots for Ref-NeRF, 5 for the proposal network)
@@ -1420,7 +1416,7 @@ int launch_chain_t(int which, const char* stream, int64_t M, const char* act, ch
     const dim3 grid(bwd_grid(n_tiles)), block(P::NW * 64);
     switch (which) {
         case 0:                                                // (its own translation unit: see bwd_launch_dir_chain)
-            return bwd_launch_dir_chain(P::PREC, stream, M, masks, ms, dlt, ls, rows, st);
+            return nk::bwd_launch_dir_chain(P::PREC, stream, M, masks, ms, dlt, ls, rows, st);
         case 1:
             if (int e = nerf_host::allow_dynamic_lds(reinterpret_cast<const void*>(ref_spa_bwd_kernel<P>), lds)) return e;
             hipLaunchKernelGGL((ref_spa_bwd_kernel<P>), grid, block, lds, st, stream, M, masks, (unsigned long long)ms, dlt, (unsigned long long)ls);
@@ -1438,9 +1434,7 @@ int launch_chain_t(int which, const char* stream, int64_t M, const char* act, ch
 // which: 0 Ref-NeRF directional, 1 Ref-NeRF spatial, 2 Ref-NeRF density gradient, 3 proposal density gradient; `start_frag`: where the
 // chain's stream begins in the blob
 }  // namespace
-size_t mlp_train_layer_stride(int precision, int64_t M);
-size_t mlp_train_mask_stride(int precision, int64_t M);
-int bwd_launch_chain(int which, int precision, const void* blob, int start_frag, int64_t M, const void* act, void* dlt, float* rows, hipStream_t st) {
+int nk::bwd_launch_chain(int which, int precision, const void* blob, int start_frag, int64_t M, const void* act, void* dlt, float* rows, hipStream_t st) {
     const size_t fb = precision == NERF_AMD_BF16 ? 1024 : 2048;
     const char* stream = reinterpret_cast<const char*>(blob) + (size_t)start_frag * fb;
     const size_t ls = mlp_train_layer_stride(precision, M), ms = mlp_train_mask_stride(precision, M);
@@ -1453,10 +1447,6 @@ int bwd_launch_chain(int which, int precision, const void* blob, int start_frag,
 }
 #endif  // BWD_TU != 1 && != 3
 #if BWD_TU != 2 && BWD_TU != 3
-#if BWD_TU == 1
-}  // namespace
-int bwd_launch_chain(int which, int precision, const void* blob, int start_frag, int64_t M, const void* act, void* dlt, float* rows, hipStream_t st);
-#endif
 namespace {
 
 template <class P, bool F8 = false>
@@ -1502,10 +1492,7 @@ int launch_wgrad_f8(const WgradJobs& jobs, int n_jobs, int n_wg, int64_t n_sub, 
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ host-visible launchers (capi.hip)
-size_t mlp_train_layer_stride(int precision, int64_t M);
-size_t mlp_train_mask_stride(int precision, int64_t M);
-
-int bwd_launch_prop_chain(const void* packed_bwd, int precision, const float* g_density, int64_t M, const void* act_dump, void* delta_dump,
+int nk::bwd_launch_prop_chain(const void* packed_bwd, int precision, const float* g_density, int64_t M, const void* act_dump, void* delta_dump,
                           hipStream_t st) {
     const unsigned long long ls = mlp_train_layer_stride(precision, M), ms = mlp_train_mask_stride(precision, M);
     const Dump act{const_cast<char*>(reinterpret_cast<const char*>(act_dump)), ls, reinterpret_cast<const char*>(act_dump) + (size_t)PROP_DUMP_SLOTS * ls, ms},
@@ -1514,7 +1501,7 @@ int bwd_launch_prop_chain(const void* packed_bwd, int precision, const float* g_
     if (precision == NERF_AMD_BF16) return launch_prop_bwd<PB16>(packed_bwd, g_density, M, act, dlt, st);
     return launch_prop_bwd<PF32>(packed_bwd, g_density, M, act, dlt, st);
 }
-int bwd_launch_mip_chain(const void* packed_bwd, int precision, const float* g_rgbo, const float* rgbo, int64_t M, const void* act_dump,
+int nk::bwd_launch_mip_chain(const void* packed_bwd, int precision, const float* g_rgbo, const float* rgbo, int64_t M, const void* act_dump,
                          void* delta_dump, hipStream_t st) {
     const unsigned long long ls = mlp_train_layer_stride(precision, M), ms = mlp_train_mask_stride(precision, M);
     const Dump act{const_cast<char*>(reinterpret_cast<const char*>(act_dump)), ls, reinterpret_cast<const char*>(act_dump) + (size_t)MIP_DUMP_SLOTS * ls, ms},
@@ -1598,7 +1585,7 @@ int64_t bwd_n_sub(int precision, int64_t M) {
 }
 
 // workspace: per-product workgroup partials (+ G for the un-fold)
-size_t bwd_wgrad_workspace_bytes(int net, int precision, int64_t M) {
+size_t nk::bwd_wgrad_workspace_bytes(int net, int precision, int64_t M) {
     const int64_t n_sub = bwd_n_sub(precision, M);
     if (net == NERF_AMD_NET_PROPOSAL) {
         const size_t w0 = wgrad_workgroups(n_sub, 3, true), w1 = wgrad_workgroups(n_sub, 1, false);
@@ -1616,7 +1603,7 @@ size_t bwd_wgrad_workspace_bytes(int net, int precision, int64_t M) {
 }
 
 // ProposalNetwork: d_w / d_b = gradients of layers.{0,2,4,6,8} (addtional.py:67-71), written in the reference's (out, in) layout
-int bwd_prop_weight_grads(int precision, int64_t M, const void* act_dump, const void* delta_dump, float* const* d_w, float* const* d_b,
+int nk::bwd_prop_weight_grads(int precision, int64_t M, const void* act_dump, const void* delta_dump, float* const* d_w, float* const* d_b,
                           void* workspace, hipStream_t st) {
     const bool f8 = precision == NERF_AMD_BF16_F8;          // hidden slots of both dumps in scaled e4m3 (arithmetic: bf16)
     if (f8) precision = NERF_AMD_BF16;
@@ -1649,7 +1636,7 @@ int bwd_prop_weight_grads(int precision, int64_t M, const void* act_dump, const 
 }
 
 // MipNeRF: tensors in _linear_layers() order (0..3 lin_block1, 4..6 lin_block2, 7 bottle_neck.0, 8 opacity_head.0, 9, 10 rgb_layer.{0,2})
-int bwd_mip_weight_grads(int precision, int64_t M, const void* act_dump, const void* delta_dump, const float* const* w, const float* const* b,
+int nk::bwd_mip_weight_grads(int precision, int64_t M, const void* act_dump, const void* delta_dump, const float* const* w, const float* const* b,
                          float* const* d_w, float* const* d_b, void* workspace, hipStream_t st) {
     const bool f8 = precision == NERF_AMD_BF16_F8;          // hidden slots of both dumps in scaled e4m3 (arithmetic: bf16)
     if (f8) precision = NERF_AMD_BF16;
@@ -1710,7 +1697,7 @@ int bwd_mip_weight_grads(int precision, int64_t M, const void* act_dump, const v
 namespace {
 struct ChainCtx {                     // addressing of fragment dumps: slot l, K group kg
     int precision; int64_t M; size_t breg, ls, sub;
-    ChainCtx(int prec, int64_t m) : precision(prec), M(m), breg(prec == NERF_AMD_BF16 ? 1024 : 2048), ls(mlp_train_layer_stride(prec, m)), sub(16 * breg) {}
+    ChainCtx(int prec, int64_t m) : precision(prec), M(m), breg(prec == NERF_AMD_BF16 ? 1024 : 2048), ls(nk::mlp_train_layer_stride(prec, m)), sub(16 * breg) {}
     const char* at(const void* dump, int slot, int kg = 0) const { return reinterpret_cast<const char*>(dump) + (size_t)slot * ls + (size_t)kg * breg; }
     char* at(void* dump, int slot, int kg = 0) const { return reinterpret_cast<char*>(dump) + (size_t)slot * ls + (size_t)kg * breg; }
 };
@@ -1721,10 +1708,10 @@ int blocks_1d(int64_t work) { int64_t b = (work + 255) / 256; return (int)(b > 4
 // d density / d position, times scale[m] (RefNeRF.get_grad, ref_model.py:119-125; train.py:165-168,178) for the proposal network
 // (net 0: activation slots 0..3) and Ref-NeRF's spatial network (net 2: slots 0..7): a dgrad-only chain from the density row down to
 // the encoded position, then the encoding's derivative.  workspace: two delta buffers of one slot each + d_enc rows (M, 64) fp32.
-size_t bwd_density_grad_workspace_bytes(int precision, int64_t M) {
+size_t nk::bwd_density_grad_workspace_bytes(int precision, int64_t M) {
     return align256((size_t)M * 64 * 4) + 256;
 }
-int bwd_density_grad(int net, const void* blob, int precision, int64_t M, const void* act, const float* x, int x_stride, const float* scale, int scale_stride,
+int nk::bwd_density_grad(int net, const void* blob, int precision, int64_t M, const void* act, const float* x, int x_stride, const float* scale, int scale_stride,
                      float* out, void* workspace, hipStream_t st, int contract) {
     if (M == 0) return 0;
     const ChainCtx c(precision, M);
@@ -1739,7 +1726,7 @@ int bwd_density_grad(int net, const void* blob, int precision, int64_t M, const 
 
 // Ref-NeRF parameter backward (what autograd computes for ref_model.py:68-106 inside train.py:176-199).
 // workspace: delta dump (REF_DUMP_SLOTS slots) | d_allin rows (M,192) | wgrad partials
-size_t bwd_ref_workspace_bytes(int precision, int64_t M) {
+size_t nk::bwd_ref_workspace_bytes(int precision, int64_t M) {
     const int64_t n_sub = bwd_n_sub(precision, M);
     const size_t w7 = wgrad_workgroups(n_sub, 7, true), w2 = wgrad_workgroups(n_sub, 2, false), w1h = wgrad_workgroups(n_sub, 1, true),
                  w1 = wgrad_workgroups(n_sub, 1, false);
@@ -1752,7 +1739,7 @@ size_t bwd_ref_workspace_bytes(int precision, int64_t M) {
 }
 // w: the 20 tensors of nerf_amd_pack_weights(NET_REF) (only the ide_table, index 19, is read here).  d_w / d_b (20 each): 0..7 spatial,
 // 8 bottle_neck, 9 norm_col_tint_head (9 rows), 10 rho_tau_head (2 rows), 11..18 directional, 19 spec_rgb_head.0
-int bwd_ref_backward(const void* blob, int precision, int64_t M, const void* act, const float* aux, const float* dirs, int dir_stride,
+int nk::bwd_ref_backward(const void* blob, int precision, int64_t M, const void* act, const float* aux, const float* dirs, int dir_stride,
                      const float* g_out, int g_stride, const float* ide_table, float* const* d_w, float* const* d_b, void* workspace, int flags, hipStream_t st) {
     if (M == 0) return 0;
     using L = RefBwdLayout;
@@ -1835,7 +1822,7 @@ int bwd_ref_backward(const void* blob, int precision, int64_t M, const void* act
     return run_finalize(f, n, st);
 }
 
-int bwd_launch_adam(float* const* p, const float* const* g, float* const* m, float* const* v, const long long* n, int count, float* step, double lr,
+int nk::bwd_launch_adam(float* const* p, const float* const* g, float* const* m, float* const* v, const long long* n, int count, float* step, double lr,
                     const double* lr_dev, double beta1, double beta2, double eps, float grad_scale, hipStream_t st) {
     hipLaunchKernelGGL(adam_step_kernel, dim3(1), dim3(1), 0, st, step);
     for (int base = 0; base < count; base += ADAM_MAX) {

@@ -6,102 +6,9 @@
 #include "../../include/nerf_amd.h"
 #include "mlp_layout.h"
 
-// launchers defined in the kernel translation units
-int mlp_launch_proposal(const void*, int, const nerf_amd_samples&, float*, hipStream_t);
-int mlp_launch_proposal128(const void*, int, const nerf_amd_samples&, float*, hipStream_t);
-int mlp_launch_mip(const void*, int, const nerf_amd_samples&, float*, hipStream_t);
-int mlp_launch_mip128(const void*, int, const nerf_amd_samples&, float*, hipStream_t);
-int mlp_launch_mip_composite(const void*, int, const nerf_amd_samples&, float*, float*, float*, int, float, float, hipStream_t);
-int mlp_launch_ref(const void*, int, const nerf_amd_samples&, float*, float*, const float*, int, hipStream_t);
-size_t mlp_train_layer_stride(int, int64_t);
-size_t mlp_train_mask_stride(int, int64_t);
-int mlp_launch_proposal_train(const void*, int, const nerf_amd_samples&, float*, void*, hipStream_t);
-int mlp_launch_mip_train(const void*, int, const nerf_amd_samples&, float*, void*, hipStream_t);
-int sk_frag_to_rows(const void*, int, int64_t, int, int64_t, void*, hipStream_t);
-int sk_relu_mask(void*, const void*, int, int64_t, hipStream_t);
-int sk_merge_sorted(const float*, const float*, int64_t, int, int, float*, hipStream_t);
-int sk_merge_sorted_order(const float*, const float*, const int64_t*, int64_t, int, int, float*, int64_t*, int64_t*, hipStream_t);
-int sk_coarse_grad_select(const float*, const int64_t*, int64_t, int, int, int, float*, hipStream_t);
-int pack_mfma_stream(int, int, int, float*, hipStream_t);
-int sk_weighted_dot_loss(const float*, const float*, const float*, int64_t, int, float, float*, float*, hipStream_t);
-int sk_weighted_dot_loss_backward(const float*, const float*, const float*, const float*, int64_t, int, float, float*, float*, float*, hipStream_t);
-int sk_distortion_loss(const float*, const float*, int64_t, int, int, float, float*, float*, hipStream_t);
-int sk_distortion_loss_backward(const float*, const float*, int64_t, int, int, float, const float*, float*, float*, hipStream_t);
-int sk_interlevel_loss(const float*, const float*, const float*, const float*, int64_t, int, int, int, float, float*, float*, float*, hipStream_t);
-int sk_interlevel_loss_backward(const float*, const float*, const float*, const float*, int64_t, int, int, int, float, const float*, float*, hipStream_t);
-int sk_encode_rows(const float*, int, int64_t, int, int, int, void*, hipStream_t);
-int sk_frag_rows_mask_blocks();
-int sk_frag_rows_mask(const void*, int, int64_t, int, int64_t, void*, void*, float*, hipStream_t);
-int sk_relu_mask_bias(void*, const void*, int, int64_t, int, float*, hipStream_t);
-int pack_ref(int, const float* const*, const float* const*, void*, hipStream_t);
-int pack_proposal_bwd(int, const float* const*, void*, hipStream_t);
-int pack_mip_bwd(int, const float* const*, void*, hipStream_t);
-int pack_ref_bwd(int, const float* const*, void*, hipStream_t);
-int mlp_launch_ref_train(const void*, int, const nerf_amd_samples&, float*, float*, const float*, void*, float*, int, hipStream_t, unsigned long long, const unsigned long long*, float);
-size_t bwd_density_grad_workspace_bytes(int, int64_t);
-int bwd_density_grad(int, const void*, int, int64_t, const void*, const float*, int, const float*, int, float*, void*, hipStream_t, int);
-size_t bwd_ref_workspace_bytes(int, int64_t);
-int bwd_ref_backward(const void*, int, int64_t, const void*, const float*, const float*, int, const float*, int, const float*, float* const*,
-                     float* const*, void*, int, hipStream_t);
-int bwd_launch_prop_chain(const void*, int, const float*, int64_t, const void*, void*, hipStream_t);
-int bwd_launch_mip_chain(const void*, int, const float*, const float*, int64_t, const void*, void*, hipStream_t);
-size_t bwd_wgrad_workspace_bytes(int, int, int64_t);
-int bwd_prop_weight_grads(int, int64_t, const void*, const void*, float* const*, float* const*, void*, hipStream_t);
-int bwd_mip_weight_grads(int, int64_t, const void*, const void*, const float* const*, const float* const*, float* const*, float* const*, void*,
-                         hipStream_t);
-int bwd_launch_adam(float* const*, const float* const*, float* const*, float* const*, const long long*, int, float*, double, const double*, double,
-                    double, double, float, hipStream_t);
-int pack_proposal(int, const float* const*, const float* const*, void*, hipStream_t);
-int pack_proposal128(int, const float* const*, const float* const*, void*, hipStream_t);
-int pack_mip128(int, const float* const*, const float* const*, void*, hipStream_t);
-int pack_mip(int, const float* const*, const float* const*, void*, hipStream_t);
-int sk_positional_encoding(const float*, int64_t, int, float*, hipStream_t);
-int sk_ipe_feature(const float*, const float*, int64_t, int, int, float, const float*, float*, float*, float*, int, hipStream_t);
-int sk_dirs_norm(const float*, int64_t, float*, hipStream_t);
-int sk_dirs_norm_scratch(const float*, int64_t, float*, void*, hipStream_t);
-int sk_train_sampler(const float*, const int64_t*, int64_t, const float*, const float*, float, float, float, float, int64_t, int, uint64_t, const uint64_t*,
-                     float*, float*, float*, float*, hipStream_t);
-int sk_scene_sampler(const float*, const float*, int64_t, int, int, const int64_t*, int64_t, int, int, int, int, float, float, float, float, int64_t, int,
-                     uint64_t, const uint64_t*, float*, float*, float*, float*, int64_t*, hipStream_t);
-int sk_philox_uniforms(float*, int64_t, int, uint64_t, const uint64_t*, int64_t, int, hipStream_t);
-int sk_philox_normal(float*, int64_t, uint64_t, const uint64_t*, float, int64_t, hipStream_t);
-size_t gk_gemm_workspace_bytes(int64_t, int64_t, int64_t);
-int gk_gemm(int, int64_t, int64_t, int64_t, const float*, int64_t, int64_t, const float*, int64_t, int64_t, float*, int64_t, const float*, int, const float*, int64_t,
-            void*, hipStream_t);
-int gk_sigmoid_backward(const float*, int64_t, const float*, int64_t, int64_t, int, float*, int64_t, hipStream_t);
-int gr_dir_inputs(const float*, int64_t, const float*, int64_t, int64_t, int, const float*, float*, int64_t, float*, hipStream_t);
-int gr_dir_inputs_backward(const float*, int64_t, const float*, int64_t, int64_t, int, const float*, const float*, int64_t, const float*, int64_t, float*, int64_t,
-                           hipStream_t);
-int gr_combine(const float*, int64_t, const float*, int64_t, int64_t, int, float*, hipStream_t);
-int gr_combine_backward(const float*, int64_t, const float*, int64_t, const float*, int64_t, int64_t, int, float*, int64_t, float*, int64_t, hipStream_t);
-int gr_pe_backward(const float*, int64_t, const float*, int64_t, int64_t, int, int, float*, hipStream_t);
-int gr_add_rows(float*, int64_t, const float*, int64_t, int64_t, int, hipStream_t);
-int gr_contract(const float*, int64_t, int64_t, const float*, int64_t, float*, hipStream_t);
-int rg_rows_gemm(int64_t, int64_t, int64_t, const void*, int64_t, const void*, int64_t, int64_t, const float*, int, void*, int64_t, int, hipStream_t);
-int rg_rows_to_bf16(const float*, int64_t, int64_t, int64_t, int, int, void*, int64_t, hipStream_t);
-int sk_advance_seed(uint64_t*, hipStream_t);
-int sk_cone_parameters(const float*, int64_t, int, float, float*, float*, float*, hipStream_t);
-int sk_generate_rays(const float*, int, int, float, float, int64_t, int64_t, float*, hipStream_t);
-int sk_length2pts(const float*, const float*, int64_t, int, float*, hipStream_t);
-int sk_sigma_to_weights(const float*, const float*, const float*, int64_t, int, int, float*, hipStream_t);
-int sk_max_blur(const float*, int64_t, int, float, float*, hipStream_t);
-int sk_inverse_sample(const float*, const float*, const float*, int64_t, int, int, int, int, float*, int64_t*, int64_t*, hipStream_t);
-int sk_pixel_rays(const float*, float, float, const int64_t*, int64_t, float*, hipStream_t);
-int sk_stratified_points(const float*, const float*, const float*, float, int64_t, int, float*, float*, hipStream_t);
-int sk_resample(const float*, const float*, const float*, const float*, float, const float*, int, const float*, int64_t, int,
-                int, int, float, uint64_t, int64_t, float*, int64_t*, float*, float*, hipStream_t);
-int sk_composite(const float*, const float*, int, const float*, int, int64_t, int, int, int, float, float, float, const float*,
-                 const float*, float*, float*, float*, float*, hipStream_t);
-int sk_get_bounds(const float*, const int64_t*, int64_t, int, int, float*, hipStream_t);
-int sk_warp_depths(const float*, const float*, int64_t, int, int, float, float, float, float, float*, float*, hipStream_t);
-int sk_warped_stratified(const float*, const float*, int64_t, int, uint64_t, int64_t, float, float, float, float, float*, float*, float*, hipStream_t);
-size_t sk_warped_resample_lds_bytes(int, int);
-int sk_warped_resample(const float*, const float*, const float*, int, const float*, int64_t, int, int, int, float, float, float, float, float, uint64_t,
-                       int64_t, float*, float*, int64_t*, float*, hipStream_t);
-int sk_weights_backward(const float*, int, int, const float*, int, const float*, int, int64_t, int, int, int, float, const float*, const float*,
-                        const float*, const float*, int, float, float, float*, int, int, float*, hipStream_t);
-int sk_max_blur_backward(const float*, const float*, int64_t, int, float*, hipStream_t);
-int sk_get_bounds_backward(const int64_t*, const float*, int64_t, int, int, float*, hipStream_t);
+#include "launchers.h"
+
+using namespace nk;
 
 namespace {
 thread_local char g_err[512] = "";
@@ -139,6 +46,17 @@ int check_samples(const nerf_amd_samples* s, bool need_dir) {
     return NERF_AMD_OK;
 }
 bool bad_prec(int p) { return p != NERF_AMD_F32 && p != NERF_AMD_BF16; }
+// layout flags ride above the low byte of a `precision` argument (nerf_amd.h): split them off; true = unknown precision or a flag not in `allowed`
+bool split_precision(int& precision, int& lflags, int allowed) {
+    lflags = precision & ~0xff;
+    precision &= 0xff;
+    return bad_prec(precision) || (lflags & ~allowed);
+}
+// A shape is accepted only if the launch it leads to (launchers.h: sk_*_lds_bytes) fits 64 KiB, the dynamic LDS this project ASSUMES a kernel gets
+// without an opt-in (host_common.h).  The assumption is unmeasured: the runtime may well launch more.
+int check_lds(size_t bytes, const char* what) {
+    return bytes > 64 * 1024 ? fail(NERF_AMD_EINVAL, "%s too large: the per-ray rows of four rays must fit 64 KiB of LDS", what) : NERF_AMD_OK;
+}
 int check_distortion(int64_t N, int Sn, int mode) {
     if (N < 0) return fail(NERF_AMD_EINVAL, "negative ray count");
     if (mode != 0 && mode != 1) return fail(NERF_AMD_EINVAL, "unknown mode (0: Regularizer, 1: Mip-NeRF 360 L_dist)");
@@ -165,8 +83,7 @@ int check_spacing(int spacing, float near, float far, float* gn, float* gf) {
 }
 int check_warped_resample_shape(int C, int K) {
     if (C < 3 || C > 256 || K < 1 || K > 1024) return fail(NERF_AMD_EINVAL, "need 3 <= C <= 256 and 1 <= K <= 1024");
-    if (sk_warped_resample_lds_bytes(C, K) > 65536) return fail(NERF_AMD_EINVAL, "C and K too large: the per-ray rows of four rays must fit 64 KiB of LDS");
-    return NERF_AMD_OK;
+    return check_lds(sk_warped_resample_lds_bytes(C, K), "C and K");
 }
 }  // namespace
 
@@ -222,9 +139,8 @@ int nerf_amd_pack_weights(int net, int precision, const float* const* weights, c
 }
 
 int nerf_amd_proposal_forward(const void* packed, int precision, const nerf_amd_samples* src, float* density, void* stream) {
-    const int lflags = precision & ~0xff;
-    precision &= 0xff;
-    if (bad_prec(precision) || (lflags & ~NERF_AMD_PROP_W128)) return fail(NERF_AMD_EINVAL, "unknown precision");
+    int lflags;
+    if (split_precision(precision, lflags, NERF_AMD_PROP_W128)) return fail(NERF_AMD_EINVAL, "unknown precision");
     if (int c = check_samples(src, false)) return c;
     if (src->M == 0) return NERF_AMD_OK;
     if (!packed || !density) return fail(NERF_AMD_EINVAL, "NULL argument");
@@ -232,9 +148,8 @@ int nerf_amd_proposal_forward(const void* packed, int precision, const nerf_amd_
 }
 
 int nerf_amd_mip_forward(const void* packed, int precision, const nerf_amd_samples* src, float* rgbo, void* stream) {
-    const int lflags = precision & ~0xff;
-    precision &= 0xff;
-    if (bad_prec(precision) || (lflags & ~NERF_AMD_FINE_W128)) return fail(NERF_AMD_EINVAL, "unknown precision");
+    int lflags;
+    if (split_precision(precision, lflags, NERF_AMD_FINE_W128)) return fail(NERF_AMD_EINVAL, "unknown precision");
     if (int c = check_samples(src, true)) return c;
     if (src->M == 0) return NERF_AMD_OK;
     if (!packed || !rgbo) return fail(NERF_AMD_EINVAL, "NULL argument");
@@ -244,10 +159,9 @@ int nerf_amd_mip_forward(const void* packed, int precision, const nerf_amd_sampl
 
 int nerf_amd_mip_forward_composite(const void* packed, int precision, const nerf_amd_samples* src, int white_bkg, float near,
                                    float far, float* rgb, float* depth, float* weights, void* stream) {
-    const int lflags = precision & ~0xff;                   // layout flags ride in `precision` (nerf_amd.h): strip them before bad_prec
-    precision &= 0xff;
-    if (bad_prec(precision) || (lflags & ~NERF_AMD_FINE_W128)) return fail(NERF_AMD_EINVAL, "unknown precision");
-    if (lflags & NERF_AMD_FINE_W128)                        // (a NET_MIP_128 blob walked by the 256-wide kernel = wrong image + reads past the blob)
+    int lflags;
+    if (split_precision(precision, lflags, NERF_AMD_FINE_W128)) return fail(NERF_AMD_EINVAL, "unknown precision");
+    if (lflags & NERF_AMD_FINE_W128)
         return fail(NERF_AMD_EUNSUPPORTED, "the 128-wide fine layout has no fused-compositing kernel: use nerf_amd_mip_forward + nerf_amd_composite");
     if (int c = check_samples(src, true)) return c;
     if (src->mode != 1 || !src->z) return fail(NERF_AMD_EUNSUPPORTED, "fused compositing needs mode 1 (rays + z)");
@@ -260,20 +174,20 @@ int nerf_amd_mip_forward_composite(const void* packed, int precision, const nerf
 }
 
 static bool bad_ref_flags(int f) { return (f & ~NERF_AMD_REF_SRGB) != 0; }
-int nerf_amd_ref_forward(const void* packed, int precision, const nerf_amd_samples* src, int ref_flags, float* rgbo, float* normal, void* stream) {
+static int ref_forward_any(const void* packed, int precision, const nerf_amd_samples* src, int ref_flags, const float* bn_noise, bool train, float* rgbo,
+                           float* normal, void* stream, const char* name) {
     if (bad_prec(precision) || bad_ref_flags(ref_flags)) return fail(NERF_AMD_EINVAL, "unknown precision or ref_flags");
     if (int c = check_samples(src, true)) return c;
     if (src->M == 0) return NERF_AMD_OK;
-    if (!packed || !rgbo) return fail(NERF_AMD_EINVAL, "NULL argument");
-    return hip_status(mlp_launch_ref(packed, precision, *src, rgbo, normal, nullptr, ref_flags, S(stream)), "nerf_amd_ref_forward");
+    if (!packed || !rgbo || (train && !bn_noise)) return fail(NERF_AMD_EINVAL, "NULL argument");
+    return hip_status(mlp_launch_ref(packed, precision, *src, rgbo, normal, bn_noise, ref_flags, S(stream)), name);
+}
+int nerf_amd_ref_forward(const void* packed, int precision, const nerf_amd_samples* src, int ref_flags, float* rgbo, float* normal, void* stream) {
+    return ref_forward_any(packed, precision, src, ref_flags, nullptr, false, rgbo, normal, stream, "nerf_amd_ref_forward");
 }
 int nerf_amd_ref_forward_train(const void* packed, int precision, const nerf_amd_samples* src, int ref_flags, const float* bn_noise, float* rgbo,
                                float* normal, void* stream) {
-    if (bad_prec(precision) || bad_ref_flags(ref_flags)) return fail(NERF_AMD_EINVAL, "unknown precision or ref_flags");
-    if (int c = check_samples(src, true)) return c;
-    if (src->M == 0) return NERF_AMD_OK;
-    if (!packed || !rgbo || !bn_noise) return fail(NERF_AMD_EINVAL, "NULL argument");
-    return hip_status(mlp_launch_ref(packed, precision, *src, rgbo, normal, bn_noise, ref_flags, S(stream)), "nerf_amd_ref_forward_train");
+    return ref_forward_any(packed, precision, src, ref_flags, bn_noise, true, rgbo, normal, stream, "nerf_amd_ref_forward_train");
 }
 
 int nerf_amd_positional_encoding(const float* x, int64_t M, int L, float* out, void* stream) {
@@ -282,19 +196,20 @@ int nerf_amd_positional_encoding(const float* x, int64_t M, int L, float* out, v
     return hip_status(sk_positional_encoding(x, M, L, out, S(stream)), "nerf_amd_positional_encoding");
 }
 
-int nerf_amd_ipe_feature(const float* z, const float* rays, int64_t N, int Sn, int L, float r, const float* dir_norm, float* feat, float* mu,
-                         float* mu_t, void* stream) {
+static int ipe_feature_any(const float* z, const float* rays, int64_t N, int Sn, int L, float r, const float* dir_norm, float* feat, float* mu, float* mu_t,
+                           int contract, void* stream, const char* name) {
     if (N < 0 || Sn < 0 || L < 1 || L > 15) return fail(NERF_AMD_EINVAL, "bad size or L (1..15)");
     if (N * Sn && (!z || !rays || !dir_norm || !feat)) return fail(NERF_AMD_EINVAL, "NULL argument");
     const float r2 = (float)((double)r * (double)r);        // Python's `r ** 2` is a double, rounded when it meets the fp32 tensor
-    return hip_status(sk_ipe_feature(z, rays, N, Sn, L, r2, dir_norm, feat, mu, mu_t, 0, S(stream)), "nerf_amd_ipe_feature");
+    return hip_status(sk_ipe_feature(z, rays, N, Sn, L, r2, dir_norm, feat, mu, mu_t, contract, S(stream)), name);
+}
+int nerf_amd_ipe_feature(const float* z, const float* rays, int64_t N, int Sn, int L, float r, const float* dir_norm, float* feat, float* mu,
+                         float* mu_t, void* stream) {
+    return ipe_feature_any(z, rays, N, Sn, L, r, dir_norm, feat, mu, mu_t, 0, stream, "nerf_amd_ipe_feature");
 }
 int nerf_amd_ipe_feature_contracted(const float* z, const float* rays, int64_t N, int Sn, int L, float r, const float* dir_norm, float* feat, float* mu,
                                     float* mu_t, void* stream) {
-    if (N < 0 || Sn < 0 || L < 1 || L > 15) return fail(NERF_AMD_EINVAL, "bad size or L (1..15)");
-    if (N * Sn && (!z || !rays || !dir_norm || !feat)) return fail(NERF_AMD_EINVAL, "NULL argument");
-    const float r2 = (float)((double)r * (double)r);
-    return hip_status(sk_ipe_feature(z, rays, N, Sn, L, r2, dir_norm, feat, mu, mu_t, 1, S(stream)), "nerf_amd_ipe_feature_contracted");
+    return ipe_feature_any(z, rays, N, Sn, L, r, dir_norm, feat, mu, mu_t, 1, stream, "nerf_amd_ipe_feature_contracted");
 }
 int nerf_amd_cone_parameters(const float* z, int64_t N, int Sn, float r, float* mu_t, float* var_t, float* var_r, void* stream) {
     if (N < 0 || Sn < 0) return fail(NERF_AMD_EINVAL, "negative size");
@@ -335,6 +250,7 @@ int nerf_amd_max_blur(const float* w, int64_t N, int Sn, float alpha, float* out
 int nerf_amd_inverse_sample(const float* w, const float* z, const float* u, int64_t N, int C, int K, int sort, float* z_out,
                             int64_t* below, void* stream) {
     if (N < 0 || C < 3 || C > 256 || K < 1 || K > 1024) return fail(NERF_AMD_EINVAL, "need 3 <= C <= 256 and 1 <= K <= 1024");
+    if (int e = check_lds(sk_inverse_sample_lds_bytes(C, K), "C and K")) return e;
     if (N && (!w || !z || !u || !z_out)) return fail(NERF_AMD_EINVAL, "NULL argument");
     return hip_status(sk_inverse_sample(w, z, u, N, C, K, sort, 0, z_out, below, nullptr, S(stream)), "nerf_amd_inverse_sample");
 }
@@ -342,6 +258,7 @@ int nerf_amd_inverse_sample(const float* w, const float* z, const float* u, int6
 int nerf_amd_sample_pdf(const float* bins, const float* weights, const float* u, int64_t N, int B, int K, float* samples,
                         int64_t* below, int64_t* above, void* stream) {
     if (N < 0 || B < 2 || B > 256 || K < 1 || K > 1024) return fail(NERF_AMD_EINVAL, "need 2 <= B <= 256 and 1 <= K <= 1024");
+    if (int e = check_lds(sk_inverse_sample_lds_bytes(B, K), "B and K")) return e;
     if (N && (!bins || !weights || !u || !samples)) return fail(NERF_AMD_EINVAL, "NULL argument");
     return hip_status(sk_inverse_sample(weights, bins, u, N, B, K, 0, 1, samples, below, above, S(stream)), "nerf_amd_sample_pdf");
 }
@@ -351,23 +268,26 @@ int nerf_amd_pixel_rays(const float* pose_host, float fx, float fy, const int64_
     return hip_status(sk_pixel_rays(pose_host, fx, fy, coords, N, rays, S(stream)), "nerf_amd_pixel_rays");
 }
 
+// the pose and the seed come from the host (pose_host, rng_seed) or both from the device (pose_dev, seed_dev)
+static int train_sampler_any(const float* rgbs, const int64_t* coords, int64_t n_pixels, const float* pose_host, const float* pose_dev, float fx, float fy,
+                             float near, float far, int64_t N, int C, uint64_t rng_seed, const uint64_t* seed_dev, float* pts, float* lengths, float* rgb,
+                             float* rays, void* stream, const char* name) {
+    if (N < 0 || C < 0 || n_pixels < 1) return fail(NERF_AMD_EINVAL, "bad size");
+    if (!(pose_host || (pose_dev && seed_dev)) || (N && (!rgbs || !coords || !rgb || !rays))) return fail(NERF_AMD_EINVAL, "NULL argument");
+    if ((pts == nullptr) != (lengths == nullptr) || (pts && C < 1)) return fail(NERF_AMD_EINVAL, "pts and lengths go together (C >= 1)");
+    return hip_status(sk_train_sampler(rgbs, coords, n_pixels, pose_host, pose_dev, fx, fy, near, far, N, C, rng_seed, seed_dev, pts, lengths, rgb, rays, S(stream)), name);
+}
 int nerf_amd_sample_training_rays(const float* rgbs, const int64_t* coords, int64_t n_pixels, const float* pose_host, float fx, float fy,
                                   float near, float far, int64_t N, int C, uint64_t rng_seed, float* pts, float* lengths, float* rgb, float* rays,
                                   void* stream) {
-    if (N < 0 || C < 0 || n_pixels < 1) return fail(NERF_AMD_EINVAL, "bad size");
-    if (!pose_host || (N && (!rgbs || !coords || !rgb || !rays))) return fail(NERF_AMD_EINVAL, "NULL argument");
-    if ((pts == nullptr) != (lengths == nullptr) || (pts && C < 1)) return fail(NERF_AMD_EINVAL, "pts and lengths go together (C >= 1)");
-    return hip_status(sk_train_sampler(rgbs, coords, n_pixels, pose_host, nullptr, fx, fy, near, far, N, C, rng_seed, nullptr, pts, lengths, rgb, rays, S(stream)),
-                      "nerf_amd_sample_training_rays");
+    return train_sampler_any(rgbs, coords, n_pixels, pose_host, nullptr, fx, fy, near, far, N, C, rng_seed, nullptr, pts, lengths, rgb, rays, stream,
+                             "nerf_amd_sample_training_rays");
 }
 int nerf_amd_sample_training_rays_dev(const float* rgbs, const int64_t* coords, int64_t n_pixels, const float* pose_dev, float fx, float fy,
                                       float near, float far, int64_t N, int C, const uint64_t* seed_dev, float* pts, float* lengths, float* rgb,
                                       float* rays, void* stream) {
-    if (N < 0 || C < 0 || n_pixels < 1) return fail(NERF_AMD_EINVAL, "bad size");
-    if (!pose_dev || !seed_dev || (N && (!rgbs || !coords || !rgb || !rays))) return fail(NERF_AMD_EINVAL, "NULL argument");
-    if ((pts == nullptr) != (lengths == nullptr) || (pts && C < 1)) return fail(NERF_AMD_EINVAL, "pts and lengths go together (C >= 1)");
-    return hip_status(sk_train_sampler(rgbs, coords, n_pixels, nullptr, pose_dev, fx, fy, near, far, N, C, 0, seed_dev, pts, lengths, rgb, rays, S(stream)),
-                      "nerf_amd_sample_training_rays_dev");
+    return train_sampler_any(rgbs, coords, n_pixels, nullptr, pose_dev, fx, fy, near, far, N, C, 0, seed_dev, pts, lengths, rgb, rays, stream,
+                             "nerf_amd_sample_training_rays_dev");
 }
 int nerf_amd_sample_scene_rays(const float* images, const float* poses, int64_t V, int H, int W, const int64_t* view_ids, int64_t K, int x0, int x1,
                                int y0, int y1, float fx, float fy, float near, float far, int64_t N, int C, uint64_t rng_seed,
@@ -418,6 +338,7 @@ int nerf_amd_resample(const float* density, const float* z, const float* z_base,
                       float blur_alpha, uint64_t rng_seed, int64_t rng_ray_offset, float* z_fine, int64_t* below, float* w_prop,
                       float* z_coarse, void* stream) {
     if (N < 0 || C < 3 || C > 256 || K < 1 || K > 1024) return fail(NERF_AMD_EINVAL, "need 3 <= C <= 256 and 1 <= K <= 1024");
+    if (int e = check_lds(sk_resample_lds_bytes(C, K), "C and K")) return e;   // (5 C + 2 K <= 2816: K <= 768 at C = 256)
     if (N && (!density || !dirs || !z_fine)) return fail(NERF_AMD_EINVAL, "NULL argument");
     if (N && !z && !z_base) return fail(NERF_AMD_EINVAL, "need z, or z_base (with u_strat, or without: in-kernel uniforms)");
     return hip_status(sk_resample(density, z, z_base, u_strat, z_jitter, dirs, dirs_stride, u_inv, N, C, K, softplus_density,
@@ -436,19 +357,20 @@ int nerf_amd_composite(const float* rgbo, const float* z, int z_stride, const fl
 
 int nerf_amd_get_bounds(const float* w_prop, const int64_t* below, int64_t N, int C, int K, float* bounds, void* stream) {
     if (N < 0 || C < 1 || C > 4096 || K < 2) return fail(NERF_AMD_EINVAL, "bad size");
+    if (int e = check_lds(sk_get_bounds_lds_bytes(C), "C")) return e;           // (C + 1 floats per ray: C <= 4095)
     if (N && (!w_prop || !below || !bounds)) return fail(NERF_AMD_EINVAL, "NULL argument");
     return hip_status(sk_get_bounds(w_prop, below, N, C, K, bounds, S(stream)), "nerf_amd_get_bounds");
 }
 
 int nerf_amd_merge_depths(const float* z_fine, const float* z_coarse, int64_t N, int K, int C, float* z_out, void* stream) {
-    if (N < 0 || K < 1 || C < 1 || K + C > 2048) return fail(NERF_AMD_EINVAL, "bad size (K + C <= 2048: four rays of depths and their sort scratch per workgroup live in 64 KiB of LDS)");
+    if (N < 0 || K < 1 || C < 1 || sk_merge_sorted_lds_bytes(K, C, 0) > 64 * 1024) return fail(NERF_AMD_EINVAL, "bad size (K + C <= 2048: four rays of depths and their sort scratch per workgroup live in 64 KiB of LDS)");
     if (N && (!z_fine || !z_coarse || !z_out)) return fail(NERF_AMD_EINVAL, "NULL argument");
     return hip_status(sk_merge_sorted(z_fine, z_coarse, N, K, C, z_out, S(stream)), "nerf_amd_merge_depths");
 }
 
 int nerf_amd_merge_depths_order(const float* z_fine, const float* z_coarse, const int64_t* f_inds, int64_t N, int K, int C, float* z_out, int64_t* order,
                                 int64_t* all_inds, void* stream) {
-    if (N < 0 || K < 1 || C < 1 || K + C > 1024) return fail(NERF_AMD_EINVAL, "bad size (K + C <= 1024: four rays of depths, indices and their sort scratch per workgroup live in 64 KiB of LDS)");
+    if (N < 0 || K < 1 || C < 1 || sk_merge_sorted_lds_bytes(K, C, 1) > 64 * 1024) return fail(NERF_AMD_EINVAL, "bad size (K + C <= 1024: four rays of depths, indices and their sort scratch per workgroup live in 64 KiB of LDS)");
     if (N && (!z_fine || !z_coarse || !z_out || !order)) return fail(NERF_AMD_EINVAL, "NULL argument");
     if (N && all_inds && !f_inds) return fail(NERF_AMD_EINVAL, "all_inds needs f_inds");
     return hip_status(sk_merge_sorted_order(z_fine, z_coarse, f_inds, N, K, C, z_out, order, all_inds, S(stream)), "nerf_amd_merge_depths_order");
@@ -730,86 +652,117 @@ int nerf_amd_max_blur_backward(const float* weights, const float* d_out, int64_t
     return hip_status(sk_max_blur_backward(weights, d_out, N, Sn, d_weights, S(stream)), "nerf_amd_max_blur_backward");
 }
 int nerf_amd_get_bounds_backward(const int64_t* below, const float* d_bounds, int64_t N, int C, int K, float* d_w_prop, void* stream) {
-    if (N < 0 || C < 1 || C > 4096 || K < 2 || K > 2048) return fail(NERF_AMD_EINVAL, "bad size (C <= 4096, 2 <= K <= 2048)");
+    if (N < 0 || C < 1 || C > 4096 || K < 2 || sk_get_bounds_backward_lds_bytes(K) > 64 * 1024) return fail(NERF_AMD_EINVAL, "bad size (C <= 4096, 2 <= K <= 2048)");
     if (N && (!below || !d_bounds || !d_w_prop)) return fail(NERF_AMD_EINVAL, "NULL argument");
     return hip_status(sk_get_bounds_backward(below, d_bounds, N, C, K, d_w_prop, S(stream)), "nerf_amd_get_bounds_backward");
 }
 
-// workspace: density (N,64) | z_fine (N, n_fine+1) | rgbo (N, n_fine, 4) | rays (N, 6)
-size_t nerf_amd_render_workspace_bytes(int64_t N, int n_fine) {
-    if (N < 0 || n_fine < 1) return 0;
-    const size_t a = ((size_t)N * 64 * 4 + 255) & ~(size_t)255;
-    const size_t b = ((size_t)N * (n_fine + 1) * 4 + 255) & ~(size_t)255;
-    const size_t c = ((size_t)N * n_fine * 16 + 255) & ~(size_t)255;
-    const size_t d = ((size_t)N * 24 + 255) & ~(size_t)255;
-    return a + b + c + d + 512;                             // + alignment slack + one scalar slot (direction norm of the IPE mode)
-}
+// ------------------------------------------------------------------------------------------------ whole-ray rendering
+namespace {
+constexpr int RENDER_C = 64;                                // procedures.py:22 RENDER_COARSE_PNUM
+// The workspace of the three render entry points, described ONCE: the constructor walks the parts in order, each rounded up to 256 bytes.
+// Walked from NULL it gives the size (nerf_amd_render*_workspace_bytes), from the caller's pointer the parts.
+//   plain:   density (N,64) | z_fine (N, n_fine+1) | rgbo (N, n_fine, 4) | rays (N, 6) | one scalar slot (direction norm of the IPE mode)
+//   warped:  density | s_c (N,64) | z_c (N,64) | z_fine | rgbo | raw depth (N) | rays | the scalar slot
+//   ref:     density | z_fine | z_coarse (N,64) | z_all (N, n_fine+64) | rgbo (N, n_fine+64, 4) | normals (N, n_fine+64, 3) | rays (unrounded)
+enum WsKind { WS_PLAIN, WS_WARPED, WS_REF };
+struct RenderWs {
+    float *density, *s_c = nullptr, *z_c = nullptr, *z_fine, *z_coarse = nullptr, *z_all = nullptr, *rgbo, *normals = nullptr, *depth_raw = nullptr, *rays, *dir_norm;
+    size_t bytes;
+    RenderWs(WsKind kind, void* base, int64_t N, int n_fine) {
+        const uintptr_t start = (reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255;
+        uintptr_t p = start;
+        auto take = [&p](size_t part) { float* r = reinterpret_cast<float*>(p); p += (part + 255) & ~(size_t)255; return r; };
+        const size_t n = (size_t)N, S = (size_t)n_fine + (kind == WS_REF ? RENDER_C : 0);    // samples per ray of the fine pass
+        density = take(n * RENDER_C * 4);
+        if (kind == WS_WARPED) { s_c = take(n * RENDER_C * 4); z_c = take(n * RENDER_C * 4); }
+        z_fine = take(n * (n_fine + 1) * 4);
+        if (kind == WS_REF) { z_coarse = take(n * RENDER_C * 4); z_all = take(n * S * 4); }
+        rgbo = take(n * S * 16);
+        if (kind == WS_REF) normals = take(n * S * 12);
+        if (kind == WS_WARPED) depth_raw = take(n * 4);
+        rays = kind == WS_REF ? reinterpret_cast<float*>(p) : take(n * 24);   // ref: the ray table is the unrounded tail
+        dir_norm = reinterpret_cast<float*>(p);             // plain, warped: the scalar slot behind the ray table
+        bytes = (size_t)(p - start) + (kind == WS_REF ? n * 24 + 256 : 512);   // + alignment slack (+ the scalar slot)
+    }
+};
+size_t render_ws_bytes(WsKind kind, int64_t N, int n_fine) { return (N < 0 || n_fine < 1) ? 0 : RenderWs(kind, nullptr, N, n_fine).bytes; }
 
-int nerf_amd_render_rays(const void* packed_prop, const void* packed_mip, int precision, const float* rays,
-                         const nerf_amd_samples* camera, int64_t ray_offset, const float* z_base, const float* u_strat,
-                         const float* u_inv, int64_t N, int n_fine, float near, float far, int white_bkg, float* rgb,
-                         float* depth, float* weights, void* workspace, void* stream) {
-    const int lflags = precision & ~0xff;
-    precision &= 0xff;
-    if (bad_prec(precision) || (lflags & ~(NERF_AMD_PROP_W128 | NERF_AMD_FINE_W128))) return fail(NERF_AMD_EINVAL, "unknown precision");
-    if ((lflags & NERF_AMD_FINE_W128) && camera && camera->ipe) return fail(NERF_AMD_EINVAL, "the 128-wide fine layout has no integrated-PE kernel: pack the network 256-wide");
-    if (N < 0 || n_fine < 1 || n_fine > 1023) return fail(NERF_AMD_EINVAL, "bad N or n_fine");
-    if (N == 0) return NERF_AMD_OK;
-    if (!packed_prop || !packed_mip || !z_base || !rgb || !workspace) return fail(NERF_AMD_EINVAL, "NULL argument");
+// ---- what the render entry points check and do alike ----
+int check_render_inputs(bool have_all, const float* rays, const nerf_amd_samples* camera, const float* u_strat, const float* u_inv) {
+    if (!have_all) return fail(NERF_AMD_EINVAL, "NULL argument");   // (have_all: none of the entry point's own required pointers is NULL)
     if ((u_strat == nullptr) != (u_inv == nullptr)) return fail(NERF_AMD_EINVAL, "u_strat and u_inv are both given or both NULL (in-kernel uniforms)");
     if (!u_strat && !camera) return fail(NERF_AMD_EINVAL, "in-kernel uniforms need the descriptor (rng_seed, rng_ray_offset)");
     if (!rays && !camera) return fail(NERF_AMD_EINVAL, "need rays or camera");
-    const uint64_t seed = camera ? camera->rng_seed : 0;
-    const int64_t ray0 = camera ? camera->rng_ray_offset : 0;
-    constexpr int C = 64;                                   // procedures.py:22 RENDER_COARSE_PNUM
-    char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    float* density = reinterpret_cast<float*>(ws);
-    ws += ((size_t)N * C * 4 + 255) & ~(size_t)255;
-    float* z_fine = reinterpret_cast<float*>(ws);
-    ws += ((size_t)N * (n_fine + 1) * 4 + 255) & ~(size_t)255;
-    float* rgbo = reinterpret_cast<float*>(ws);
-    ws += ((size_t)N * n_fine * 16 + 255) & ~(size_t)255;
-    hipStream_t st = S(stream);
-    if (!rays) {                                            // row 1: procedures.py:43-51,64
-        if (camera->H <= 0 || camera->W <= 0 || ray_offset < 0 || ray_offset + N > (int64_t)camera->H * camera->W)
-            return fail(NERF_AMD_EINVAL, "ray range outside the camera image");
-        float* gen = reinterpret_cast<float*>(ws);
-        if (int e = sk_generate_rays(camera->pose, camera->H, camera->W, camera->fx, camera->fy, ray_offset, N, gen, st))
-            return hip_status(e, "ray generation");
-        rays = gen;
-    }
-    ws += ((size_t)N * 24 + 255) & ~(size_t)255;
-    float* dir_norm = reinterpret_cast<float*>(ws);
-    const bool ipe = camera && camera->ipe;
-    if (ipe) {                                              // row 12 inside the fine pass: the direction norm of this ray batch
-        if (!(camera->ipe_radius > 0.0f)) return fail(NERF_AMD_EINVAL, "integrated PE needs a positive ipe_radius");
-        // (the density buffer is scratch until the proposal pass below writes it: room for the 256 fp64 workgroup partials when N >= 8)
-        // a caller that renders a SHARD of a ray list hands over the norm of the whole list (camera->ipe_dir_norm): the norm of
-        // mip_methods.py:31 is over all rays of the reference's call, not over the rays this launch happens to hold
-        if (camera->ipe_dir_norm) dir_norm = const_cast<float*>(camera->ipe_dir_norm);
-        else if (int e = (N >= 8) ? sk_dirs_norm_scratch(rays, N, dir_norm, density, st) : sk_dirs_norm(rays, N, dir_norm, st))
-            return hip_status(e, "direction norm");
-    }
+    return NERF_AMD_OK;
+}
+// row 1 (procedures.py:43-51,64): without a ray table, the camera's rays ray_offset .. ray_offset + N - 1 are generated into the workspace
+int provide_rays(const float*& rays, const nerf_amd_samples* camera, int64_t ray_offset, int64_t N, float* gen, hipStream_t st) {
+    if (rays) return NERF_AMD_OK;
+    if (camera->H <= 0 || camera->W <= 0 || ray_offset < 0 || ray_offset + N > (int64_t)camera->H * camera->W) return fail(NERF_AMD_EINVAL, "ray range outside the camera image");
+    if (int e = sk_generate_rays(camera->pose, camera->H, camera->W, camera->fx, camera->fy, ray_offset, N, gen, st)) return hip_status(e, "ray generation");
+    rays = gen;
+    return NERF_AMD_OK;
+}
+// row 12 inside the fine pass (IPE mode; else *dir_norm = NULL): the direction norm of this ray batch, into `slot` (`scratch`, the density
+// buffer, is free until the proposal pass writes it: room for the 256 fp64 workgroup partials when N >= 8).  A caller that renders a SHARD
+// of a ray list hands over the norm of the whole list (camera->ipe_dir_norm): mip_methods.py:31 norms all rays of the reference's call.
+int provide_dir_norm(const nerf_amd_samples* camera, const float* rays, int64_t N, float* slot, void* scratch, hipStream_t st, const float** dir_norm) {
+    *dir_norm = nullptr;
+    if (!camera || !camera->ipe) return NERF_AMD_OK;
+    if (!(camera->ipe_radius > 0.0f)) return fail(NERF_AMD_EINVAL, "integrated PE needs a positive ipe_radius");
+    *dir_norm = camera->ipe_dir_norm ? camera->ipe_dir_norm : slot;
+    if (camera->ipe_dir_norm) return NERF_AMD_OK;
+    return hip_status((N >= 8) ? sk_dirs_norm_scratch(rays, N, slot, scratch, st) : sk_dirs_norm(rays, N, slot, st), "direction norm");
+}
+// S samples per ray at the depths z (row stride z_stride); the descriptor may accompany explicit rays just to carry `contract`
+nerf_amd_samples ray_samples(const float* rays, int64_t N, int S, const float* z, int z_stride, const nerf_amd_samples* camera) {
+    nerf_amd_samples s{};
+    s.mode = 1; s.rays = rays; s.S = S; s.M = N * S; s.z = z; s.z_stride = z_stride; s.contract = camera ? camera->contract : 0;
+    return s;
+}
+// rows 2-7 under linear spacing: stratified z fused into the proposal MLP, then weights -> max-blur(0.01) -> inverse sampling of n_fine + 1
+// sorted depths (procedures.py:59,68-70); ws.z_coarse (Ref-NeRF) also receives the stratified depths the proposal pass used
+int coarse_pass(int lflags, const void* packed_prop, int precision, const float* rays, const nerf_amd_samples* camera, const float* z_base, const float* u_strat,
+                const float* u_inv, int64_t N, int n_fine, float near, float far, const RenderWs& ws, hipStream_t st) {
     const float jitter = (far - near) / (float)n_fine;      // procedures.py:59
+    nerf_amd_samples sc = ray_samples(rays, N, RENDER_C, nullptr, RENDER_C, camera);
+    sc.z_base = z_base; sc.u = u_strat; sc.z_jitter = jitter;
+    sc.rng_seed = camera ? camera->rng_seed : 0; sc.rng_ray_offset = camera ? camera->rng_ray_offset : 0;   // (read only when u_strat == NULL)
+    if (int e = launch_proposal_any(lflags, packed_prop, precision, sc, ws.density, st)) return hip_status(e, "proposal MLP");
+    return hip_status(sk_resample(ws.density, nullptr, z_base, u_strat, jitter, rays + 3, 6, u_inv, N, RENDER_C, n_fine + 1, 0, 0.01f, sc.rng_seed, sc.rng_ray_offset,
+                                  ws.z_fine, nullptr, nullptr, ws.z_coarse, st), "resample");
+}
+// rows 8-9: drop the last depth, length2pts fused into the fine MLP (`dir_norm`: integrated PE, frustum s = [z_fine[s], z_fine[s+1]])
+int fine_pass(int lflags, const void* packed_mip, int precision, const float* rays, const nerf_amd_samples* camera, int64_t N, int n_fine, const float* dir_norm,
+              const RenderWs& ws, hipStream_t st) {
+    nerf_amd_samples sf = ray_samples(rays, N, n_fine, ws.z_fine, n_fine + 1, camera);
+    if (dir_norm) { sf.ipe = 1; sf.ipe_radius = camera->ipe_radius; sf.ipe_dir_norm = dir_norm; }
+    return hip_status(launch_mip_any(lflags, packed_mip, precision, sf, ws.rgbo, st), "fine MLP");
+}
+}  // namespace
 
-    nerf_amd_samples sc{};                                  // rows 2-4: stratified z fused into the proposal MLP
-    sc.mode = 1; sc.rays = rays; sc.S = C; sc.M = N * C; sc.z = nullptr; sc.z_base = z_base; sc.u = u_strat;
-    sc.z_jitter = jitter; sc.z_stride = C;
-    sc.contract = camera ? camera->contract : 0;           // (the descriptor may accompany explicit rays just to carry this flag)
-    sc.rng_seed = seed; sc.rng_ray_offset = ray0;          // (read only when u_strat == NULL)
-    if (int e = launch_proposal_any(lflags, packed_prop, precision, sc, density, st)) return hip_status(e, "proposal MLP");
-    // rows 5-7: weights -> max-blur(0.01) -> inverse sampling of n_fine+1 sorted depths (procedures.py:68-70)
-    if (int e = sk_resample(density, nullptr, z_base, u_strat, jitter, rays + 3, 6, u_inv, N, C, n_fine + 1, 0, 0.01f, seed, ray0, z_fine,
-                            nullptr, nullptr, nullptr, st)) return hip_status(e, "resample");
-    nerf_amd_samples sf{};                                  // rows 8-9: drop the last depth, length2pts fused into the MLP
-    sf.mode = 1; sf.rays = rays; sf.S = n_fine; sf.M = N * n_fine; sf.z = z_fine; sf.z_stride = n_fine + 1;
-    sf.contract = sc.contract;
-    if (ipe) { sf.ipe = 1; sf.ipe_radius = camera->ipe_radius; sf.ipe_dir_norm = dir_norm; }   // frustum s = [z_fine[s], z_fine[s+1]]
+size_t nerf_amd_render_workspace_bytes(int64_t N, int n_fine) { return render_ws_bytes(WS_PLAIN, N, n_fine); }
+int nerf_amd_render_rays(const void* packed_prop, const void* packed_mip, int precision, const float* rays, const nerf_amd_samples* camera,
+                         int64_t ray_offset, const float* z_base, const float* u_strat, const float* u_inv, int64_t N, int n_fine, float near, float far,
+                         int white_bkg, float* rgb, float* depth, float* weights, void* workspace, void* stream) {
+    int lflags;
+    if (split_precision(precision, lflags, NERF_AMD_PROP_W128 | NERF_AMD_FINE_W128)) return fail(NERF_AMD_EINVAL, "unknown precision");
+    if ((lflags & NERF_AMD_FINE_W128) && camera && camera->ipe) return fail(NERF_AMD_EINVAL, "the 128-wide fine layout has no integrated-PE kernel: pack the network 256-wide");
+    if (N < 0 || n_fine < 1 || n_fine > 1023) return fail(NERF_AMD_EINVAL, "bad N or n_fine");
+    if (N == 0) return NERF_AMD_OK;
+    if (int e = check_render_inputs(packed_prop && packed_mip && z_base && rgb && workspace, rays, camera, u_strat, u_inv)) return e;
+    const RenderWs ws(WS_PLAIN, workspace, N, n_fine);
+    hipStream_t st = S(stream);
+    if (int e = provide_rays(rays, camera, ray_offset, N, ws.rays, st)) return e;
+    const float* dir_norm;
+    if (int e = provide_dir_norm(camera, rays, N, ws.dir_norm, ws.density, st, &dir_norm)) return e;
+    if (int e = coarse_pass(lflags, packed_prop, precision, rays, camera, z_base, u_strat, u_inv, N, n_fine, near, far, ws, st)) return e;
     // rows 9 and 10 as two launches: measured 2-3 % faster than the fused epilogue of nerf_amd_mip_forward_composite on
     // MI355X, and the composite kernel's HBM rate stays individually measurable
-    if (int e = launch_mip_any(lflags, packed_mip, precision, sf, rgbo, st)) return hip_status(e, "fine MLP");
+    if (int e = fine_pass(lflags, packed_mip, precision, rays, camera, N, n_fine, dir_norm, ws, st)) return e;
     const int flags = 1 | (white_bkg ? 2 : 0);              // row 10
-    if (int e = sk_composite(rgbo, z_fine, n_fine + 1, rays + 3, 6, N, n_fine, flags, NERF_AMD_ACT_RELU, 0.0f, near, far, nullptr,
+    if (int e = sk_composite(ws.rgbo, ws.z_fine, n_fine + 1, rays + 3, 6, N, n_fine, flags, NERF_AMD_ACT_RELU, 0.0f, near, far, nullptr,
                              nullptr, rgb, weights, depth, nullptr, st)) return hip_status(e, "composite");
     return NERF_AMD_OK;
 }
@@ -848,146 +801,70 @@ int nerf_amd_warped_resample(const float* density, const float* s_c, const float
                                          rng_ray_offset, z_fine, s_fine, below, w_prop, S(stream)), "nerf_amd_warped_resample");
 }
 
-// workspace: density (N,64) | s_c (N,64) | z_c (N,64) | z_fine (N, n_fine+1) | rgbo (N, n_fine, 4) | raw depth (N) | rays (N, 6)
-static size_t ws256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-size_t nerf_amd_render_warped_workspace_bytes(int64_t N, int n_fine) {
-    if (N < 0 || n_fine < 1) return 0;
-    return 3 * ws256((size_t)N * 64 * 4) + ws256((size_t)N * (n_fine + 1) * 4) + ws256((size_t)N * n_fine * 16) + ws256((size_t)N * 4) + ws256((size_t)N * 24) + 512;
-}
-
+size_t nerf_amd_render_warped_workspace_bytes(int64_t N, int n_fine) { return render_ws_bytes(WS_WARPED, N, n_fine); }
 int nerf_amd_render_rays_warped(const void* packed_prop, const void* packed_mip, int precision, const float* rays, const nerf_amd_samples* camera,
                                 int64_t ray_offset, const float* u_strat, const float* u_inv, int64_t N, int n_fine, int spacing, float near, float far,
                                 int white_bkg, float* rgb, float* depth, float* weights, void* workspace, void* stream) {
-    const int lflags = precision & ~0xff;
-    precision &= 0xff;
+    int lflags;
+    const bool bad_precision = split_precision(precision, lflags, NERF_AMD_PROP_W128 | NERF_AMD_FINE_W128);
     float gn, gf;
     if (int e = check_spacing(spacing, near, far, &gn, &gf)) return e;
-    if (bad_prec(precision) || (lflags & ~(NERF_AMD_PROP_W128 | NERF_AMD_FINE_W128))) return fail(NERF_AMD_EINVAL, "unknown precision");
+    if (bad_precision) return fail(NERF_AMD_EINVAL, "unknown precision");
     if ((lflags & NERF_AMD_FINE_W128) && camera && camera->ipe) return fail(NERF_AMD_EINVAL, "the 128-wide fine layout has no integrated-PE kernel: pack the network 256-wide");
     if (N < 0 || n_fine < 1 || n_fine > 1023) return fail(NERF_AMD_EINVAL, "bad N or n_fine");
-    constexpr int C = 64;                                   // procedures.py:22 RENDER_COARSE_PNUM
+    constexpr int C = RENDER_C;
     if (int e = check_warped_resample_shape(C, n_fine + 1)) return e;
     if (N == 0) return NERF_AMD_OK;
-    if (!packed_prop || !packed_mip || !rgb || !workspace) return fail(NERF_AMD_EINVAL, "NULL argument");
-    if ((u_strat == nullptr) != (u_inv == nullptr)) return fail(NERF_AMD_EINVAL, "u_strat and u_inv are both given or both NULL (in-kernel uniforms)");
-    if (!u_strat && !camera) return fail(NERF_AMD_EINVAL, "in-kernel uniforms need the descriptor (rng_seed, rng_ray_offset)");
-    if (!rays && !camera) return fail(NERF_AMD_EINVAL, "need rays or camera");
-    const bool ipe = camera && camera->ipe;
-    if (ipe && !(camera->ipe_radius > 0.0f)) return fail(NERF_AMD_EINVAL, "integrated PE needs a positive ipe_radius");
-    if (ipe && !rays) return fail(NERF_AMD_EINVAL, "integrated PE needs an explicit ray table");
-    if (!rays && (camera->H <= 0 || camera->W <= 0 || ray_offset < 0 || ray_offset + N > (int64_t)camera->H * camera->W))
-        return fail(NERF_AMD_EINVAL, "ray range outside the camera image");
+    if (int e = check_render_inputs(packed_prop && packed_mip && rgb && workspace, rays, camera, u_strat, u_inv)) return e;
+    if (camera && camera->ipe && !rays) return fail(NERF_AMD_EINVAL, "integrated PE needs an explicit ray table");
     const uint64_t seed = camera ? camera->rng_seed : 0;
     const int64_t ray0 = camera ? camera->rng_ray_offset : 0;
-    char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    auto take = [&](size_t bytes) { float* p = reinterpret_cast<float*>(ws); ws += ws256(bytes); return p; };
-    float* density = take((size_t)N * C * 4);
-    float* s_c = take((size_t)N * C * 4);
-    float* z_c = take((size_t)N * C * 4);
-    float* z_fine = take((size_t)N * (n_fine + 1) * 4);
-    float* rgbo = take((size_t)N * n_fine * 16);
-    float* depth_raw = take((size_t)N * 4);
-    float* gen = take((size_t)N * 24);
-    float* dir_norm = reinterpret_cast<float*>(ws);
+    const RenderWs ws(WS_WARPED, workspace, N, n_fine);
     hipStream_t st = S(stream);
-    if (!rays) {
-        if (int e = sk_generate_rays(camera->pose, camera->H, camera->W, camera->fx, camera->fy, ray_offset, N, gen, st))
-            return hip_status(e, "ray generation");
-        rays = gen;
-    }
-    if (ipe) {                                              // as in nerf_amd_render_rays (the density buffer is scratch until the proposal pass)
-        if (camera->ipe_dir_norm) dir_norm = const_cast<float*>(camera->ipe_dir_norm);
-        else if (int e = (N >= 8) ? sk_dirs_norm_scratch(rays, N, dir_norm, density, st) : sk_dirs_norm(rays, N, dir_norm, st))
-            return hip_status(e, "direction norm");
-    }
+    if (int e = provide_rays(rays, camera, ray_offset, N, ws.rays, st)) return e;
+    const float* dir_norm;
+    if (int e = provide_dir_norm(camera, rays, N, ws.dir_norm, ws.density, st, &dir_norm)) return e;
     // the coarse draw in s and its metric depths (no position tensor: the proposal MLP forms o + z d itself)
-    if (int e = sk_warped_stratified(rays, u_strat, N, C, seed, ray0, near, far, gn, gf, s_c, z_c, nullptr, st)) return hip_status(e, "warped stratified draw");
-    nerf_amd_samples sc{};
-    sc.mode = 1; sc.rays = rays; sc.S = C; sc.M = N * C; sc.z = z_c; sc.z_stride = C;
-    sc.contract = camera ? camera->contract : 0;
-    if (int e = launch_proposal_any(lflags, packed_prop, precision, sc, density, st)) return hip_status(e, "proposal MLP");
-    if (int e = sk_warped_resample(density, s_c, rays + 3, 6, u_inv, N, C, n_fine + 1, 0, 0.01f, near, far, gn, gf, seed, ray0, z_fine, nullptr, nullptr,
+    if (int e = sk_warped_stratified(rays, u_strat, N, C, seed, ray0, near, far, gn, gf, ws.s_c, ws.z_c, nullptr, st)) return hip_status(e, "warped stratified draw");
+    const nerf_amd_samples sc = ray_samples(rays, N, C, ws.z_c, C, camera);
+    if (int e = launch_proposal_any(lflags, packed_prop, precision, sc, ws.density, st)) return hip_status(e, "proposal MLP");
+    if (int e = sk_warped_resample(ws.density, ws.s_c, rays + 3, 6, u_inv, N, C, n_fine + 1, 0, 0.01f, near, far, gn, gf, seed, ray0, ws.z_fine, nullptr, nullptr,
                                    nullptr, st)) return hip_status(e, "warped resample");
-    nerf_amd_samples sf{};
-    sf.mode = 1; sf.rays = rays; sf.S = n_fine; sf.M = N * n_fine; sf.z = z_fine; sf.z_stride = n_fine + 1;
-    sf.contract = sc.contract;
-    if (ipe) { sf.ipe = 1; sf.ipe_radius = camera->ipe_radius; sf.ipe_dir_norm = dir_norm; }
-    if (int e = launch_mip_any(lflags, packed_mip, precision, sf, rgbo, st)) return hip_status(e, "fine MLP");
+    if (int e = fine_pass(lflags, packed_mip, precision, rays, camera, N, n_fine, dir_norm, ws, st)) return e;
     const int flags = 1 | (white_bkg ? 2 : 0);
     // near = 0, far = 1: the composite kernel's depth is then the raw expected metric depth sum w z |d|
-    if (int e = sk_composite(rgbo, z_fine, n_fine + 1, rays + 3, 6, N, n_fine, flags, NERF_AMD_ACT_RELU, 0.0f, 0.0f, 1.0f, nullptr, nullptr, rgb, weights,
-                             depth ? depth_raw : nullptr, nullptr, st)) return hip_status(e, "composite");
+    if (int e = sk_composite(ws.rgbo, ws.z_fine, n_fine + 1, rays + 3, 6, N, n_fine, flags, NERF_AMD_ACT_RELU, 0.0f, 0.0f, 1.0f, nullptr, nullptr, rgb, weights,
+                             depth ? ws.depth_raw : nullptr, nullptr, st)) return hip_status(e, "composite");
     if (depth) {
-        if (int e = sk_warp_depths(depth_raw, nullptr, N, 1, 1, near, far, gn, gf, depth, nullptr, st)) return hip_status(e, "depth un-warp");
+        if (int e = sk_warp_depths(ws.depth_raw, nullptr, N, 1, 1, near, far, gn, gf, depth, nullptr, st)) return hip_status(e, "depth un-warp");
     }
     return NERF_AMD_OK;
 }
 
-// workspace of nerf_amd_render_rays_ref: density (N,64) | z_fine (N, n_fine+1) | z_coarse (N,64) | z_all (N, n_fine+64) | rgbo (N, n_fine+64, 4)
-//                                        | normals (N, n_fine+64, 3) | rays (N, 6)
-static size_t ref_ws_part(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
-size_t nerf_amd_render_ref_workspace_bytes(int64_t N, int n_fine) {
-    if (N < 0 || n_fine < 1) return 0;
-    const size_t n = (size_t)N, S = (size_t)n_fine + 64;
-    return ref_ws_part(n * 64 * 4) * 2 + ref_ws_part(n * (n_fine + 1) * 4) + ref_ws_part(n * S * 4) + ref_ws_part(n * S * 16) + ref_ws_part(n * S * 12) +
-           n * 24 + 256;
-}
-
-int nerf_amd_render_rays_ref(const void* packed_prop, const void* packed_ref, int precision, int ref_flags, const float* rays,
-                             const nerf_amd_samples* camera, int64_t ray_offset, const float* z_base, const float* u_strat,
-                             const float* u_inv, int64_t N, int n_fine, float near, float far, int white_bkg, const float* cam_dir,
-                             float* rgb, float* depth, float* normal_img, void* workspace, void* stream) {
-    const int lflags = precision & ~0xff;
-    precision &= 0xff;
-    if (bad_prec(precision) || (lflags & ~NERF_AMD_PROP_W128) || bad_ref_flags(ref_flags)) return fail(NERF_AMD_EINVAL, "unknown precision or ref_flags");
+size_t nerf_amd_render_ref_workspace_bytes(int64_t N, int n_fine) { return render_ws_bytes(WS_REF, N, n_fine); }
+int nerf_amd_render_rays_ref(const void* packed_prop, const void* packed_ref, int precision, int ref_flags, const float* rays, const nerf_amd_samples* camera,
+                             int64_t ray_offset, const float* z_base, const float* u_strat, const float* u_inv, int64_t N, int n_fine, float near, float far,
+                             int white_bkg, const float* cam_dir, float* rgb, float* depth, float* normal_img, void* workspace, void* stream) {
+    int lflags;
+    if (split_precision(precision, lflags, NERF_AMD_PROP_W128) || bad_ref_flags(ref_flags)) return fail(NERF_AMD_EINVAL, "unknown precision or ref_flags");
     if (N < 0 || n_fine < 1 || n_fine > 1023) return fail(NERF_AMD_EINVAL, "bad N or n_fine");
     if (N == 0) return NERF_AMD_OK;
-    if (!packed_prop || !packed_ref || !z_base || !rgb || !workspace) return fail(NERF_AMD_EINVAL, "NULL argument");
-    if ((u_strat == nullptr) != (u_inv == nullptr)) return fail(NERF_AMD_EINVAL, "u_strat and u_inv are both given or both NULL (in-kernel uniforms)");
-    if (!u_strat && !camera) return fail(NERF_AMD_EINVAL, "in-kernel uniforms need the descriptor (rng_seed, rng_ray_offset)");
-    if (!rays && !camera) return fail(NERF_AMD_EINVAL, "need rays or camera");
-    const uint64_t seed = camera ? camera->rng_seed : 0;
-    const int64_t ray0 = camera ? camera->rng_ray_offset : 0;
+    if (int e = check_render_inputs(packed_prop && packed_ref && z_base && rgb && workspace, rays, camera, u_strat, u_inv)) return e;
     if ((normal_img != nullptr) != (cam_dir != nullptr)) return fail(NERF_AMD_EINVAL, "normal_img and cam_dir go together");
-    const int contract = camera ? camera->contract : 0;    // (round 4: a flag of the sample fetch for this path too; the build's own definition)
-    constexpr int C = 64;                                   // procedures.py:22 RENDER_COARSE_PNUM
+    constexpr int C = RENDER_C;
     const int S_all = n_fine + C;                           // (n_fine + 1) fine + 64 coarse depths, the last one dropped
-    char* ws = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    auto take = [&](size_t bytes) { float* p = reinterpret_cast<float*>(ws); ws += ref_ws_part(bytes); return p; };
-    float* density = take((size_t)N * C * 4);
-    float* z_fine = take((size_t)N * (n_fine + 1) * 4);
-    float* z_coarse = take((size_t)N * C * 4);
-    float* z_all = take((size_t)N * S_all * 4);
-    float* rgbo = take((size_t)N * S_all * 16);
-    float* normals = take((size_t)N * S_all * 12);
+    const RenderWs ws(WS_REF, workspace, N, n_fine);
     hipStream_t st = S(stream);
-    if (!rays) {                                            // row 1: procedures.py:43-51,64
-        if (camera->H <= 0 || camera->W <= 0 || ray_offset < 0 || ray_offset + N > (int64_t)camera->H * camera->W)
-            return fail(NERF_AMD_EINVAL, "ray range outside the camera image");
-        float* gen = reinterpret_cast<float*>(ws);
-        if (int e = sk_generate_rays(camera->pose, camera->H, camera->W, camera->fx, camera->fy, ray_offset, N, gen, st))
-            return hip_status(e, "ray generation");
-        rays = gen;
-    }
-    const float jitter = (far - near) / (float)n_fine;      // procedures.py:59
-    nerf_amd_samples sc{};                                  // rows 2-4
-    sc.mode = 1; sc.rays = rays; sc.S = C; sc.M = N * C; sc.z = nullptr; sc.z_base = z_base; sc.u = u_strat;
-    sc.z_jitter = jitter; sc.z_stride = C;
-    sc.contract = contract;
-    sc.rng_seed = seed; sc.rng_ray_offset = ray0;          // (read only when u_strat == NULL)
-    if (int e = launch_proposal_any(lflags, packed_prop, precision, sc, density, st)) return hip_status(e, "proposal MLP");
-    // rows 5-7 (procedures.py:68-70), also returning the stratified depths the proposal pass used
-    if (int e = sk_resample(density, nullptr, z_base, u_strat, jitter, rays + 3, 6, u_inv, N, C, n_fine + 1, 0, 0.01f, seed, ray0, z_fine,
-                            nullptr, nullptr, z_coarse, st)) return hip_status(e, "resample");
+    if (int e = provide_rays(rays, camera, ray_offset, N, ws.rays, st)) return e;
+    if (int e = coarse_pass(lflags, packed_prop, precision, rays, camera, z_base, u_strat, u_inv, N, n_fine, near, far, ws, st)) return e;
     // row 8, Ref-NeRF branch (procedures.py:71-74): fine and coarse depths merged, the last one dropped
-    if (int e = sk_merge_sorted(z_fine, z_coarse, N, n_fine + 1, C, z_all, st)) return hip_status(e, "depth merge");
-    nerf_amd_samples sf{};                                  // row 13
-    sf.mode = 1; sf.rays = rays; sf.S = S_all; sf.M = N * S_all; sf.z = z_all; sf.z_stride = S_all;
-    sf.contract = contract;
-    if (int e = mlp_launch_ref(packed_ref, precision, sf, rgbo, normal_img ? normals : nullptr, nullptr, ref_flags, st)) return hip_status(e, "Ref-NeRF MLP");
+    if (int e = sk_merge_sorted(ws.z_fine, ws.z_coarse, N, n_fine + 1, C, ws.z_all, st)) return hip_status(e, "depth merge");
+    const nerf_amd_samples sf = ray_samples(rays, N, S_all, ws.z_all, S_all, camera);   // row 13
+    float* normals = normal_img ? ws.normals : nullptr;
+    if (int e = mlp_launch_ref(packed_ref, precision, sf, ws.rgbo, normals, nullptr, ref_flags, st)) return hip_status(e, "Ref-NeRF MLP");
     const int flags = 1 | (white_bkg ? 2 : 0);              // row 10 with sigma -> softplus(sigma + 0.5) (procedures.py:73)
-    if (int e = sk_composite(rgbo, z_all, S_all, rays + 3, 6, N, S_all, flags, NERF_AMD_ACT_SOFTPLUS, 0.5f, near, far,
-                             normal_img ? normals : nullptr, cam_dir, rgb, nullptr, depth, normal_img, st)) return hip_status(e, "composite");
+    if (int e = sk_composite(ws.rgbo, ws.z_all, S_all, rays + 3, 6, N, S_all, flags, NERF_AMD_ACT_SOFTPLUS, 0.5f, near, far, normals, cam_dir, rgb, nullptr, depth,
+                             normal_img, st)) return hip_status(e, "composite");
     return NERF_AMD_OK;
 }
 

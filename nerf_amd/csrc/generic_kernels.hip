@@ -22,6 +22,7 @@
 
 #include "device_common.h"
 #include "host_common.h"
+#include "launchers.h"
 
 namespace {
 
@@ -284,12 +285,12 @@ int split_count(int64_t M, int64_t N, int64_t P) {
 
 }  // namespace
 
-size_t gk_gemm_workspace_bytes(int64_t M, int64_t N, int64_t P) {
+size_t nk::gk_gemm_workspace_bytes(int64_t M, int64_t N, int64_t P) {
     const int s = split_count(M, N, P);
     return s > 1 ? (size_t)s * (size_t)M * (size_t)N * sizeof(float) : 0;
 }
 
-int gk_gemm(int bf16, int64_t M, int64_t N, int64_t P, const float* A, int64_t a_si, int64_t a_sp, const float* B, int64_t b_sp, int64_t b_sj, float* C,
+int nk::gk_gemm(int bf16, int64_t M, int64_t N, int64_t P, const float* A, int64_t a_si, int64_t a_sp, const float* B, int64_t b_sp, int64_t b_sj, float* C,
             int64_t ldc, const float* bias, int act, const float* mask, int64_t ldm, void* workspace, hipStream_t st) {
     if (M == 0 || N == 0) return 0;
     const int S = split_count(M, N, P);
@@ -309,7 +310,7 @@ int gk_gemm(int bf16, int64_t M, int64_t N, int64_t P, const float* A, int64_t a
     return (int)hipGetLastError();
 }
 
-int gk_sigmoid_backward(const float* g, int64_t gs, const float* y, int64_t ys, int64_t M, int cols, float* out, int64_t os, hipStream_t st) {
+int nk::gk_sigmoid_backward(const float* g, int64_t gs, const float* y, int64_t ys, int64_t M, int cols, float* out, int64_t os, hipStream_t st) {
     if (M * cols == 0) return 0;
     hipLaunchKernelGGL(sigmoid_backward_kernel, dim3((unsigned)((M * cols + 255) / 256)), dim3(256), 0, st, g, gs, y, ys, M, cols, out, os);
     return (int)hipGetLastError();

@@ -18,6 +18,7 @@
 
 #include "device_common.h"
 #include "host_common.h"
+#include "launchers.h"
 
 namespace {
 
@@ -236,7 +237,7 @@ __global__ __launch_bounds__(256) void contract_kernel(const float* __restrict__
         default: return -1;                                                       \
     }
 
-int gr_dir_inputs(const float* heads, int64_t ldh, const float* dirs, int64_t ds, int64_t M, int deg, const float* mat, float* out, int64_t ldo, float* normal,
+int nk::gr_dir_inputs(const float* heads, int64_t ldh, const float* dirs, int64_t ds, int64_t M, int deg, const float* mat, float* out, int64_t ldo, float* normal,
                   hipStream_t st) {
     if (M == 0) return 0;
 #define GR_CALL(D) hipLaunchKernelGGL(ref_dir_inputs_kernel<D>, dim3(blocks(M)), dim3(256), 0, st, heads, ldh, dirs, ds, mat, M, out, ldo, normal)
@@ -245,7 +246,7 @@ int gr_dir_inputs(const float* heads, int64_t ldh, const float* dirs, int64_t ds
     return (int)hipGetLastError();
 }
 
-int gr_dir_inputs_backward(const float* heads, int64_t ldh, const float* dirs, int64_t ds, int64_t M, int deg, const float* mat, const float* d_in, int64_t ldi,
+int nk::gr_dir_inputs_backward(const float* heads, int64_t ldh, const float* dirs, int64_t ds, int64_t M, int deg, const float* mat, const float* d_in, int64_t ldi,
                            const float* g_normal, int64_t ldg, float* d_heads, int64_t ldd, hipStream_t st) {
     if (M == 0) return 0;
 #define GR_CALL(D) hipLaunchKernelGGL(ref_dir_inputs_backward_kernel<D>, dim3(blocks(M)), dim3(256), 0, st, heads, ldh, dirs, ds, mat, M, d_in, ldi, g_normal, ldg, d_heads, ldd)
@@ -254,32 +255,32 @@ int gr_dir_inputs_backward(const float* heads, int64_t ldh, const float* dirs, i
     return (int)hipGetLastError();
 }
 
-int gr_combine(const float* heads, int64_t ldh, const float* spec, int64_t lds_, int64_t M, int srgb, float* rgbo, hipStream_t st) {
+int nk::gr_combine(const float* heads, int64_t ldh, const float* spec, int64_t lds_, int64_t M, int srgb, float* rgbo, hipStream_t st) {
     if (M == 0) return 0;
     hipLaunchKernelGGL(ref_combine_kernel, dim3(blocks(M)), dim3(256), 0, st, heads, ldh, spec, lds_, M, srgb, rgbo);
     return (int)hipGetLastError();
 }
 
-int gr_combine_backward(const float* g, int64_t ldg, const float* heads, int64_t ldh, const float* spec, int64_t lds_, int64_t M, int srgb, float* d_spec, int64_t ldsp,
+int nk::gr_combine_backward(const float* g, int64_t ldg, const float* heads, int64_t ldh, const float* spec, int64_t lds_, int64_t M, int srgb, float* d_spec, int64_t ldsp,
                         float* d_heads, int64_t ldd, hipStream_t st) {
     if (M == 0) return 0;
     hipLaunchKernelGGL(ref_combine_backward_kernel, dim3(blocks(M)), dim3(256), 0, st, g, ldg, heads, ldh, spec, lds_, M, srgb, d_spec, ldsp, d_heads, ldd);
     return (int)hipGetLastError();
 }
 
-int gr_pe_backward(const float* d_enc, int64_t ldd, const float* x, int64_t ldx, int64_t M, int L, int cat_origin, float* d_x, hipStream_t st) {
+int nk::gr_pe_backward(const float* d_enc, int64_t ldd, const float* x, int64_t ldx, int64_t M, int L, int cat_origin, float* d_x, hipStream_t st) {
     if (M == 0) return 0;
     hipLaunchKernelGGL(pe_backward_kernel, dim3(blocks(M * 3)), dim3(256), 0, st, d_enc, ldd, x, ldx, M, L, cat_origin, d_x);
     return (int)hipGetLastError();
 }
 
-int gr_contract(const float* x, int64_t ldx, int64_t M, const float* g, int64_t ldg, float* out, hipStream_t st) {
+int nk::gr_contract(const float* x, int64_t ldx, int64_t M, const float* g, int64_t ldg, float* out, hipStream_t st) {
     if (M == 0) return 0;
     hipLaunchKernelGGL(contract_kernel, dim3(blocks(M)), dim3(256), 0, st, x, ldx, M, g, ldg, out);
     return (int)hipGetLastError();
 }
 
-int gr_add_rows(float* dst, int64_t ldd, const float* src, int64_t lds_, int64_t M, int cols, hipStream_t st) {
+int nk::gr_add_rows(float* dst, int64_t ldd, const float* src, int64_t lds_, int64_t M, int cols, hipStream_t st) {
     if (M * cols == 0) return 0;
     hipLaunchKernelGGL(add_rows_kernel, dim3(blocks(M * cols)), dim3(256), 0, st, dst, ldd, src, lds_, M, cols);
     return (int)hipGetLastError();

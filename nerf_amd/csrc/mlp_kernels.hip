@@ -22,6 +22,7 @@
 //
 // Reference semantics: addtional.py:88-96 (proposal), mip_model.py:41-60 (fine).
 #include "mlp_core.h"
+#include "launchers.h"
 
 namespace {
 
@@ -1321,14 +1322,14 @@ using PB16 = PBF16W;
 #define MLP_TU 0
 #endif
 #if MLP_TU == 0 || MLP_TU == 1
-int mlp_launch_proposal(const void* packed, int precision, const nerf_amd_samples& s, float* density, hipStream_t st) {
+int nk::mlp_launch_proposal(const void* packed, int precision, const nerf_amd_samples& s, float* density, hipStream_t st) {
     if (precision == NERF_AMD_BF16)
         return launch<PB16, PropLayout, false, false, (MLP_RESIDENT_PROP ? PropResident::TOTAL : 0)>(proposal_kernel<PB16, false>, packed, s, density, st, NO_DUMP);
     return launch<PF32, PropLayout>(proposal_kernel<PF32, false>, packed, s, density, st, NO_DUMP);
 }
 #endif
 #if MLP_TU == 0 || MLP_TU == 2
-int mlp_launch_mip(const void* packed, int precision, const nerf_amd_samples& s, float* rgbo, hipStream_t st) {
+int nk::mlp_launch_mip(const void* packed, int precision, const nerf_amd_samples& s, float* rgbo, hipStream_t st) {
     const FusedComposite off{nullptr, nullptr, nullptr, 0, 0.0f, 1.0f};
     if (s.ipe) {                                            // integrated positional encoding (validated by the C-ABI: mode 1, z, dir norm)
         if (precision == NERF_AMD_BF16) return launch<PB16, MipLayout>(mip_kernel<PB16, false, true>, packed, s, rgbo, st, off, NO_DUMP);
@@ -1339,18 +1340,22 @@ int mlp_launch_mip(const void* packed, int precision, const nerf_amd_samples& s,
     return launch<PF32, MipLayout>(mip_kernel<PF32, false>, packed, s, rgbo, st, off, NO_DUMP);
 }
 // packed = nerf_amd_pack_weights(NERF_AMD_NET_MIP_128, ...); point PE only (the C-ABI refuses s.ipe with this layout)
-int mlp_launch_mip128(const void* packed, int precision, const nerf_amd_samples& s, float* rgbo, hipStream_t st) {
+int nk::mlp_launch_mip128(const void* packed, int precision, const nerf_amd_samples& s, float* rgbo, hipStream_t st) {
     if (precision == NERF_AMD_BF16) return launch<PB16, MipLayout128>(mip128_kernel<PB16>, packed, s, rgbo, st);
     return launch<PF32, MipLayout128>(mip128_kernel<PF32>, packed, s, rgbo, st);
 }
 // fine MLP + compositing in one launch; requires mode 1 (rays + z) and S in {32, 64, 128}
-int mlp_launch_mip_composite(const void* packed, int precision, const nerf_amd_samples& s, float* rgb, float* depth, float* weights,
+int nk::mlp_launch_mip_composite(const void* packed, int precision, const nerf_amd_samples& s, float* rgb, float* depth, float* weights,
                              int white_bkg, float near, float far, hipStream_t st) {
     const FusedComposite fc{rgb, depth, weights, white_bkg, near, far};
     if (precision == NERF_AMD_BF16) return launch<PB16, MipLayout>(mip_kernel<PB16, false, false, false, true>, packed, s, (float*)nullptr, st, fc, NO_DUMP);
     return launch<PF32, MipLayout>(mip_kernel<PF32, false, false, false, true>, packed, s, (float*)nullptr, st, fc, NO_DUMP);
 }
 #endif
+static ActDump make_dump(void* dump, int precision, int64_t M, int slots) {
+    const unsigned long long ls = nk::mlp_train_layer_stride(precision, M);
+    return ActDump{reinterpret_cast<char*>(dump), ls, reinterpret_cast<char*>(dump) + (size_t)slots * ls, (unsigned long long)nk::mlp_train_mask_stride(precision, M)};
+}
 #if MLP_TU == 0 || MLP_TU == 1
 template <class P>
 static int launch_proposal128(const void* packed, const nerf_amd_samples& s, float* density, hipStream_t st) {
@@ -1363,30 +1368,19 @@ static int launch_proposal128(const void* packed, const nerf_amd_samples& s, flo
     return (int)hipGetLastError();
 }
 // packed = nerf_amd_pack_weights(NERF_AMD_NET_PROPOSAL_128, ...)
-int mlp_launch_proposal128(const void* packed, int precision, const nerf_amd_samples& s, float* density, hipStream_t st) {
+int nk::mlp_launch_proposal128(const void* packed, int precision, const nerf_amd_samples& s, float* density, hipStream_t st) {
     if (precision == NERF_AMD_BF16) return launch_proposal128<PBF16N>(packed, s, density, st);
     return launch_proposal128<PF32>(packed, s, density, st);
 }
-#endif
 // training forwards: the same kernels, also dumping the hidden activations (ActDump) for the backward
-#if MLP_TU == 0 || MLP_TU == 1
-size_t mlp_train_layer_stride(int precision, int64_t M) {
+size_t nk::mlp_train_layer_stride(int precision, int64_t M) {
     const int64_t ts = (precision != NERF_AMD_F32) ? (int64_t)PB16::NW * PB16::NT * 32 : (int64_t)PF32::NW * PF32::NT * 32;   // (BF16_F8 slots keep the bf16 footprint)
     const int64_t n_sub = ((M + ts - 1) / ts) * (ts / 32);
     return (size_t)n_sub * 16 * (precision != NERF_AMD_F32 ? 1024 : 2048);
 }
 // the ReLU bit masks sit behind the `slots` activation slots of a dump: 1 KiB per slot and subtile
-size_t mlp_train_mask_stride(int precision, int64_t M) { return mlp_train_layer_stride(precision, M) / (16 * (precision != NERF_AMD_F32 ? 1024 : 2048)) * 1024; }
-#else
-size_t mlp_train_layer_stride(int precision, int64_t M);
-size_t mlp_train_mask_stride(int precision, int64_t M);
-#endif
-static ActDump make_dump(void* dump, int precision, int64_t M, int slots) {
-    const unsigned long long ls = mlp_train_layer_stride(precision, M);
-    return ActDump{reinterpret_cast<char*>(dump), ls, reinterpret_cast<char*>(dump) + (size_t)slots * ls, (unsigned long long)mlp_train_mask_stride(precision, M)};
-}
-#if MLP_TU == 0 || MLP_TU == 1
-int mlp_launch_proposal_train(const void* packed, int precision, const nerf_amd_samples& s, float* density, void* dump, hipStream_t st) {
+size_t nk::mlp_train_mask_stride(int precision, int64_t M) { return mlp_train_layer_stride(precision, M) / (16 * (precision != NERF_AMD_F32 ? 1024 : 2048)) * 1024; }
+int nk::mlp_launch_proposal_train(const void* packed, int precision, const nerf_amd_samples& s, float* density, void* dump, hipStream_t st) {
     if (precision == NERF_AMD_BF16_F8) {                    // bf16 arithmetic, hidden slots of the dump in scaled e4m3 (mlp_layout.h)
         const ActDump d8 = make_dump(dump, NERF_AMD_BF16, s.M, PROP_DUMP_SLOTS);
         return launch<PB16, PropLayout, true, true>(proposal_kernel<PB16, true, true>, packed, s, density, st, d8);
@@ -1400,7 +1394,7 @@ int mlp_launch_proposal_train(const void* packed, int precision, const nerf_amd_
 }
 #endif
 #if MLP_TU == 0 || MLP_TU == 2
-int mlp_launch_mip_train(const void* packed, int precision, const nerf_amd_samples& s, float* rgbo, void* dump, hipStream_t st) {
+int nk::mlp_launch_mip_train(const void* packed, int precision, const nerf_amd_samples& s, float* rgbo, void* dump, hipStream_t st) {
     const FusedComposite off{nullptr, nullptr, nullptr, 0, 0.0f, 1.0f};
     if (precision == NERF_AMD_BF16_F8) {                    // bf16 arithmetic, hidden slots of the dump in scaled e4m3 (mlp_layout.h)
         const ActDump d8 = make_dump(dump, NERF_AMD_BF16, s.M, MIP_DUMP_SLOTS);
@@ -1430,13 +1424,13 @@ static int launch_ref(const void* packed, const nerf_amd_samples& s, float* rgbo
     hipLaunchKernelGGL((ref_kernel<P, TRAIN>), dim3(grid_for(n_tiles)), dim3(P::NW * 64), lds, st, packed, s, rgbo, normal, bn_noise, dump, aux, flags, seed, seed_dev, noise_std);
     return (int)hipGetLastError();
 }
-int mlp_launch_ref(const void* packed, int precision, const nerf_amd_samples& s, float* rgbo, float* normal, const float* bn_noise,
+int nk::mlp_launch_ref(const void* packed, int precision, const nerf_amd_samples& s, float* rgbo, float* normal, const float* bn_noise,
                    int flags, hipStream_t st) {
     if (precision == NERF_AMD_BF16) return launch_ref<PB16, false>(packed, s, rgbo, normal, bn_noise, NO_DUMP, nullptr, flags, st);
     return launch_ref<PF32, false>(packed, s, rgbo, normal, bn_noise, NO_DUMP, nullptr, flags, st);
 }
 // training forward of Ref-NeRF: activation dump (REF_DUMP_SLOTS slots of mlp_train_layer_stride bytes) + aux (M,16)
-int mlp_launch_ref_train(const void* packed, int precision, const nerf_amd_samples& s, float* rgbo, float* normal, const float* bn_noise,
+int nk::mlp_launch_ref_train(const void* packed, int precision, const nerf_amd_samples& s, float* rgbo, float* normal, const float* bn_noise,
                          void* dump, float* aux, int flags, hipStream_t st, unsigned long long seed, const unsigned long long* seed_dev, float noise_std) {
     const ActDump d = make_dump(dump, precision, s.M, REF_DUMP_SLOTS);     // 17 activation slots + (round 4) their ReLU bit-mask records
     // bf16 training forward: the 8-wave x 32-sample tile, like the proposal network's -- its 512 dump stores per wave and tile cost their

@@ -3,6 +3,7 @@
 // Runs on the GPU (a few microseconds) so it can be repeated after every optimiser step.
 #include "device_common.h"
 #include "mlp_layout.h"
+#include "launchers.h"
 
 namespace {
 
@@ -111,7 +112,7 @@ int launch_pack(const PackBatch& B, int n_layers, int precision, char* stream, f
 
 }  // namespace
 
-int pack_proposal(int precision, const float* const* w, const float* const* b, void* packed, hipStream_t st) {
+int nk::pack_proposal(int precision, const float* const* w, const float* const* b, void* packed, hipStream_t st) {
     using Lay = PropLayout;
     char* stream = reinterpret_cast<char*>(packed);
     float* bias = reinterpret_cast<float*>(stream + Lay::stream_bytes(precision));
@@ -127,7 +128,7 @@ int pack_proposal(int precision, const float* const* w, const float* const* b, v
 
 // ProposalNetwork(10, 128): w = layers.{0,2,4,6,8}.weight in their own (128-wide) shapes; the stream's last 8 fragments are padding
 // (never multiplied: the kernel fetches and drops them), zeroed once here so that the blob is deterministic
-int pack_proposal128(int precision, const float* const* w, const float* const* b, void* packed, hipStream_t st) {
+int nk::pack_proposal128(int precision, const float* const* w, const float* const* b, void* packed, hipStream_t st) {
     using Lay = PropLayout128;
     char* stream = reinterpret_cast<char*>(packed);
     float* bias = reinterpret_cast<float*>(stream + Lay::stream_bytes(precision));
@@ -143,7 +144,7 @@ int pack_proposal128(int precision, const float* const* w, const float* const* b
     return launch_pack(B, 5, precision, stream, bias, st);
 }
 
-int pack_mip(int precision, const float* const* w, const float* const* b, void* packed, hipStream_t st) {
+int nk::pack_mip(int precision, const float* const* w, const float* const* b, void* packed, hipStream_t st) {
     using Lay = MipLayout;
     char* stream = reinterpret_cast<char*>(packed);
     float* bias = reinterpret_cast<float*>(stream + Lay::stream_bytes(precision));
@@ -171,7 +172,7 @@ int pack_mip(int precision, const float* const* w, const float* const* b, void* 
 }
 
 // MipNeRF(10, 4, 128): the 11 tensors in their own shapes (lin_block1 128 wide, lin_block2.0 (128, 191), lin_block2.4 (256, 128), heads as at 256)
-int pack_mip128(int precision, const float* const* w, const float* const* b, void* packed, hipStream_t st) {
+int nk::pack_mip128(int precision, const float* const* w, const float* const* b, void* packed, hipStream_t st) {
     using Lay = MipLayout128;
     char* stream = reinterpret_cast<char*>(packed);
     float* bias = reinterpret_cast<float*>(stream + Lay::stream_bytes(precision));
@@ -199,7 +200,7 @@ int pack_mip128(int precision, const float* const* w, const float* const* b, voi
 
 // tensors: 0-3 spa_block1.{0,2,4,6}; 4-7 spa_block2.{0,2,4,6}; 8 bottle_neck; 9 heads (11,256); 10-13 dir_block1.{0,2,4,6};
 //          14-17 dir_block2.{0,2,4,6}; 18 spec_rgb_head.0; 19 ide_table (9,19) in the weights slot
-int pack_ref(int precision, const float* const* w, const float* const* b, void* packed, hipStream_t st) {
+int nk::pack_ref(int precision, const float* const* w, const float* const* b, void* packed, hipStream_t st) {
     using Lay = RefLayout;
     char* stream = reinterpret_cast<char*>(packed);
     float* bias = reinterpret_cast<float*>(stream + Lay::stream_bytes(precision));
@@ -241,7 +242,7 @@ PackLayer make_trans_layer(const float* w, int stride, int col0, int rows, int k
 }  // namespace
 
 // proposal: w = layers.{0,2,4,6,8}.weight
-int pack_proposal_bwd(int precision, const float* const* w, void* packed, hipStream_t st) {
+int nk::pack_proposal_bwd(int precision, const float* const* w, void* packed, hipStream_t st) {
     using Lay = PropBwdLayout;
     PackBatch B = {};
     B.L[0] = make_trans_layer(w[4], 256, 0, 256, 1, Lay::NKG[0], Lay::NFB[0], Lay::START[0]);       // d3 = layers.8^T g (+ one zero K group)
@@ -251,7 +252,7 @@ int pack_proposal_bwd(int precision, const float* const* w, void* packed, hipStr
 }
 
 // MipNeRF: w in _linear_layers() order (0..3 lin_block1, 4..6 lin_block2, 7 bottle_neck.0, 8 opacity_head.0, 9, 10 rgb_layer.{0,2})
-int pack_mip_bwd(int precision, const float* const* w, void* packed, hipStream_t st) {
+int nk::pack_mip_bwd(int precision, const float* const* w, void* packed, hipStream_t st) {
     using Lay = MipBwdLayout;
     char* stream = reinterpret_cast<char*>(packed);
     float* wf = reinterpret_cast<float*>(stream + Lay::stream_bytes(precision));
@@ -273,7 +274,7 @@ int pack_mip_bwd(int precision, const float* const* w, void* packed, hipStream_t
 
 // Ref-NeRF: w = the 20 tensors of pack_ref (0-3 spa_block1, 4-7 spa_block2, 8 bottle_neck, 9 heads (11,256), 10-13 dir_block1,
 // 14-17 dir_block2, 18 spec_rgb_head.0, 19 ide_table); layer table: mlp_layout.h RefBwdLayout
-int pack_ref_bwd(int precision, const float* const* w, void* packed, hipStream_t st) {
+int nk::pack_ref_bwd(int precision, const float* const* w, void* packed, hipStream_t st) {
     using Lay = RefBwdLayout;
     PackBatch B = {};
     auto full = [&](int l, const float* m) { B.L[l] = make_trans_layer(m, 256, 0, 256, 256, 16, 8, Lay::START[l]); };
@@ -413,7 +414,7 @@ int launch_mfma_stream(int iters, int workgroups, float* sink, hipStream_t st) {
     return (int)hipGetLastError();
 }
 }  // namespace
-int pack_mfma_stream(int iters, int workgroups, int mode, float* sink, hipStream_t st) {
+int nk::pack_mfma_stream(int iters, int workgroups, int mode, float* sink, hipStream_t st) {
     switch (mode) {
         case 0: return launch_mfma_stream<0>(iters, workgroups, sink, st);
         case 1: return launch_mfma_stream<1>(iters, workgroups, sink, st);

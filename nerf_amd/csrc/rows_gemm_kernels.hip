@@ -32,6 +32,7 @@
 
 #include "device_common.h"
 #include "host_common.h"
+#include "launchers.h"
 
 namespace {
 
@@ -322,7 +323,7 @@ __global__ __launch_bounds__(256) void rows_to_bf16_kernel(const float* __restri
 
 }  // namespace
 
-int rg_rows_gemm(int64_t M, int64_t N, int64_t K, const void* X, int64_t ldx, const void* W, int64_t ldw, int64_t n_pad, const float* bias, int act, void* C,
+int nk::rg_rows_gemm(int64_t M, int64_t N, int64_t K, const void* X, int64_t ldx, const void* W, int64_t ldw, int64_t n_pad, const float* bias, int act, void* C,
                  int64_t ldc, int out_bf16, hipStream_t st) {
     if (M == 0 || N == 0) return 0;
     if (K < 1 || (ldx & 7) || (reinterpret_cast<uintptr_t>(X) & 15u) || (ldw & 63) || ldw < K || (reinterpret_cast<uintptr_t>(W) & 15u) || (n_pad & 255) || n_pad < N ||
@@ -340,7 +341,7 @@ int rg_rows_gemm(int64_t M, int64_t N, int64_t K, const void* X, int64_t ldx, co
     return rows_launch<RowsCfg<128, 256, 32, 3, 2, 2, 2>>(g, out_bf16, st);
 }
 
-int rg_rows_to_bf16(const float* src, int64_t rows_src, int64_t lds, int64_t rows, int cols, int fill, void* dst, int64_t ldd, hipStream_t st) {
+int nk::rg_rows_to_bf16(const float* src, int64_t rows_src, int64_t lds, int64_t rows, int cols, int fill, void* dst, int64_t ldd, hipStream_t st) {
     if (rows * fill == 0) return 0;
     hipLaunchKernelGGL(rows_to_bf16_kernel, dim3((unsigned)((rows * fill + 255) / 256)), dim3(256), 0, st, src, rows_src, lds, rows, cols, fill,
                        reinterpret_cast<uint16_t*>(dst), ldd);

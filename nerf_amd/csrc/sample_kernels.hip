@@ -8,6 +8,7 @@
 #include "device_common.h"
 #include "host_common.h"
 #include "../../include/nerf_amd.h"
+#include "launchers.h"
 
 extern __shared__ __attribute__((aligned(16))) char smem[];
 
@@ -547,8 +548,9 @@ DEVINL void wave_inverse_sample(const float* pw, const float* bins, int nw, floa
     }
 }
 
-// LDS floats per wave: pw[C] bins[C] cdf[C] samp[K] bel[K] sortbuf
-DEVINL size_t inv_lds_floats(int C, int K) { return (size_t)3 * C + 2 * K + SORT_LDS_FLOATS; }
+// LDS floats per wave: pw[C] bins[C] cdf[C] samp[K] bel[K] sortbuf; resample_kernel appends zl[C] wraw[C]
+static inline __host__ __device__ size_t inv_lds_floats(int C, int K) { return (size_t)3 * C + 2 * K + SORT_LDS_FLOATS; }
+static inline __host__ __device__ size_t rs_lds_floats(int C, int K) { return inv_lds_floats(C, K) + 2 * C; }
 
 // mode 0: inverseSample(weights (N,C), depths (N,C)) -> bins = mid-points, pdf = weights[1:-1]   (utils.py:34-44)
 // mode 1: sample_pdf(bins (N,C), weights (N,C-1))                                               (utils.py:108-133)
@@ -594,8 +596,7 @@ struct ResampleArgs {
 #endif
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RS_BLOCKS_PER_CU, RS_BLOCKS_PER_CU))) void resample_kernel(ResampleArgs a) {
     const int C = a.C, K = a.K;
-    // per wave: pw[C] bins[C] cdf[C] samp[K] bel[K] | zl[C] wraw[C]
-    float* base = reinterpret_cast<float*>(smem) + wave_in_block() * (inv_lds_floats(C, K) + 2 * C);
+    float* base = reinterpret_cast<float*>(smem) + wave_in_block() * rs_lds_floats(C, K);
     float* pw = base; float* bins = pw + C; float* cdf = bins + C; float* samp = cdf + C;
     int* bel = reinterpret_cast<int*>(samp + K);
     int* sortbuf = bel + K;
@@ -750,7 +751,7 @@ struct WarpedResampleArgs {
     float alpha; WarpConsts c; float* z_fine; float* s_fine; int64_t* below; float* w_prop; uint64_t rng_seed; int64_t rng_ray_offset;
 };
 // LDS floats per wave: the rows of inverse_sample_kernel | zl[C] wraw[C] | sf[K] uu[K]
-DEVINL size_t warped_lds_floats(int C, int K) { return inv_lds_floats(C, K) + (size_t)2 * C + (size_t)2 * K; }
+static inline __host__ __device__ size_t warped_lds_floats(int C, int K) { return inv_lds_floats(C, K) + (size_t)2 * C + (size_t)2 * K; }
 
 __global__ __launch_bounds__(256) void warped_resample_kernel(WarpedResampleArgs a) {
     const int C = a.C, K = a.K;
@@ -926,9 +927,10 @@ __global__ __launch_bounds__(256) void composite_kernel(CompositeArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------- row 11
+template <class T> static inline __host__ __device__ T gb_lds_floats(T C) { return C + 1; }               // per wave: the summed-area row sat[C + 1]
 __global__ __launch_bounds__(256) void get_bounds_kernel(const float* __restrict__ w, const int64_t* __restrict__ below,
                                                         int64_t N, int C, int K, float* __restrict__ bounds) {
-    float* sat = reinterpret_cast<float*>(smem) + wave_in_block() * (C + 1);
+    float* sat = reinterpret_cast<float*>(smem) + wave_in_block() * gb_lds_floats(C);
     const int lane = lane_id();
     for (int64_t n = blockIdx.x * (int64_t)WAVES_PER_BLOCK + wave_in_block(); n < N; n += (int64_t)gridDim.x * WAVES_PER_BLOCK) {
         lds_wave_sync();
@@ -1066,9 +1068,10 @@ __global__ void max_blur_backward_kernel(const float* __restrict__ w, const floa
 // getBounds backward (addtional.py:14-18): bounds_k = sat[below_{k+1} + 1] - sat[below_k] = +sum of w over [below_k, below_{k+1}] (or minus the
 // sum over the gap when the indices are not ascending)  ->  dw_j = sum_k g_k * ([st_k <= j < en_k] - [en_k <= j < st_k]).
 // Every lane gathers its own j in ascending k: no atomics, reproducible.
+template <class T> static inline __host__ __device__ T gbb_lds_words(T K) { return 2 * K; }               // per wave: below[K] (int) g[K]
 __global__ __launch_bounds__(256) void get_bounds_backward_kernel(const int64_t* __restrict__ below, const float* __restrict__ g, int64_t N, int C,
                                                                   int K, float* __restrict__ dw) {
-    int* bl_lds = reinterpret_cast<int*>(smem) + wave_in_block() * (2 * K);
+    int* bl_lds = reinterpret_cast<int*>(smem) + wave_in_block() * gbb_lds_words(K);
     float* g_lds = reinterpret_cast<float*>(bl_lds + K);
     const int lane = lane_id();
     for (int64_t n = blockIdx.x * (int64_t)WAVES_PER_BLOCK + wave_in_block(); n < N; n += (int64_t)gridDim.x * WAVES_PER_BLOCK) {
@@ -1096,6 +1099,8 @@ __global__ __launch_bounds__(256) void get_bounds_backward_kernel(const int64_t*
 // Training dump (mlp_kernels.hip ActDump) -> row-major activations.  Block (subtile, K group) of the dump holds, for lane
 // (h = lane >> 5, j = lane & 31), the 8 features 16 kg + 8 (e >> 2) + 4 h + (e & 3), e = 0..7, of sample 32 subtile + j
 // (mlp_layout.h dmap_feature): two runs of four consecutive features.  ELEM = 2 (bf16) or 4 (fp32, halves 1 KiB apart).
+static inline __host__ __device__ int frag_pitch(int n_kg, int elem) { return n_kg * 16 * elem + 16; }   // per wave: a 32-row tile, the row pitch padded by 16 bytes
+static inline __host__ __device__ size_t frag_wave_bytes(int n_kg, int elem) { return (size_t)32 * frag_pitch(n_kg, elem); }
 template <int ELEM>
 __global__ __launch_bounds__(256) void frag_to_rows_kernel(const char* __restrict__ frag, int64_t n_sub, int n_kg, int64_t M,
                                                            char* __restrict__ out, int ld) {
@@ -1105,8 +1110,8 @@ __global__ __launch_bounds__(256) void frag_to_rows_kernel(const char* __restric
     const int lane = lane_id(), h = lane >> 5, j = lane & 31;
     constexpr int BLOCK = 512 * ELEM;                           // bytes per (subtile, K group)
     const int row_bytes = n_kg * 16 * ELEM;
-    const int pitch = row_bytes + 16;
-    char* tile = smem + (size_t)wave_in_block() * 32 * pitch;
+    const int pitch = frag_pitch(n_kg, ELEM);
+    char* tile = smem + (size_t)wave_in_block() * frag_wave_bytes(n_kg, ELEM);
     for (int64_t sub = blockIdx.x * (int64_t)WAVES_PER_BLOCK + wave_in_block(); sub < n_sub; sub += (int64_t)gridDim.x * WAVES_PER_BLOCK) {
         lds_wave_sync();
         char* trow = tile + j * pitch;
@@ -1146,9 +1151,9 @@ __global__ __launch_bounds__(256) void frag_rows_mask_kernel(const char* __restr
     constexpr int BLOCK = 512 * ELEM;
     constexpr int NV = 16 / ELEM;                                // values per 16-byte chunk
     const int row_bytes = n_kg * 16 * ELEM;
-    const int pitch = row_bytes + 16;
+    const int pitch = frag_pitch(n_kg, ELEM);
     const int ld = n_kg * 16;
-    char* tile = smem + (size_t)wave_in_block() * 32 * pitch;
+    char* tile = smem + (size_t)wave_in_block() * frag_wave_bytes(n_kg, ELEM);
     const int cpr = row_bytes / 16;                              // 16, 32 or 64: divides the wave size
     const int q = lane % cpr, r0 = lane / cpr, rstep = 64 / cpr;
     float acc[NV];
@@ -1332,9 +1337,10 @@ DEVINL void wave_sort_if_needed(float* v, float* tmp, int n, int lane) {
     for (int i = lane; i < n; i += 64) v[i] = tmp[i];
     lds_wave_sync();
 }
+template <class T> static inline __host__ __device__ T merge_lds_floats(T K, T C, bool order) { return (order ? 4 : 2) * (K + C); }   // per wave: la[K] lb[C] tmp[K + C] (order: + indices)
 __global__ __launch_bounds__(256) void merge_sorted_kernel(const float* __restrict__ a, const float* __restrict__ b, int64_t N, int K, int C,
                                                            float* __restrict__ out) {
-    float* la = reinterpret_cast<float*>(smem) + wave_in_block() * 2 * (K + C);
+    float* la = reinterpret_cast<float*>(smem) + wave_in_block() * merge_lds_floats(K, C, false);
     float* lb = la + K;
     float* tmp = lb + C;                                        // K + C floats of scratch for the rare sorting path
     const int lane = lane_id();
@@ -1382,7 +1388,7 @@ DEVINL void wave_sort_idx_if_needed(float* v, int* idx, float* tmp, int* itmp, i
 __global__ __launch_bounds__(256) void merge_sorted_order_kernel(const float* __restrict__ a, const float* __restrict__ b, const int64_t* __restrict__ f_inds,
                                                                  int64_t N, int K, int C, float* __restrict__ out, int64_t* __restrict__ order,
                                                                  int64_t* __restrict__ all_inds) {
-    float* la = reinterpret_cast<float*>(smem) + wave_in_block() * 4 * (K + C);
+    float* la = reinterpret_cast<float*>(smem) + wave_in_block() * merge_lds_floats(K, C, true);
     float* lb = la + K;
     float* tmp = lb + C;
     int* ia = reinterpret_cast<int*>(tmp + K + C);
@@ -1520,11 +1526,12 @@ DEVINL void dist_stage(const float* __restrict__ w, const float* __restrict__ t,
     }
 }
 
+static inline __host__ __device__ size_t dist_wave_floats(int W, int M) { return (size_t)W * M; }   // per wave: W floats for each of the M intervals
 template <int MODE>
 __global__ __launch_bounds__(256) void distortion_loss_kernel(const float* __restrict__ w, const float* __restrict__ t, int64_t N, int S,
                                                               double* __restrict__ partial) {
     const int M = S - 1, lane = lane_id();
-    float* row = reinterpret_cast<float*>(smem) + (size_t)wave_in_block() * 2 * M;
+    float* row = reinterpret_cast<float*>(smem) + (size_t)wave_in_block() * 2 * M;   // = wave x dist_wave_floats(2, M), kept spelled out: through the call the compiler schedules this kernel differently
     double accP = 0.0, accQ = 0.0;
     for (int64_t n = blockIdx.x * (int64_t)WAVES_PER_BLOCK + wave_in_block(); n < N; n += (int64_t)gridDim.x * WAVES_PER_BLOCK) {
         lds_wave_sync();
@@ -1603,7 +1610,7 @@ __global__ __launch_bounds__(256) void distortion_loss_backward_kernel(const flo
                                                                        float* __restrict__ d_t) {
     constexpr int W = MODE == 0 ? 6 : 2;                                                     // LDS floats per interval: c, a (, u, q as doubles)
     const int M = S - 1, lane = lane_id();
-    float* row = reinterpret_cast<float*>(smem) + (size_t)wave_in_block() * W * M;
+    float* row = reinterpret_cast<float*>(smem) + wave_in_block() * dist_wave_floats(W, M);
     double kP, kQ;
     dist_coeffs(MODE, N, M, kP, kQ);
     const double gs = (double)g[0] * (double)scale;
@@ -1867,33 +1874,41 @@ int blocks_for(int64_t work, int per_block) {
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ host launchers
-int sk_positional_encoding(const float* x, int64_t M, int L, float* out, hipStream_t st) {
+// dynamic LDS of the launch a shape leads to = the kernel's own per-wave layout x the waves of a workgroup, in size_t: no shape overflows (capi.hip checks against these)
+static size_t wave_rows_bytes(size_t floats_per_wave) { return WAVES_PER_BLOCK * floats_per_wave * 4; }
+size_t nk::sk_inverse_sample_lds_bytes(int C, int K) { return wave_rows_bytes(inv_lds_floats(C, K)); }
+size_t nk::sk_resample_lds_bytes(int C, int K) { return wave_rows_bytes(rs_lds_floats(C, K)); }
+size_t nk::sk_warped_resample_lds_bytes(int C, int K) { return wave_rows_bytes(warped_lds_floats(C, K)); }
+size_t nk::sk_get_bounds_lds_bytes(int C) { return wave_rows_bytes(gb_lds_floats((size_t)C)); }
+size_t nk::sk_get_bounds_backward_lds_bytes(int K) { return wave_rows_bytes(gbb_lds_words((size_t)K)); }
+size_t nk::sk_merge_sorted_lds_bytes(int K, int C, int order) { return wave_rows_bytes(merge_lds_floats((size_t)K, (size_t)C, order != 0)); }
+int nk::sk_positional_encoding(const float* x, int64_t M, int L, float* out, hipStream_t st) {
     if (M * L == 0) return 0;
     hipLaunchKernelGGL(pe_kernel, dim3(blocks_for(M, ENC_TILE)), dim3(256), enc_lds_bytes(L), st, x, M, L, out);
     return (int)hipGetLastError();
 }
-int sk_ipe_feature(const float* z, const float* rays, int64_t N, int Sn, int L, float r2, const float* dir_norm, float* feat, float* mu,
+int nk::sk_ipe_feature(const float* z, const float* rays, int64_t N, int Sn, int L, float r2, const float* dir_norm, float* feat, float* mu,
                    float* mu_t, int contract, hipStream_t st) {
     if (N * Sn == 0) return 0;
     hipLaunchKernelGGL(ipe_feature_kernel, dim3(blocks_for(N * Sn, ENC_TILE)), dim3(256), enc_lds_bytes(L), st, z, rays, N, Sn, L, r2, dir_norm, feat, mu, mu_t, contract);
     return (int)hipGetLastError();
 }
-int sk_cone_parameters(const float* z, int64_t N, int Sn, float r2, float* mu_t, float* var_t, float* var_r, hipStream_t st) {
+int nk::sk_cone_parameters(const float* z, int64_t N, int Sn, float r2, float* mu_t, float* var_t, float* var_r, hipStream_t st) {
     if (N * Sn == 0) return 0;
     hipLaunchKernelGGL(cone_parameters_kernel, dim3(blocks_for(N * Sn, 256)), dim3(256), 0, st, z, N, Sn, r2, mu_t, var_t, var_r);
     return (int)hipGetLastError();
 }
-int sk_dirs_norm(const float* rays, int64_t N, float* out, hipStream_t st) {
+int nk::sk_dirs_norm(const float* rays, int64_t N, float* out, hipStream_t st) {
     hipLaunchKernelGGL(dirs_norm_kernel, dim3(1), dim3(1024), 0, st, rays, N, out);
     return (int)hipGetLastError();
 }
 // `partials`: DN_BLOCKS doubles of device scratch (8-byte aligned)
-int sk_dirs_norm_scratch(const float* rays, int64_t N, float* out, void* partials, hipStream_t st) {
+int nk::sk_dirs_norm_scratch(const float* rays, int64_t N, float* out, void* partials, hipStream_t st) {
     hipLaunchKernelGGL(dirs_norm_partial_kernel, dim3(DN_BLOCKS), dim3(256), 0, st, rays, N, reinterpret_cast<double*>(partials));
     hipLaunchKernelGGL(dirs_norm_final_kernel, dim3(1), dim3(256), 0, st, reinterpret_cast<const double*>(partials), out);
     return (int)hipGetLastError();
 }
-int sk_train_sampler(const float* rgbs, const int64_t* coords, int64_t P, const float* pose, const float* pose_dev, float fx, float fy, float near, float far,
+int nk::sk_train_sampler(const float* rgbs, const int64_t* coords, int64_t P, const float* pose, const float* pose_dev, float fx, float fy, float near, float far,
                      int64_t N, int C, uint64_t seed, const uint64_t* seed_dev, float* pts, float* lengths, float* rgb, float* rays, hipStream_t st) {
     if (N == 0) return 0;
     Cam c; c.H = 0; c.W = 0; c.fx = fx; c.fy = fy;
@@ -1904,7 +1919,7 @@ int sk_train_sampler(const float* rgbs, const int64_t* coords, int64_t P, const 
 }
 
 // window: x0 <= col < x1, y0 <= row < y1 (validated by the caller)
-int sk_scene_sampler(const float* images, const float* poses, int64_t V, int H, int W, const int64_t* view_ids, int64_t K, int x0, int x1, int y0, int y1,
+int nk::sk_scene_sampler(const float* images, const float* poses, int64_t V, int H, int W, const int64_t* view_ids, int64_t K, int x0, int x1, int y0, int y1,
                      float fx, float fy, float near, float far, int64_t N, int C, uint64_t seed, const uint64_t* seed_dev, float* pts, float* lengths,
                      float* rgb, float* rays, int64_t* index, hipStream_t st) {
     if (N == 0) return 0;
@@ -1946,7 +1961,7 @@ __global__ void philox_normal_kernel(float* __restrict__ out, int64_t M, uint64_
         *reinterpret_cast<f32x4*>(row + 8) = f32x4{z[4], z[5], z[6], z[7]};
     }
 }
-int sk_philox_normal(float* out, int64_t M, uint64_t seed, const uint64_t* seed_dev, float std, int64_t sample_offset, hipStream_t st) {
+int nk::sk_philox_normal(float* out, int64_t M, uint64_t seed, const uint64_t* seed_dev, float std, int64_t sample_offset, hipStream_t st) {
     if (M == 0) return 0;
     hipLaunchKernelGGL(philox_normal_kernel, dim3(blocks_for(M * 16, 256)), dim3(256), 0, st, out, M, seed, seed_dev, std, sample_offset);
     return (int)hipGetLastError();
@@ -1958,16 +1973,16 @@ __global__ void advance_seed_kernel(uint64_t* __restrict__ seed_dev) {
     x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
     seed_dev[0] = x ^ (x >> 31);
 }
-int sk_philox_uniforms(float* out, int64_t N, int K, uint64_t seed, const uint64_t* seed_dev, int64_t ray_offset, int strat, hipStream_t st) {
+int nk::sk_philox_uniforms(float* out, int64_t N, int K, uint64_t seed, const uint64_t* seed_dev, int64_t ray_offset, int strat, hipStream_t st) {
     if (N * K == 0) return 0;
     hipLaunchKernelGGL(philox_uniforms_kernel, dim3(blocks_for(N * K, 256)), dim3(256), 0, st, out, N, K, seed, seed_dev, ray_offset, strat);
     return (int)hipGetLastError();
 }
-int sk_advance_seed(uint64_t* seed_dev, hipStream_t st) {
+int nk::sk_advance_seed(uint64_t* seed_dev, hipStream_t st) {
     hipLaunchKernelGGL(advance_seed_kernel, dim3(1), dim3(1), 0, st, seed_dev);
     return (int)hipGetLastError();
 }
-int sk_generate_rays(const float* pose, int H, int W, float fx, float fy, int64_t first, int64_t count, float* rays,
+int nk::sk_generate_rays(const float* pose, int H, int W, float fx, float fy, int64_t first, int64_t count, float* rays,
                      hipStream_t st) {
     Cam c; c.H = H; c.W = W; c.fx = fx; c.fy = fy;
     for (int i = 0; i < 12; ++i) c.pose[i] = pose[i];
@@ -1975,73 +1990,70 @@ int sk_generate_rays(const float* pose, int H, int W, float fx, float fy, int64_
     hipLaunchKernelGGL(raygen_kernel, dim3(blocks_for(count, 256)), dim3(256), 0, st, c, first, count, rays);
     return (int)hipGetLastError();
 }
-int sk_pixel_rays(const float* pose, float fx, float fy, const int64_t* coords, int64_t N, float* rays, hipStream_t st) {
+int nk::sk_pixel_rays(const float* pose, float fx, float fy, const int64_t* coords, int64_t N, float* rays, hipStream_t st) {
     Cam c; c.H = 0; c.W = 0; c.fx = fx; c.fy = fy;
     for (int i = 0; i < 12; ++i) c.pose[i] = pose[i];
     if (N == 0) return 0;
     hipLaunchKernelGGL(pixel_rays_kernel, dim3(blocks_for(N, 256)), dim3(256), 0, st, c, coords, N, rays);
     return (int)hipGetLastError();
 }
-int sk_stratified_points(const float* rays, const float* z_base, const float* u, float jitter, int64_t N, int S, float* z_out,
+int nk::sk_stratified_points(const float* rays, const float* z_base, const float* u, float jitter, int64_t N, int S, float* z_out,
                          float* pts, hipStream_t st) {
     if (N * S == 0) return 0;
     hipLaunchKernelGGL(stratified_points_kernel, dim3(blocks_for(N * S, 256)), dim3(256), 0, st, rays, z_base, u, jitter, N, S, z_out, pts);
     return (int)hipGetLastError();
 }
-int sk_length2pts(const float* rays, const float* z, int64_t N, int S, float* out, hipStream_t st) {
+int nk::sk_length2pts(const float* rays, const float* z, int64_t N, int S, float* out, hipStream_t st) {
     if (N * S == 0) return 0;
     hipLaunchKernelGGL(length2pts_kernel, dim3(blocks_for(N * S * 6, 256)), dim3(256), 0, st, rays, z, N, S, out);
     return (int)hipGetLastError();
 }
-int sk_sigma_to_weights(const float* sigma, const float* z, const float* dirs, int64_t N, int S, int act, float* w, hipStream_t st) {
+int nk::sk_sigma_to_weights(const float* sigma, const float* z, const float* dirs, int64_t N, int S, int act, float* w, hipStream_t st) {
     if (N * S == 0) return 0;
     hipLaunchKernelGGL(sigma_to_weights_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), 0, st, sigma, z, dirs, N, S, act, w);
     return (int)hipGetLastError();
 }
-int sk_max_blur(const float* w, int64_t N, int S, float alpha, float* out, hipStream_t st) {
+int nk::sk_max_blur(const float* w, int64_t N, int S, float alpha, float* out, hipStream_t st) {
     if (N * S == 0) return 0;
     hipLaunchKernelGGL(max_blur_kernel, dim3(blocks_for(N * S, 256)), dim3(256), 0, st, w, N, S, alpha, out);
     return (int)hipGetLastError();
 }
-int sk_inverse_sample(const float* w, const float* z, const float* u, int64_t N, int C, int K, int sort, int mode, float* z_out,
+int nk::sk_inverse_sample(const float* w, const float* z, const float* u, int64_t N, int C, int K, int sort, int mode, float* z_out,
                       int64_t* below, int64_t* above, hipStream_t st) {
     if (N == 0) return 0;
-    const size_t lds = WAVES_PER_BLOCK * ((size_t)3 * C + 2 * K + SORT_LDS_FLOATS) * 4;
-    hipLaunchKernelGGL(inverse_sample_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), lds, st, w, z, u, N, C, K, sort, mode,
+    hipLaunchKernelGGL(inverse_sample_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), sk_inverse_sample_lds_bytes(C, K), st, w, z, u, N, C, K, sort, mode,
                        z_out, below, above);
     return (int)hipGetLastError();
 }
-int sk_resample(const float* density, const float* z, const float* z_base, const float* u_strat, float z_jitter,
+int nk::sk_resample(const float* density, const float* z, const float* z_base, const float* u_strat, float z_jitter,
                 const float* dirs, int dirs_stride, const float* u_inv, int64_t N, int C, int K, int softplus, float alpha,
                 uint64_t rng_seed, int64_t rng_ray_offset, float* z_fine, int64_t* below, float* w_prop, float* z_coarse, hipStream_t st) {
     if (N == 0) return 0;
     ResampleArgs a{density, z, z_base, u_strat, z_jitter, dirs, dirs_stride, u_inv, N, C, K, softplus, alpha, z_fine, below, w_prop, z_coarse,
                    rng_seed, rng_ray_offset};
-    const size_t lds = WAVES_PER_BLOCK * ((size_t)5 * C + 2 * K + SORT_LDS_FLOATS) * 4;
     // persistent over rays: exactly one resident round (RS_BLOCKS_PER_CU workgroups fit a CU by registers and LDS at the render shapes),
     // so that no partially filled last round trails behind
     int64_t blocks = (N + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
     const int64_t resident = (int64_t)nerf_host::cu_count() * RS_BLOCKS_PER_CU;
     if (blocks > resident) blocks = resident;
-    hipLaunchKernelGGL(resample_kernel, dim3((unsigned)blocks), dim3(256), lds, st, a);
+    hipLaunchKernelGGL(resample_kernel, dim3((unsigned)blocks), dim3(256), sk_resample_lds_bytes(C, K), st, a);
     return (int)hipGetLastError();
 }
 // ---- disparity ray spacing (near, far, gn = fp32(1/near), gf = fp32(1/far): validated and rounded by the caller) ----
-int sk_warp_depths(const float* in, const float* rays, int64_t N, int S, int inverse, float near, float far, float gn, float gf, float* out, float* pts,
+int nk::sk_warp_depths(const float* in, const float* rays, int64_t N, int S, int inverse, float near, float far, float gn, float gf, float* out, float* pts,
                    hipStream_t st) {
     if (N * S == 0) return 0;
     hipLaunchKernelGGL(warp_depths_kernel, dim3(blocks_for(N * S, 256)), dim3(256), 0, st, in, rays, N, S, inverse, WarpConsts{near, far, gn, gf}, out, pts);
     return (int)hipGetLastError();
 }
-int sk_warped_stratified(const float* rays, const float* u, int64_t N, int C, uint64_t seed, int64_t ray_offset, float near, float far, float gn, float gf,
+int nk::sk_warped_stratified(const float* rays, const float* u, int64_t N, int C, uint64_t seed, int64_t ray_offset, float near, float far, float gn, float gf,
                          float* s_out, float* z_out, float* pts, hipStream_t st) {
     if (N * C == 0) return 0;
     hipLaunchKernelGGL(warped_stratified_kernel, dim3(blocks_for(N * C, 256)), dim3(256), 0, st, rays, u, N, C, 1.0f / (float)C, seed, ray_offset,
                        WarpConsts{near, far, gn, gf}, s_out, z_out, pts);
     return (int)hipGetLastError();
 }
-size_t sk_warped_resample_lds_bytes(int C, int K) { return WAVES_PER_BLOCK * ((size_t)5 * C + 4 * K + SORT_LDS_FLOATS) * 4; }
-int sk_warped_resample(const float* density, const float* s_c, const float* dirs, int dirs_stride, const float* u_inv, int64_t N, int C, int K, int softplus,
+int nk::sk_warped_resample(const float* density, const float* s_c, const float* dirs, int dirs_stride, const float* u_inv, int64_t N, int C, int K, int softplus,
                        float alpha, float near, float far, float gn, float gf, uint64_t rng_seed, int64_t rng_ray_offset, float* z_fine, float* s_fine,
                        int64_t* below, float* w_prop, hipStream_t st) {
     if (N == 0) return 0;
@@ -2050,7 +2062,7 @@ int sk_warped_resample(const float* density, const float* s_c, const float* dirs
     hipLaunchKernelGGL(warped_resample_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), sk_warped_resample_lds_bytes(C, K), st, a);
     return (int)hipGetLastError();
 }
-int sk_composite(const float* rgbo, const float* z, int z_stride, const float* dirs, int dirs_stride, int64_t N, int S, int flags,
+int nk::sk_composite(const float* rgbo, const float* z, int z_stride, const float* dirs, int dirs_stride, int64_t N, int S, int flags,
                  int act, float sigma_shift, float near, float far, const float* normal, const float* cam_dir, float* rgb, float* weights,
                  float* depth, float* normal_img, hipStream_t st) {
     if (N == 0) return 0;
@@ -2058,15 +2070,14 @@ int sk_composite(const float* rgbo, const float* z, int z_stride, const float* d
     hipLaunchKernelGGL(composite_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
-int sk_get_bounds(const float* w, const int64_t* below, int64_t N, int C, int K, float* bounds, hipStream_t st) {
+int nk::sk_get_bounds(const float* w, const int64_t* below, int64_t N, int C, int K, float* bounds, hipStream_t st) {
     if (N == 0 || K < 2) return 0;
-    const size_t lds = WAVES_PER_BLOCK * ((size_t)C + 1) * 4;
-    hipLaunchKernelGGL(get_bounds_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), lds, st, w, below, N, C, K, bounds);
+    hipLaunchKernelGGL(get_bounds_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), sk_get_bounds_lds_bytes(C), st, w, below, N, C, K, bounds);
     return (int)hipGetLastError();
 }
 
 // ---- backward launchers ----
-int sk_weights_backward(const float* sigma, int sigma_stride, int sigma_off, const float* z, int z_stride, const float* dirs, int dirs_stride,
+int nk::sk_weights_backward(const float* sigma, int sigma_stride, int sigma_off, const float* z, int z_stride, const float* dirs, int dirs_stride,
                         int64_t N, int S, int mul_norm, int act, float sigma_shift, const float* rgbo, const float* d_rgb,
                         const float* d_weights, const float* d_depth, int white_bkg, float near, float far, float* d_sigma,
                         int d_sigma_stride, int d_sigma_off, float* d_rgbo, hipStream_t st) {
@@ -2079,37 +2090,33 @@ int sk_weights_backward(const float* sigma, int sigma_stride, int sigma_off, con
     else hipLaunchKernelGGL(weights_backward_kernel<16>, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
-int sk_max_blur_backward(const float* w, const float* g, int64_t N, int S, float* dw, hipStream_t st) {
+int nk::sk_max_blur_backward(const float* w, const float* g, int64_t N, int S, float* dw, hipStream_t st) {
     if (N * S == 0) return 0;
     hipLaunchKernelGGL(max_blur_backward_kernel, dim3(blocks_for(N * S, 256)), dim3(256), 0, st, w, g, N, S, dw);
     return (int)hipGetLastError();
 }
-int sk_get_bounds_backward(const int64_t* below, const float* g, int64_t N, int C, int K, float* dw, hipStream_t st) {
+int nk::sk_get_bounds_backward(const int64_t* below, const float* g, int64_t N, int C, int K, float* dw, hipStream_t st) {
     if (N == 0) return 0;
     if (K < 2) { return (int)hipMemsetAsync(dw, 0, (size_t)N * C * 4, st); }
-    const size_t lds = WAVES_PER_BLOCK * (size_t)(2 * K) * 4;
-    hipLaunchKernelGGL(get_bounds_backward_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), lds, st, below, g, N, C, K, dw);
+    hipLaunchKernelGGL(get_bounds_backward_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), sk_get_bounds_backward_lds_bytes(K), st, below, g, N, C, K, dw);
     return (int)hipGetLastError();
 }
-int sk_frag_to_rows(const void* frag, int elem_bytes, int64_t n_sub, int n_kg, int64_t M, void* out, hipStream_t st) {
+int nk::sk_frag_to_rows(const void* frag, int elem_bytes, int64_t n_sub, int n_kg, int64_t M, void* out, hipStream_t st) {
     if (n_sub == 0 || M == 0) return 0;
-    const size_t lds = (size_t)WAVES_PER_BLOCK * 32 * ((size_t)n_kg * 16 * elem_bytes + 16);
-    if (elem_bytes == 2) {
-        hipLaunchKernelGGL(frag_to_rows_kernel<2>, dim3(blocks_for(n_sub, WAVES_PER_BLOCK)), dim3(256), lds, st, (const char*)frag, n_sub, n_kg, M, (char*)out, n_kg * 16);
-    } else {
-        if (int e = nerf_host::allow_dynamic_lds(reinterpret_cast<const void*>(frag_to_rows_kernel<4>), 140 * 1024)) return e;
-        hipLaunchKernelGGL(frag_to_rows_kernel<4>, dim3(blocks_for(n_sub, WAVES_PER_BLOCK)), dim3(256), lds, st, (const char*)frag, n_sub, n_kg, M, (char*)out, n_kg * 16);
-    }
+    const size_t lds = WAVES_PER_BLOCK * frag_wave_bytes(n_kg, elem_bytes);
+    const auto kernel = elem_bytes == 2 ? frag_to_rows_kernel<2> : frag_to_rows_kernel<4>;      // (the opt-in below: the fp32 kernel's alone)
+    if (int e = elem_bytes == 2 ? 0 : nerf_host::allow_dynamic_lds(reinterpret_cast<const void*>(kernel), 140 * 1024)) return e;
+    hipLaunchKernelGGL(kernel, dim3(blocks_for(n_sub, WAVES_PER_BLOCK)), dim3(256), lds, st, (const char*)frag, n_sub, n_kg, M, (char*)out, n_kg * 16);
     return (int)hipGetLastError();
 }
-int sk_relu_mask(void* delta, const void* act, int elem_bytes, int64_t n, hipStream_t st) {
+int nk::sk_relu_mask(void* delta, const void* act, int elem_bytes, int64_t n, hipStream_t st) {
     if (n == 0) return 0;
     const int64_t words = elem_bytes == 2 ? n / 2 : n;
     if (elem_bytes == 2) hipLaunchKernelGGL(relu_mask_kernel<2>, dim3(blocks_for(words, 256)), dim3(256), 0, st, (uint32_t*)delta, (const uint32_t*)act, words);
     else hipLaunchKernelGGL(relu_mask_kernel<4>, dim3(blocks_for(words, 256)), dim3(256), 0, st, (uint32_t*)delta, (const uint32_t*)act, words);
     return (int)hipGetLastError();
 }
-int sk_relu_mask_bias(void* delta, const void* act, int elem_bytes, int64_t rows, int cols, float* col_sum, hipStream_t st) {
+int nk::sk_relu_mask_bias(void* delta, const void* act, int elem_bytes, int64_t rows, int cols, float* col_sum, hipStream_t st) {
     if (rows == 0) return 0;
     const int W = cols * elem_bytes / 4;
     if (W < 1 || W > 256 || (256 % W) != 0) return (int)hipErrorInvalidValue;
@@ -2120,32 +2127,30 @@ int sk_relu_mask_bias(void* delta, const void* act, int elem_bytes, int64_t rows
     else hipLaunchKernelGGL(relu_mask_bias_kernel<4>, dim3((int)blocks), dim3(256), 0, st, (uint32_t*)delta, (const uint32_t*)act, rows, W, col_sum);
     return (int)hipGetLastError();
 }
-int sk_merge_sorted(const float* a, const float* b, int64_t N, int K, int C, float* out, hipStream_t st) {
+int nk::sk_merge_sorted(const float* a, const float* b, int64_t N, int K, int C, float* out, hipStream_t st) {
     if (N == 0) return 0;
-    const size_t lds = WAVES_PER_BLOCK * (size_t)(K + C) * 2 * 4;
-    hipLaunchKernelGGL(merge_sorted_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), lds, st, a, b, N, K, C, out);
+    hipLaunchKernelGGL(merge_sorted_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), sk_merge_sorted_lds_bytes(K, C, 0), st, a, b, N, K, C, out);
     return (int)hipGetLastError();
 }
-int sk_merge_sorted_order(const float* a, const float* b, const int64_t* f_inds, int64_t N, int K, int C, float* out, int64_t* order, int64_t* all_inds,
+int nk::sk_merge_sorted_order(const float* a, const float* b, const int64_t* f_inds, int64_t N, int K, int C, float* out, int64_t* order, int64_t* all_inds,
                           hipStream_t st) {
     if (N == 0) return 0;
-    const size_t lds = WAVES_PER_BLOCK * (size_t)(K + C) * 4 * 4;
-    hipLaunchKernelGGL(merge_sorted_order_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), lds, st, a, b, f_inds, N, K, C, out, order, all_inds);
+    hipLaunchKernelGGL(merge_sorted_order_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), sk_merge_sorted_lds_bytes(K, C, 1), st, a, b, f_inds, N, K, C, out, order, all_inds);
     return (int)hipGetLastError();
 }
-int sk_coarse_grad_select(const float* grads, const int64_t* sort_inds, int64_t N, int T, int D, int c_pnum, float* out, hipStream_t st) {
+int nk::sk_coarse_grad_select(const float* grads, const int64_t* sort_inds, int64_t N, int T, int D, int c_pnum, float* out, hipStream_t st) {
     if (N == 0 || c_pnum == 0 || D == 0) return 0;
     hipLaunchKernelGGL(coarse_grad_select_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), 0, st, grads, sort_inds, N, T, D, c_pnum, out);
     return (int)hipGetLastError();
 }
-int sk_weighted_dot_loss(const float* w, const float* a, const float* b, int64_t M, int mode, float scale, float* out, float* workspace, hipStream_t st) {
+int nk::sk_weighted_dot_loss(const float* w, const float* a, const float* b, int64_t M, int mode, float scale, float* out, float* workspace, hipStream_t st) {
     int64_t nb = (M + 255) / 256;
     const int blocks = (int)(nb > LOSS_BLOCKS ? LOSS_BLOCKS : (nb < 1 ? 1 : nb));
     hipLaunchKernelGGL(weighted_dot_loss_kernel, dim3(blocks), dim3(256), 64, st, w, a, b, M, mode, workspace);
     hipLaunchKernelGGL(weighted_dot_loss_final_kernel, dim3(1), dim3(256), 64, st, workspace, blocks, scale, out);
     return (int)hipGetLastError();
 }
-int sk_weighted_dot_loss_backward(const float* g, const float* w, const float* a, const float* b, int64_t M, int mode, float scale, float* d_w, float* d_a,
+int nk::sk_weighted_dot_loss_backward(const float* g, const float* w, const float* a, const float* b, int64_t M, int mode, float scale, float* d_w, float* d_a,
                                   float* d_b, hipStream_t st) {
     if (M == 0) return 0;
     hipLaunchKernelGGL(weighted_dot_loss_backward_kernel, dim3(blocks_for(M, 256)), dim3(256), 0, st, g, w, a, b, M, mode, scale, d_w, d_a, d_b);
@@ -2153,11 +2158,11 @@ int sk_weighted_dot_loss_backward(const float* g, const float* w, const float* a
 }
 // S <= 1024 (checked by the C-ABI): the rows take <= WAVES_PER_BLOCK x 24 x 1023 B = 96 KiB of LDS (mode 0 backward; above the default
 // dynamic limit from S = 684 on), the other kernels <= 32 KiB
-int sk_distortion_loss(const float* w, const float* t, int64_t N, int S, int mode, float scale, float* out, float* workspace, hipStream_t st) {
+int nk::sk_distortion_loss(const float* w, const float* t, int64_t N, int S, int mode, float scale, float* out, float* workspace, hipStream_t st) {
     const int M = S - 1;
     int64_t nb = (N + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
     const int blocks = (int)(nb > DIST_BLOCKS ? DIST_BLOCKS : (nb < 1 ? 1 : nb));
-    size_t lds = (size_t)WAVES_PER_BLOCK * 2 * M * 4;
+    size_t lds = wave_rows_bytes(dist_wave_floats(2, M));
     if (lds < 64) lds = 64;                                                                  // (the block reduction's 4 x 2 doubles)
     double* partial = reinterpret_cast<double*>(workspace);
     if (mode == 0) hipLaunchKernelGGL(distortion_loss_kernel<0>, dim3(blocks), dim3(256), lds, st, w, t, N, S, partial);
@@ -2165,10 +2170,10 @@ int sk_distortion_loss(const float* w, const float* t, int64_t N, int S, int mod
     hipLaunchKernelGGL(distortion_loss_final_kernel, dim3(1), dim3(256), 64, st, partial, blocks, N, M, mode, scale, out);
     return (int)hipGetLastError();
 }
-int sk_distortion_loss_backward(const float* w, const float* t, int64_t N, int S, int mode, float scale, const float* g, float* d_w, float* d_t,
+int nk::sk_distortion_loss_backward(const float* w, const float* t, int64_t N, int S, int mode, float scale, const float* g, float* d_w, float* d_t,
                                 hipStream_t st) {
     if (N == 0 || (!d_w && !d_t)) return 0;
-    const size_t lds = (size_t)WAVES_PER_BLOCK * (mode == 0 ? 6 : 2) * (S - 1) * 4;
+    const size_t lds = wave_rows_bytes(dist_wave_floats(mode == 0 ? 6 : 2, S - 1));
     const dim3 grid(blocks_for(N, WAVES_PER_BLOCK)), block(256);
     if (mode == 0 && lds > 64 * 1024)
         if (int e = nerf_host::allow_dynamic_lds(reinterpret_cast<const void*>(distortion_loss_backward_kernel<0>), lds)) return e;
@@ -2177,7 +2182,7 @@ int sk_distortion_loss_backward(const float* w, const float* t, int64_t N, int S
     return (int)hipGetLastError();
 }
 // 1 <= M, K <= 1024 (checked by the C-ABI): four waves x <= 16 KiB or two waves x <= 24.6 KB of rows, always within the default 64 KiB
-int sk_interlevel_loss(const float* w, const float* t, const float* w_prop, const float* t_prop, int64_t N, int M, int K, int Kp, float scale, float* out,
+int nk::sk_interlevel_loss(const float* w, const float* t, const float* w_prop, const float* t_prop, int64_t N, int M, int K, int Kp, float scale, float* out,
                        float* bounds_out, float* workspace, hipStream_t st) {
     const int waves = il_waves(M, K, false);
     int64_t nb = (N + waves - 1) / waves;
@@ -2189,7 +2194,7 @@ int sk_interlevel_loss(const float* w, const float* t, const float* w_prop, cons
     hipLaunchKernelGGL(interlevel_loss_final_kernel, dim3(1), dim3(256), 64, st, partial, blocks, scale, out);
     return (int)hipGetLastError();
 }
-int sk_interlevel_loss_backward(const float* w, const float* t, const float* w_prop, const float* t_prop, int64_t N, int M, int K, int Kp, float scale,
+int nk::sk_interlevel_loss_backward(const float* w, const float* t, const float* w_prop, const float* t_prop, int64_t N, int M, int K, int Kp, float scale,
                                 const float* g, float* d_w_prop, hipStream_t st) {
     if (N == 0) return 0;
     const int waves = il_waves(M, K, true);
@@ -2197,7 +2202,7 @@ int sk_interlevel_loss_backward(const float* w, const float* t, const float* w_p
                        w_prop, t_prop, N, M, K, Kp, scale, g, d_w_prop);
     return (int)hipGetLastError();
 }
-int sk_encode_rows(const float* x, int x_stride, int64_t M, int L, int normalize, int elem_bytes, void* out, hipStream_t st) {
+int nk::sk_encode_rows(const float* x, int x_stride, int64_t M, int L, int normalize, int elem_bytes, void* out, hipStream_t st) {
     if (M == 0) return 0;
     const dim3 grid(blocks_for(M, 256)), block(256);
     char* o = (char*)out;
@@ -2208,16 +2213,13 @@ int sk_encode_rows(const float* x, int x_stride, int64_t M, int L, int normalize
     else return (int)hipErrorInvalidValue;
     return (int)hipGetLastError();
 }
-int sk_frag_rows_mask_blocks() { return 512; }                   // partial rows = blocks * WAVES_PER_BLOCK
-int sk_frag_rows_mask(const void* frag, int elem_bytes, int64_t n_sub, int n_kg, int64_t M, void* act_out, void* delta, float* col_sum, hipStream_t st) {
-    const size_t lds = (size_t)WAVES_PER_BLOCK * 32 * ((size_t)n_kg * 16 * elem_bytes + 16);
+int nk::sk_frag_rows_mask_blocks() { return 512; }                   // partial rows = blocks * WAVES_PER_BLOCK
+int nk::sk_frag_rows_mask(const void* frag, int elem_bytes, int64_t n_sub, int n_kg, int64_t M, void* act_out, void* delta, float* col_sum, hipStream_t st) {
+    const size_t lds = WAVES_PER_BLOCK * frag_wave_bytes(n_kg, elem_bytes);
     const dim3 grid(sk_frag_rows_mask_blocks()), block(256);     // fixed grid: every wavefront writes its partial row (zeros without work)
-    if (elem_bytes == 2) {
-        hipLaunchKernelGGL(frag_rows_mask_kernel<2>, grid, block, lds, st, (const char*)frag, n_sub, n_kg, M, (char*)act_out, (char*)delta, col_sum);
-    } else {
-        if (int e = nerf_host::allow_dynamic_lds(reinterpret_cast<const void*>(frag_rows_mask_kernel<4>), 140 * 1024)) return e;
-        hipLaunchKernelGGL(frag_rows_mask_kernel<4>, grid, block, lds, st, (const char*)frag, n_sub, n_kg, M, (char*)act_out, (char*)delta, col_sum);
-    }
+    const auto kernel = elem_bytes == 2 ? frag_rows_mask_kernel<2> : frag_rows_mask_kernel<4>;  // (the opt-in below: the fp32 kernel's alone)
+    if (int e = elem_bytes == 2 ? 0 : nerf_host::allow_dynamic_lds(reinterpret_cast<const void*>(kernel), 140 * 1024)) return e;
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, (const char*)frag, n_sub, n_kg, M, (char*)act_out, (char*)delta, col_sum);
     return (int)hipGetLastError();
 }
 

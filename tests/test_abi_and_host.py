@@ -409,3 +409,84 @@ def test_nerf_shim_package_serves_every_name_the_entry_scripts_import(golden):
     r = subprocess.run([sys.executable, "-c", code, os.path.join(root, "tests", "golden", "g23_entry_imports.json"), compat],
                        capture_output=True, text=True, env=env, timeout=300)
     assert r.returncode == 0 and "resolved" in r.stdout, r.stderr[-2000:]
+
+
+def _ws256(b):
+    return (b + 255) // 256 * 256
+
+
+# the closed forms of the three render workspaces, as the C-ABI documented them before their layouts were described once
+_WORKSPACE_FORMS = {
+    # density (N,64) | z_fine (N, n_fine+1) | rgbo (N, n_fine, 4) | rays (N, 6), + alignment slack + one scalar slot
+    "nerf_amd_render_workspace_bytes": lambda N, F: _ws256(N * 64 * 4) + _ws256(N * (F + 1) * 4) + _ws256(N * F * 16) + _ws256(N * 24) + 512,
+    # density | s_c | z_c (N,64 each) | z_fine | rgbo | raw depth (N) | rays, + the same 512
+    "nerf_amd_render_warped_workspace_bytes": lambda N, F: (3 * _ws256(N * 64 * 4) + _ws256(N * (F + 1) * 4) + _ws256(N * F * 16) + _ws256(N * 4)
+                                                            + _ws256(N * 24) + 512),
+    # density | z_fine | z_coarse (N,64) | z_all (N, n_fine+64) | rgbo (.., 4) | normals (.., 3), then the unrounded ray table + alignment slack
+    "nerf_amd_render_ref_workspace_bytes": lambda N, F: (2 * _ws256(N * 64 * 4) + _ws256(N * (F + 1) * 4) + _ws256(N * (F + 64) * 4)
+                                                         + _ws256(N * (F + 64) * 16) + _ws256(N * (F + 64) * 12) + N * 24 + 256),
+}
+
+
+def test_render_workspace_sizes_are_the_documented_closed_forms():
+    """The three *_workspace_bytes functions against their closed forms AND against the table recorded from the build before the layouts
+    were described once (tests/golden/render_workspace_bytes.json): byte for byte, the + 512 of the plain and warped entries, the
+    unrounded N * 24 + 256 tail of the Ref entry and the 0 for N < 0 or n_fine < 1 included."""
+    import json
+    from nerf_amd import _lib
+    table = json.load(open(os.path.join(ROOT, "tests", "golden", "render_workspace_bytes.json")))
+    n_checked = 0
+    for name, form in _WORKSPACE_FORMS.items():
+        for N in (-1, 0, 1, 7, 1000, 640000):
+            for F in (0, 1, 128, 1023):
+                want = 0 if N < 0 or F < 1 else form(N, F)
+                assert table[name]["%d,%d" % (N, F)] == want, (name, N, F)
+                assert getattr(_lib.lib, name)(N, F) == want, (name, N, F)
+                n_checked += 1
+    assert n_checked == 72 and sum(len(t) for t in table.values()) == 72
+
+
+def test_shapes_whose_launch_exceeds_the_lds_are_refused_before_any_hip_call():
+    """A shape is accepted only if the dynamic LDS of the launch it leads to fits the 64 KiB a kernel gets without an opt-in: four rays
+    per workgroup x the kernel's per-ray rows.  nerf_amd_resample holds 5 C + 2 K + 1280 floats per ray (5 C + 2 K <= 2816),
+    nerf_amd_get_bounds C + 1.  The refusal names LDS; the largest accepted neighbour passes on to the NULL-argument check."""
+    from nerf_amd import _lib
+    lib = _lib.lib
+    p = ctypes.c_void_p(256)                                   # non-NULL, never dereferenced: every call below fails first
+
+    def resample(C, K, density=p):
+        return lib.nerf_amd_resample(density, None, p, None, 0.1, p, 6, None, 4, C, K, 0, 0.01, 0, 0, p, None, None, None, None)
+
+    def get_bounds(C, w=p):
+        return lib.nerf_amd_get_bounds(w, p, 4, C, 8, p, None)
+
+    for C, K in ((256, 768), (255, 770), (200, 908), (154, 1023), (153, 1024), (64, 1024)):          # the largest K for each C
+        assert 4 * 4 * (5 * C + 2 * K + 1280) <= 65536 and (K == 1024 or 4 * 4 * (5 * C + 2 * (K + 1) + 1280) > 65536)
+        assert resample(C, K, density=None) == -1 and b"NULL argument" in lib.nerf_amd_last_error(), (C, K)
+    for C, K in ((256, 1024), (256, 769), (255, 771), (200, 909), (154, 1024)):
+        assert 4 * 4 * (5 * C + 2 * K + 1280) > 65536
+        assert resample(C, K) == -1 and b"LDS" in lib.nerf_amd_last_error(), (C, K)
+        assert resample(C, K, density=None) == -1 and b"LDS" in lib.nerf_amd_last_error(), (C, K)   # before the pointers are looked at
+    assert resample(257, 8) == -1 and b"need 3 <= C <= 256" in lib.nerf_amd_last_error()               # the range message is unchanged
+    assert get_bounds(4096) == -1 and b"LDS" in lib.nerf_amd_last_error()
+    assert get_bounds(4095, w=None) == -1 and b"NULL argument" in lib.nerf_amd_last_error()
+    assert get_bounds(4097) == -1 and b"bad size" in lib.nerf_amd_last_error()
+    # the other launchers' limits follow from their layouts and did not move
+    assert lib.nerf_amd_inverse_sample(None, p, p, 4, 256, 1024, 1, p, None, None) == -1 and b"NULL argument" in lib.nerf_amd_last_error()
+    assert lib.nerf_amd_warped_resample(None, p, p, 6, p, 4, 256, 384, 0, 0.01, _lib.SPACING_DISPARITY, 2.0, 6.0, 0, 0, p, None, None, None, None) == -1
+    assert b"NULL argument" in lib.nerf_amd_last_error()
+    assert lib.nerf_amd_warped_resample(p, p, p, 6, p, 4, 256, 385, 0, 0.01, _lib.SPACING_DISPARITY, 2.0, 6.0, 0, 0, p, None, None, None, None) == -1
+    assert b"LDS" in lib.nerf_amd_last_error()
+    assert lib.nerf_amd_merge_depths(None, p, 4, 1984, 64, p, None) == -1 and b"NULL argument" in lib.nerf_amd_last_error()
+    assert lib.nerf_amd_merge_depths(p, p, 4, 1985, 64, p, None) == -1 and b"K + C <= 2048" in lib.nerf_amd_last_error()
+    assert lib.nerf_amd_merge_depths_order(None, p, None, 4, 960, 64, p, p, None, None) == -1 and b"NULL argument" in lib.nerf_amd_last_error()
+    assert lib.nerf_amd_merge_depths_order(p, p, None, 4, 961, 64, p, p, None, None) == -1 and b"K + C <= 1024" in lib.nerf_amd_last_error()
+    assert lib.nerf_amd_get_bounds_backward(None, p, 4, 4096, 2048, p, None) == -1 and b"NULL argument" in lib.nerf_amd_last_error()
+    assert lib.nerf_amd_get_bounds_backward(p, p, 4, 4096, 2049, p, None) == -1 and b"K <= 2048" in lib.nerf_amd_last_error()
+    # sizes whose row length wraps a 32-bit int to something small (K + C = 2^30: 4 (K + C) floats = 0 mod 2^32) are refused like any other
+    # oversize shape: the checks compute in size_t
+    for K, C in ((2 ** 30 - 64, 64), (2 ** 30 + 448, 64), (2 ** 29, 2 ** 29), (2 ** 31 - 65, 64), (64, 2 ** 31 - 65), (2 ** 31 - 1, 2 ** 31 - 1)):
+        assert lib.nerf_amd_merge_depths(p, p, 4, K, C, p, None) == -1 and b"K + C <= 2048" in lib.nerf_amd_last_error(), (K, C)
+        assert lib.nerf_amd_merge_depths_order(p, p, None, 4, K, C, p, p, None, None) == -1 and b"K + C <= 1024" in lib.nerf_amd_last_error(), (K, C)
+    for K in (2 ** 30, 2 ** 30 + 1024, 2 ** 31 - 1):
+        assert lib.nerf_amd_get_bounds_backward(p, p, 4, 64, K, p, None) == -1 and b"K <= 2048" in lib.nerf_amd_last_error(), K

@@ -3173,3 +3173,104 @@ def test_render_image_with_a_wide_network(A):
         res2 = A.procedures.render_image(mip, prop, pose.cuda(), 50, focal, NEAR, FAR, 32, white_bkg=True)
     assert torch.isfinite(res2["rgb"]).all() and float(res2["rgb"].min()) >= 0.0 and float(res2["rgb"].max()) <= 1.0 + 1e-5
     assert abs(float(res2["rgb"].mean()) - float(want["rgb"].mean())) <= 0.05        # (other uniforms: the same image up to sampling noise)
+
+
+# ------------------------------------------------------------------------------------------------ the largest shapes the row kernels accept
+# Each of these kernels keeps a ray's rows in dynamic LDS, four rays (wavefronts) per workgroup; the launcher's size and the kernel's
+# carve-up come from one layout function.  At the largest accepted shape the launch takes the whole 64 KiB, and nine rays are two full
+# workgroups plus a ragged one: a size that disagrees with the carve-up, or a wrong stride between the waves, shows here and nowhere
+# smaller.  References and tolerances are those of each op's own test above.
+LDS_RAYS = 9
+
+
+@pytest.mark.parametrize("sort", [True, False])
+def test_inverse_sampling_at_the_largest_accepted_shape(A, sort):
+    C, K = 256, 1024                                          # 4 x (3 C + 2 K + 1280) floats = 64 KiB
+    gen = torch.Generator().manual_seed(4100 + sort)
+    w = torch.rand(LDS_RAYS, C, generator=gen) ** 3 + 0.01
+    z = torch.sort(NEAR + (FAR - NEAR) * torch.rand(LDS_RAYS, C, generator=gen), dim=-1)[0]
+    u = torch.rand(LDS_RAYS, K, generator=gen)
+    if sort:
+        want_z, want_b = O.inverse_sample(w, z, u, sort=True)
+        got_z, got_b = A.ops.inverse_sample(dev(w), dev(z), dev(u), True)
+        assert torch.equal(got_b.cpu(), want_b)
+        assert bool((got_z[:, 1:] >= got_z[:, :-1]).all())
+    else:
+        want_z = O.inverse_sample(w, z, u, sort=False)
+        got_z, got_b = A.ops.inverse_sample(dev(w), dev(z), dev(u), False)
+        mids = 0.5 * (z[..., 1:] + z[..., :-1])
+        assert torch.equal(got_b.cpu(), O.sample_pdf(mids, w[..., 1:-1], u)[1])
+    assert max_abs(got_z.cpu(), want_z) <= 2e-6
+
+
+def test_resample_at_the_largest_accepted_shape(A):
+    """C = 256 coarse depths given explicitly, K = 768 explicit uniforms (5 C + 2 K + 1280 floats per ray: 64 KiB for four rays)."""
+    C, K = 256, 768
+    gen = torch.Generator().manual_seed(4200)
+    rays = torch.cat((torch.zeros(LDS_RAYS, 3), torch.randn(LDS_RAYS, 3, generator=gen)), -1).contiguous()
+    z = torch.sort(NEAR + (FAR - NEAR) * torch.rand(LDS_RAYS, C, generator=gen), dim=-1)[0]
+    dens = torch.randn(LDS_RAYS, C, generator=gen) * 2.0
+    u = torch.rand(LDS_RAYS, K, generator=gen)
+    z_f, below, w_prop, _ = A.ops.resample(dev(dens), dev(z), None, None, 0.0, dev(rays), dev(u), K, want_below=True, want_w=True)
+    w_want = O.max_blur(O.sigma_to_weights(dens, z, rays[:, 3:]), 0.01)
+    assert max_abs(w_prop.cpu(), w_want) <= 1e-5
+    z_want, _ = O.inverse_sample(w_want, z, u, sort=True)
+    assert max_abs(z_f.cpu(), z_want) <= 2e-5
+    assert bool((z_f[:, 1:] >= z_f[:, :-1]).all())
+    _, below_same = O.inverse_sample(w_prop.cpu(), z, u, sort=True)      # index work on identical inputs: exact
+    assert torch.equal(below.cpu(), below_same)
+
+
+def test_merge_depths_at_the_largest_accepted_shape():
+    from nerf_amd import ops
+    g = torch.Generator().manual_seed(4300)
+    K, C = 1984, 64                                           # K + C = 2048: 4 x 2 x 2048 floats = 64 KiB
+    a = torch.sort(torch.rand(LDS_RAYS, K, generator=g) * 4 + 2, dim=-1)[0]
+    b = torch.sort(torch.rand(LDS_RAYS, C, generator=g) * 4 + 2, dim=-1)[0]
+    b[:, 1] = a[:, 2]                                         # ties across the two sets
+    b = torch.sort(b, dim=-1)[0]
+    b[4:] = b[4:].flip(-1)                                    # rays 4..8 take the sorting path (its K + C floats of scratch)
+    a, b = a.cuda(), b.cuda()
+    want = torch.sort(torch.cat((a, b), dim=-1), dim=-1)[0][:, :-1]
+    assert torch.equal(ops.merge_depths(a, b), want)
+
+
+def test_merge_depths_order_at_the_largest_accepted_shape():
+    from nerf_amd import ops
+    g = torch.Generator().manual_seed(4400)
+    K, C = 960, 64                                            # K + C = 1024: 4 x 4 x 1024 floats = 64 KiB
+    a = torch.sort(torch.rand(LDS_RAYS, K, generator=g) * 4 + 2, dim=-1)[0]
+    b = torch.sort(torch.rand(LDS_RAYS, C, generator=g) * 4 + 2, dim=-1)[0]
+    b[:, 1] = a[:, 2]
+    b = torch.sort(b, dim=-1)[0]
+    b[4:] = b[4:].flip(-1)
+    f_inds = torch.randint(0, C, (LDS_RAYS, K), generator=g)
+    a, b, f_inds = a.cuda(), b.cuda(), f_inds.cuda()
+    wz, wo = torch.sort(torch.cat((a, b), dim=-1), dim=-1, stable=True)
+    wi = torch.gather(torch.cat((f_inds, torch.arange(C, device="cuda").expand(LDS_RAYS, -1)), dim=-1), -1, wo)
+    z, order, all_inds = ops.merge_depths_order(a, b, f_inds)
+    assert torch.equal(z, wz[:, :-1]) and torch.equal(order, wo) and torch.equal(all_inds, wi)
+
+
+def test_get_bounds_at_the_largest_accepted_shape(A):
+    """C = 4095 (C + 1 floats per ray: 64 KiB for four rays).  The weights are multiples of 2^-15 whose row sums stay below 1, so every
+    prefix sum is exact in fp32 in any order: a wrong row or index is off by at least 2^-15, three times the tolerance."""
+    C, K = 4095, 129
+    gen = torch.Generator().manual_seed(4500)
+    w = torch.randint(0, 8, (LDS_RAYS, C), generator=gen).float() * 2.0 ** -15
+    below = torch.sort(torch.randint(0, C, (LDS_RAYS, K), generator=gen), dim=-1)[0]
+    below[:, -1] = C - 1                                      # the last prefix-sum entry, sat[C]
+    got = A.ops.get_bounds(dev(w), dev(below)).cpu()
+    assert max_abs(got, O.get_bounds(w, below)) <= 1e-5
+
+
+def test_get_bounds_backward_at_the_largest_accepted_shape(A):
+    import torch_spec as ab
+    C, K = 64, 2048                                           # 2 K words per ray: 64 KiB for four rays
+    gen = torch.Generator().manual_seed(4600)
+    w = torch.rand(LDS_RAYS, C, generator=gen).cuda()
+    gb = torch.randn(LDS_RAYS, K - 1, generator=gen).cuda()
+    for below in (torch.sort(torch.randint(0, C - 2, (LDS_RAYS, K), generator=gen), dim=-1)[0].cuda(),
+                  torch.randint(0, C - 2, (LDS_RAYS, K), generator=gen).cuda()):
+        want, = _vjp(lambda x: ab.bounds_expr(x, below), gb, w)
+        assert max_abs(A.ops.get_bounds_backward(below, gb, C).cpu(), want.cpu()) <= 2e-5 * max(1.0, want.abs().max().item())

@@ -509,3 +509,28 @@ def test_parameter_gradients_with_disparity_depths():
         hip_err = (have[k].detach().cpu().double() - exact[k]).abs().max().item() / top
         ref_err = (ref32[k].double() - exact[k]).abs().max().item() / top
         gate("disparity step: d/d %s vs fp64 (of the largest entry; fp32 spec %.1e)" % (k, ref_err), hip_err, max(2.0 * ref_err, 2e-5))
+
+
+def test_warped_resample_at_the_largest_accepted_shape():
+    """C = 256, K = 384: 5 C + 4 K + 1280 floats per ray, 64 KiB of dynamic LDS for a workgroup's four rays -- the launch size and the
+    kernel's carve-up come from one layout function, and nine rays are two full workgroups plus a ragged one.  Same references as
+    test_warped_resample_equals_the_chain_of_ops_and_the_spec."""
+    from nerf_amd import ops
+    near, far, C, K, n = 2.0, 6.0, 256, 384, 9
+    rays, g = _rays(n, 356)
+    s_c = R.coarse_s(torch.rand(n, C, generator=g)).contiguous()
+    density = torch.randn(n, C, generator=g) * 2.0
+    u = torch.rand(n, K, generator=g)
+    u[3] = 0.5 + torch.rand(K, generator=g) / 300.0           # ray 3: the rank-sort fallback
+    Rc, Sc, Dc, Uc = rays.cuda(), s_c.cuda(), density.cuda(), u.cuda()
+    z_f, s_f, below, w_prop = ops.warped_resample(Dc, Sc, Rc, Uc, near, far)
+    z_c = ops.warp_depths(Sc, near, far)[0]
+    w = ops.max_blur(ops.sigma_to_weights(Dc, z_c, Rc[:, 3:].contiguous(), ops.ACT_RELU), 0.01)
+    s_chain, below_chain = ops.inverse_sample(w, Sc, Uc, sort=True)
+    z_chain = ops.warp_depths(s_chain, near, far)[0]
+    assert _same_bits(w_prop, w) and _same_bits(s_f, s_chain) and torch.equal(below, below_chain) and _same_bits(z_f, z_chain)
+    assert bool((s_f[:, 1:] >= s_f[:, :-1]).all())
+    w_spec = R.proposal_weights(density, s_c, rays[:, 3:], near, far, softplus=False)
+    s_spec, below_spec, _ = R.resample(w_spec, s_c, u, near, far)
+    gate("warped_resample s_fine vs CPU spec at C=256 K=384", max_abs(s_f.cpu(), s_spec), 5e-6)
+    gate("warped_resample share of differing below at C=256 K=384", float((below.cpu() != below_spec).float().mean()), 0.01)
