@@ -8,8 +8,10 @@ THE BLOB.  `unpack` inverts the fragment stream from the description in mlp_layo
 (feature-block pairs interleaved kg-major, an odd trailing block in plain kg order), element (lane, e) of fragment (fb, kg) = W[32 fb +
 (lane & 31)][column(kg, lane >> 5, e)], stored [lane][e] in bf16 and [e >> 2][lane][e & 3] in fp32; the column is dmap_feature for hidden
 inputs and pe_slot_column for encoded inputs; the bias table follows the stream, the fp32 fold (MipNeRF) the bias table.  The layout
-tables are a parameter (LAYOUTS): the same code reads PropLayout, MipLayout, PropLayout128 and MipLayout128.  `pack` is the same
-description written the other way round, fragment by fragment, for the host test.
+tables are a parameter (LAYOUTS): the same code reads PropLayout, MipLayout, PropLayout128, MipLayout128 and RefLayout ('ref': 18
+layers, the segment kind 'ide' = ide_slot_column for the 39 computed directional inputs, layer H = [bottle_neck ; the 11 head rows], the
+(9, 19) IDE coefficient table behind the bias table; its stages and element-wise references live in tests/ref_forward_ref.py).  `pack` is
+the same description written the other way round, fragment by fragment, for the host test.
 
 THE LAYERS.  Every stage is compared AGAINST ITS OWN INPUTS: layer L from the dumped slot L - 1 (or the dumped encoding slot) and the
 operands the blob holds.  With u = 2^-24, K = 16 NKG slots, s = in . W^T + b and A = |in| . |W|^T + |b| in fp64:
@@ -54,9 +56,10 @@ class Layout:
     matrix, its K segments (kind 'pe' | 'd', K groups, first reference column, PE levels, valid width) and the master tensor it packs
     (an index into the state_dict order, or 'fold' = [Wf | rgb_layer.0[:, 256:]] with the folded bias)."""
 
-    def __init__(self, name, nkg, nfb, start, bias_off, n_frags, n_bias, rows, in_f, src, segs, used_frags=None, fold=False):
+    def __init__(self, name, nkg, nfb, start, bias_off, n_frags, n_bias, rows, in_f, src, segs, used_frags=None, fold=False, n_ide=0):
         self.name, self.NKG, self.NFB, self.START, self.BIAS_OFF = name, nkg, nfb, start, bias_off
         self.N_FRAGS, self.N_BIAS, self.rows, self.in_f, self.src, self.fold = n_frags, n_bias, rows, in_f, src, fold
+        self.N_IDE = n_ide                                                  # floats of the IDE coefficient table behind the bias table (RefLayout)
         self.USED_FRAGS = n_frags if used_frags is None else used_frags
         self.N_LAYERS = len(nkg)
         self.segs = [segs.get(l, [("d", nkg[l], 0, 0, in_f[l])]) for l in range(self.N_LAYERS)]
@@ -65,10 +68,12 @@ class Layout:
         return self.N_FRAGS * (1024 if prec == "bf16" else 2048)
 
     def packed_bytes(self, prec):
-        return self.stream_bytes(prec) + 4 * self.N_BIAS + ((128 * 256 + 128) * 4 if self.fold else 0)
+        return self.stream_bytes(prec) + 4 * (self.N_BIAS + self.N_IDE) + ((128 * 256 + 128) * 4 if self.fold else 0)
 
 
 _PE10 = ("pe", 4, 0, 10, 63)
+_DIR_IN = [("d", 8, 0, 0, 128), ("ide", 3, 128, 0, 39)]            # [bottle_neck 128 | IDE real 19 | IDE imag 19 | n.d]
+IDE_ROWS, IDE_TERMS = 9, 19                                       # the (9, 19) coefficient table; RefLayout pads it to N_IDE = 176 floats
 LAYOUTS = {
     "prop": Layout("prop", (4, 16, 16, 16, 16), (8, 8, 8, 8, 1), (0, 32, 160, 288, 416), (0, 256, 512, 768, 1024), 432, 1056,
                    (256, 256, 256, 256, 1), (63, 256, 256, 256, 256), (0, 1, 2, 3, 4), {0: [_PE10]}),
@@ -85,6 +90,15 @@ LAYOUTS = {
                      (128, 128, 128, 128, 128, 128, 256, 1, 128, 3), (63, 128, 128, 128, 191, 128, 128, 256, 283, 128),
                      (0, 1, 2, 3, 4, 5, 6, 8, "fold", 10),
                      {0: [_PE10], 4: [_PE10, ("d", 8, 63, 0, 128)], 8: [("d", 16, 0, 0, 256), ("pe", 2, 256, 4, 27)]}, fold=True),
+    # RefLayout:      S0  S1  S2  S3  S4  S5  S6  S7  H   D0  D1  D2  D3  D4  D5  D6  D7  R
+    # src = index into the 20 tensors pack_ref takes (spatial 0..7, bottle_neck 8, heads (11, 256) 9, directional 10..17, spec head 18,
+    # IDE table 19); 'H' = [bottle_neck 128 rows ; the 11 head rows: normal 0-2, roughness 3, diffuse 4-6, density 7, tint 8-10]
+    "ref": Layout("ref", (4, 16, 16, 16, 20, 16, 16, 16, 16, 11, 16, 16, 16, 27, 16, 16, 16, 16), (8, 8, 8, 8, 8, 8, 8, 8, 5, 8, 8, 8, 8, 8, 8, 8, 8, 1),
+                  (0, 32, 160, 288, 416, 576, 704, 832, 960, 1040, 1128, 1256, 1384, 1512, 1728, 1856, 1984, 2112),
+                  (0, 256, 512, 768, 1024, 1280, 1536, 1792, 2048, 2208, 2464, 2720, 2976, 3232, 3488, 3744, 4000, 4256), 2128, 4288,
+                  (256,) * 8 + (139,) + (256,) * 8 + (3,), (63, 256, 256, 256, 319, 256, 256, 256, 256, 167, 256, 256, 256, 423, 256, 256, 256, 256),
+                  (0, 1, 2, 3, 4, 5, 6, 7, "H", 10, 11, 12, 13, 14, 15, 16, 17, 18),
+                  {0: [_PE10], 4: [_PE10, ("d", 16, 63, 0, 256)], 9: _DIR_IN, 13: _DIR_IN + [("d", 16, 167, 0, 256)]}, n_ide=176),
 }
 
 
@@ -99,11 +113,18 @@ def consumption_order(nfb, nkg):
     return order
 
 
+def ide_slot_column(q, h):
+    """column (relative to the 39 computed directional inputs [real 19 | imag 19 | n.d]) that IDE slot (q, h) holds, or -1 (mlp_layout.h)"""
+    if q < IDE_TERMS:
+        return (IDE_TERMS if h else 0) + q
+    return 38 if (q == IDE_TERMS and not h) else -1
+
+
 def slot_column(segs, kg, h, e):
     """reference column of K slot (kg, h, e) of a layer, or -1 for zero padding"""
     for kind, n, col0, L, width in segs:
         if kg < n:
-            c = R.pe_slot_column(8 * kg + e, h, L) if kind == "pe" else R.dmap_feature(kg, h, e)
+            c = R.pe_slot_column(8 * kg + e, h, L) if kind == "pe" else (ide_slot_column(8 * kg + e, h) if kind == "ide" else R.dmap_feature(kg, h, e))
             return col0 + c if 0 <= c < width else -1
         kg -= n
     raise IndexError("K group beyond the layer's segments")
@@ -148,7 +169,8 @@ def map_is_bijection(lay, prec):
 
 class Unpacked:
     """w[l] (rows, in_f) / pad[l] in the stream's element type, b[l] (rows,) / bpad[l] fp32, tail = the stream's padding fragments,
-    fold_w (128, 256) / fold_b (128,) = the fp32 fold behind the bias table (MipNeRF layouts)"""
+    fold_w (128, 256) / fold_b (128,) = the fp32 fold behind the bias table (MipNeRF layouts), ide (9, 19) = the IDE coefficient table
+    behind the bias table (RefLayout; its 5 padding floats are neither written by the pack nor read by the kernel, and are not returned)"""
 
 
 def unpack(blob, lay, prec):
@@ -173,6 +195,8 @@ def unpack(blob, lay, prec):
     if lay.fold:
         f = blob[sb + 4 * lay.N_BIAS:].view(torch.float32)
         u.fold_w, u.fold_b = f[: 128 * 256].view(128, 256).clone(), f[128 * 256:].clone()
+    if lay.N_IDE:
+        u.ide = blob[sb + 4 * lay.N_BIAS:].view(torch.float32)[: IDE_ROWS * IDE_TERMS].view(IDE_ROWS, IDE_TERMS).clone()
     return u
 
 
@@ -183,13 +207,16 @@ def layer_masters(lay, ws, bs, fold_w=None, fold_b=None):
         if src == "fold":
             mats.append(torch.cat((fold_w.float(), ws[9].detach().float()[:, 256:]), dim=1))
             biases.append(fold_b.float())
+        elif src == "H":
+            mats.append(torch.cat((ws[8].detach().float(), ws[9].detach().float()), dim=0))
+            biases.append(torch.cat((bs[8].detach().float(), bs[9].detach().float()), dim=0))
         else:
             mats.append(ws[src].detach().float())
             biases.append(bs[src].detach().float())
     return mats, biases
 
 
-def pack(lay, prec, mats, biases, fold_w=None, fold_b=None):
+def pack(lay, prec, mats, biases, fold_w=None, fold_b=None, ide=None):
     """the Python packer of the host test: mlp_layout.h written forwards, one fragment at a time -> uint8 blob"""
     dt = torch.bfloat16 if prec == "bf16" else torch.float32
     stream = torch.full((lay.N_FRAGS * 512,), float("nan")).to(dt)
@@ -214,6 +241,10 @@ def pack(lay, prec, mats, biases, fold_w=None, fold_b=None):
     parts = [stream.view(torch.uint8), bias.view(torch.uint8)]
     if lay.fold:
         parts += [fold_w.float().contiguous().view(-1).view(torch.uint8), fold_b.float().contiguous().view(torch.uint8)]
+    if lay.N_IDE:
+        tab = torch.zeros(lay.N_IDE)
+        tab[: IDE_ROWS * IDE_TERMS] = ide.float().reshape(-1)
+        parts.append(tab.view(torch.uint8))
     return torch.cat(parts)
 
 
@@ -227,6 +258,7 @@ def fold_bounds(w8, b8, wb, bb):
 WIDTH = {"prop": (256, 256, 256, 256), "mip": (256, 256, 256, 256, 256, 256, 256, 128)}
 ENC_SLOT = {"prop": 4, "mip": 8}
 ENC_WIDTH = {"prop": 64, "mip": 96}
+DUMP_SLOTS = {"prop": 5, "mip": 9, "ref": 17}                     # PROP_DUMP_SLOTS, MIP_DUMP_SLOTS, REF_DUMP_SLOTS (mlp_layout.h)
 
 
 def geometry(prec, M):
@@ -251,7 +283,7 @@ def mask_rows(block, n_features):
 
 def mask_block(dump, net, prec, M, slot):
     n_sub, ls = geometry(prec, M)
-    slots = ENC_SLOT[net] + 1
+    slots = DUMP_SLOTS[net]
     assert dump.numel() == slots * (ls + n_sub * 1024)
     return dump[slots * ls + slot * n_sub * 1024: slots * ls + (slot + 1) * n_sub * 1024]
 
@@ -277,10 +309,18 @@ def linear_tol(a, K):
     return (K + 3) * U24 * a + (K + 1) * TINY
 
 
-def check_stage(got, x, w, b, K, prec, kind, chunk=1 << 15):
+def noisy_tol(s, a, add, K, prec):
+    """round(s + add) without ReLU (Ref-NeRF's bottle-neck): the linear bound t on s, one fp32 addition of the computed s^ and add
+    (|s^ + add| <= |s| + t + |add|), and in bf16 the half-ulp conversion of the computed sum (|sum^| <= |s + add| + t1)"""
+    t = linear_tol(a, K)
+    t1 = t + U24 * (s.abs() + t + add.abs())
+    return t1 + BF16_HALF_ULP * ((s + add).abs() + t1) if prec == "bf16" else t1
+
+
+def check_stage(got, x, w, b, K, prec, kind, chunk=1 << 15, add=None):
     """One stage against its own inputs: got (M, N), x (M, in_f) the dumped input rows, w (N, in_f) / b (N,) the blob's operands.
     -> dict: worst = max(err / tol) over EVERY element, where = (sample, feature) of it, neg_nonzero = hidden elements with s < -tol
-    that are not exactly zero."""
+    that are not exactly zero.  kind 'noisy': got = round(s + add), add (M, N) or None = zero."""
     N = got.shape[1]
     w64, b64 = w.double(), b.double()
     wa, ba = w64.abs(), b64.abs()
@@ -294,6 +334,9 @@ def check_stage(got, x, w, b, K, prec, kind, chunk=1 << 15):
             neg_nonzero += int(((s < -tol) & (g != 0)).sum())
         elif kind == "linear":
             tol, want = linear_tol(a, K), s
+        elif kind == "noisy":
+            ad = torch.zeros_like(s) if add is None else add[i: i + chunk].double()
+            tol, want = noisy_tol(s, a, ad, K, prec), s + ad
         else:
             tol, want = linear_tol(a, K) / 4 + SIGMOID_C * U24, torch.sigmoid(s)
         ratio = (g - want).abs() / tol
