@@ -140,6 +140,12 @@ int nerf_amd_proposal_forward(const void* packed, int precision, const nerf_amd_
 /* MipNeRF.forward (mip_model.py:41-60): rgbo (M, 4) = [sigmoid rgb | raw sigma]. */
 int nerf_amd_mip_forward(const void* packed, int precision, const nerf_amd_samples* src,
                          float* rgbo, void* stream);
+/* (added after ABI 125; additive) rays (N,6) -> table (N, 32) bf16: for each ray the direction columns of rgb_layer.0's input, PE4(d/|d|) in
+ * MFMA B-operand order: [lane half 0: K groups 0, 1 | lane half 1: K groups 0, 1], 16 bytes each.  table: 16-byte aligned.  This is what
+ * nerf_amd_mip_forward computes once per ray itself on ray descriptors (mode 1 with explicit z, no contraction, no integrated PE) whose S
+ * is a multiple of 64 -- there the NERF_AMD_BF16 kernel takes a wave's 64 samples as one ray; before it writes them, it uses each 64-sample
+ * block of `rgbo` as scratch for that block's 64 bytes of encoding, so no workspace is needed.  Same bits as the per-sample kernel. */
+int nerf_amd_direction_table(const float* rays, int64_t N, void* table, void* stream);
 
 /* MipNeRF.forward + NeRF.render fused (mip_model.py:41-60 + nerf_base.py:91-113, mul_norm = True, relu density): the
  * (N,S,4) network output stays on chip; the last wavefront of each ray composites it.  `src` must be mode 1 (rays + z) with

@@ -43,6 +43,7 @@ SIGNATURES = {
     "nerf_amd_pack_weights": (C.c_int, [C.c_int, C.c_int, C.POINTER(c_void), C.POINTER(c_void), C.c_int, c_void, c_void]),
     "nerf_amd_proposal_forward": (C.c_int, [c_void, C.c_int, C.POINTER(Samples), c_void, c_void]),
     "nerf_amd_mip_forward": (C.c_int, [c_void, C.c_int, C.POINTER(Samples), c_void, c_void]),
+    "nerf_amd_direction_table": (C.c_int, [c_void, i64, c_void, c_void]),
     "nerf_amd_mip_forward_composite": (C.c_int, [c_void, C.c_int, C.POINTER(Samples), C.c_int, C.c_float, C.c_float, c_void, c_void, c_void,
                                                  c_void]),
     "nerf_amd_ref_forward": (C.c_int, [c_void, C.c_int, C.POINTER(Samples), C.c_int, c_void, c_void, c_void]),
@@ -146,6 +147,10 @@ SIGNATURES = {
 }
 
 
+# additive entry points that a library named by NERF_AMD_LIB may predate
+ADDED_AFTER_125 = ("nerf_amd_direction_table",)
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -153,6 +158,8 @@ def _load():
             "(or `make -C nerf_amd/csrc`). There is no CPU/torch fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in SIGNATURES.items():
+        if name in ADDED_AFTER_125 and os.environ.get("NERF_AMD_LIB") and not hasattr(lib, name):
+            continue                            # a diagnostic build of an older tree (A/B runs against a parent library)
         fn = getattr(lib, name)                 # AttributeError if the .so does not export it
         fn.restype = res
         fn.argtypes = args

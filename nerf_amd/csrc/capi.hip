@@ -157,6 +157,13 @@ int nerf_amd_mip_forward(const void* packed, int precision, const nerf_amd_sampl
     return hip_status(launch_mip_any(lflags, packed, precision, *src, rgbo, S(stream)), "nerf_amd_mip_forward");
 }
 
+int nerf_amd_direction_table(const float* rays, int64_t N, void* table, void* stream) {
+    if (N < 0) return fail(NERF_AMD_EINVAL, "negative ray count");
+    if (N && (!rays || !table)) return fail(NERF_AMD_EINVAL, "NULL argument");
+    if (reinterpret_cast<uintptr_t>(table) & 15) return fail(NERF_AMD_EINVAL, "the table must be 16-byte aligned");
+    return hip_status(mlp_launch_dir_table(rays, N, table, S(stream)), "nerf_amd_direction_table");
+}
+
 int nerf_amd_mip_forward_composite(const void* packed, int precision, const nerf_amd_samples* src, int white_bkg, float near,
                                    float far, float* rgb, float* depth, float* weights, void* stream) {
     int lflags;

@@ -8,6 +8,7 @@ namespace nk {
 // ---- mlp_kernels.hip
 int mlp_launch_proposal(const void* packed, int precision, const nerf_amd_samples& s, float* density, hipStream_t st);
 int mlp_launch_mip(const void* packed, int precision, const nerf_amd_samples& s, float* rgbo, hipStream_t st);
+int mlp_launch_dir_table(const float* rays, int64_t N, void* table, hipStream_t st);
 int mlp_launch_mip128(const void* packed, int precision, const nerf_amd_samples& s, float* rgbo, hipStream_t st);
 int mlp_launch_mip_composite(const void* packed, int precision, const nerf_amd_samples& s, float* rgb, float* depth, float* weights, int white_bkg, float near, float far, hipStream_t st);
 int mlp_launch_proposal128(const void* packed, int precision, const nerf_amd_samples& s, float* density, hipStream_t st);

@@ -295,6 +295,61 @@ template <class A> struct same_type<A, A> { static constexpr bool value = true; 
 template <bool C, class A, class B> struct conditional_type { using type = A; };
 template <class A, class B> struct conditional_type<false, A, B> { using type = B; };
 
+// ------------------------------------------------------------------------------------------------
+// Ray tile: the two inference kernels of the bf16 render path instantiated a second time, under the policy PBF16WR,
+// for ray descriptors (mode 1, no contraction) whose S is a multiple of 64.  A wave's 64 samples -- both column tiles -- then lie on ONE
+// ray, so what depends on the ray alone is done once per wave instead of once per lane: the ray index is a wave-uniform division, origin
+// and direction are one uniform fetch, the unused sources (points in memory, camera pose; in the fine kernel also the Philox draw) are
+// not compiled in, and the fine kernel reads the ray's direction encoding, which dir_table_kernel (below: the same __device__ functions
+// on the same inputs) computed once per ray, instead of running norm3, three divisions and encode<P, 4, 2> per sample and column tile.
+// That kernel leaves each wave its ray's 64 bytes at the head of the wave's own 1 KiB block of the OUTPUT (rgbo, 64 samples x 16 bytes):
+// only that wave ever touches the block -- it reads the row in its tile prologue and overwrites the whole block with its results at the
+// tile end -- so the hand-over needs no scratch memory and no ordering beyond the stream's.
+// Every value that reaches an MFMA is produced by the expressions of the plain kernels: the outputs are theirs bit for bit
+// (tests/test_gpu_ray_tile.py).  The launchers choose; PBF16W and every other instantiation are what they were.
+// ------------------------------------------------------------------------------------------------
+struct PBF16WR : PBF16W {};
+template <class P> struct ray_tile { static constexpr bool value = same_type<P, PBF16WR>::value; };
+template <class P> constexpr bool wide_bf16() { return same_type<P, PBF16W>::value || ray_tile<P>::value; }
+// -DMLP_RAY_TILE=0 (or per kernel -DMLP_RAY_TILE_PROP=0 / -DMLP_RAY_TILE_MIP=0) keeps the plain kernels on every descriptor, for A/B runs
+#ifndef MLP_RAY_TILE
+#define MLP_RAY_TILE 1
+#endif
+#ifndef MLP_RAY_TILE_PROP
+#define MLP_RAY_TILE_PROP MLP_RAY_TILE
+#endif
+#ifndef MLP_RAY_TILE_MIP
+#define MLP_RAY_TILE_MIP MLP_RAY_TILE
+#endif
+constexpr int DIR_TABLE_ROW = 64;               // bytes per row: [lane half 0: K groups 0, 1 | lane half 1: K groups 0, 1], one bf16x8 each
+
+DEVINL int64_t wave_uniform(int64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+// first sample m0 of a wave (wave-uniform, a multiple of 64, S % 64 == 0) -> its ray and the index of m0 on that ray
+DEVINL void split_wave_index(const nerf_amd_samples& s, int64_t m0, int64_t& n, int& si0) {
+    int64_t q; int r;
+    split_sample_index(s, m0, q, r);
+    n = wave_uniform(q); si0 = __builtin_amdgcn_readfirstlane(r);
+}
+// sample si of ray n (n wave-uniform): fetch_sample's mode-1 path.  EXPLICIT_Z: the depths are in memory (the fine kernel: no draw compiled in)
+template <bool EXPLICIT_Z>
+DEVINL Sample fetch_ray_sample(const nerf_amd_samples& s, int64_t n, int si) {
+    Sample r;
+    const float* ry = s.rays + n * 6;                                            // one address for the whole wave
+    const float ox = ry[0], oy = ry[1], oz = ry[2];
+    r.dx = ry[3]; r.dy = ry[4]; r.dz = ry[5];
+    float zv;
+    if (EXPLICIT_Z || s.z) zv = s.z[n * s.z_stride + si];
+    else {
+        const float uu = s.u ? s.u[n * s.S + si] : philox_u_strat(s.rng_seed, n + s.rng_ray_offset, si);
+        zv = s.z_base[si] + uu * s.z_jitter;
+    }
+    r.x = ox + zv * r.dx; r.y = oy + zv * r.dy; r.z = oz + zv * r.dz;           // procedures.py:66
+    return r;
+}
+
 struct PropResident {
     using R = ResidentSet<PropLayout::N_FRAGS, 32, 0, 168, MLP_RES_PROP_HOLE>;
     static constexpr int NSLOT = MLP_RES_PROP_NSLOT;
@@ -412,7 +467,7 @@ __global__ __launch_bounds__(P::NW * 64) void proposal_kernel(const void* __rest
     using L = PropLayout;
     using BReg = typename P::BReg;
     constexpr int FPC = P::FPC;
-    constexpr bool RES = MLP_RESIDENT_PROP && same_type<P, PBF16W>::value && !TRAIN;        // resident weights: see PropResident
+    constexpr bool RES = MLP_RESIDENT_PROP && wide_bf16<P>() && !TRAIN;        // resident weights: see PropResident
     using R = typename conditional_type<RES, PropResident::R, NoResident>::type;
     using WS = typename conditional_type<RES, WeightStream<P, PropResident::NSLOT, R, PropResident::RES>, WeightStream<P, MLP_NSLOT>>::type;
     constexpr uint32_t bias0 = RES ? PropResident::BIAS : MLP_RING_BYTES;
@@ -431,7 +486,16 @@ __global__ __launch_bounds__(P::NW * 64) void proposal_kernel(const void* __rest
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         int64_t m[NT];
         BReg enc[NT][4];
-        if constexpr (NT == 2 && P::FAST_PE) {
+        if constexpr (ray_tile<P>::value) {
+            // ray tile: the paired prologue below with the ray found and fetched once per wave -- lane (j, h) is sample m0 + lane
+            static_assert(NT == 2 && P::FAST_PE && !TRAIN, "the ray tile is an inference form of the wide bf16 tile");
+            const int64_t m0 = tile * TS + wave * 64;                          // (wave-uniform; the output index is re-formed from it at the tile end: m[] unused)
+            int64_t n; int si0;
+            split_wave_index(s, m0 < s.M ? m0 : s.M - 64, n, si0);            // (M is a multiple of 64: a wave is all inside or all outside)
+            const Sample sm = fetch_ray_sample<false>(s, n, si0 + lane);
+            encode_pair<P, 10, 4>(sm.x, sm.y, sm.z, enc[0], enc[1]);
+            half_swap_groups<4>(enc[0], enc[1]);
+        } else if constexpr (NT == 2 && P::FAST_PE) {
             // paired prologue: lane (j, h) fetches and encodes sample j of column tile h for BOTH halves, then the halves trade
             m[0] = tile * TS + (wave * NT) * 32 + j;
             m[1] = m[0] + 32;
@@ -499,8 +563,14 @@ __global__ __launch_bounds__(P::NW * 64) void proposal_kernel(const void* __rest
         dense<P, 16, 1, L::START[4]>(ws, bias0 + L::BIAS_OFF[4] * 4, IN_B, OH, prev_of(d, OB_pend)).flush(OH);
         if constexpr (TRAIN) mask_flush<P, F8>(dump, macc, lay_pend, sub0, lane, sacc);
 #pragma unroll
-        for (int t = 0; t < NT; ++t)
-            if (h == 0 && m[t] < s.M) density[m[t]] = dens[t];
+        for (int t = 0; t < NT; ++t) {
+            if constexpr (ray_tile<P>::value) {
+                const int64_t m0 = tile * TS + wave * 64;
+                if (h == 0 && m0 < s.M) density[m0 + t * 32 + j] = dens[t];
+            } else {
+                if (h == 0 && m[t] < s.M) density[m[t]] = dens[t];
+            }
+        }
     }
     ws.drain();
 }
@@ -593,7 +663,7 @@ __global__ __launch_bounds__(P::NW * 64) void mip_kernel(const void* __restrict_
     const uint64_t probe_c0 = __builtin_readcyclecounter(), probe_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
     if constexpr (FUSED) { if (threadIdx.x < 16) reinterpret_cast<unsigned*>(smem + lds_tile<P>() + P::NW * P::NT * 32 * 32 + P::NW * P::NT * 8)[threadIdx.x] = 0u; }  // ray tickets
-    constexpr bool RES = MLP_RESIDENT_MIP && same_type<P, PBF16W>::value && !TRAIN && !IPE && !F8 && !FUSED;   // resident weights: see MipResident
+    constexpr bool RES = MLP_RESIDENT_MIP && wide_bf16<P>() && !TRAIN && !IPE && !F8 && !FUSED;   // resident weights: see MipResident
     using R = typename conditional_type<RES, MipResident::R, NoResident>::type;
     using WS = typename conditional_type<RES, WeightStream<P, MipResident::NSLOT, R, MipResident::RES>, WeightStream<P, MLP_NSLOT>>::type;
     constexpr uint32_t bias0 = RES ? MipResident::BIAS : LDS_BIAS;
@@ -637,7 +707,29 @@ __global__ __launch_bounds__(P::NW * 64) void mip_kernel(const void* __restrict_
         Deferred<P, 6, 2> d;
         {
             BReg enc[NT][4];
-            if constexpr (NT == 2 && P::FAST_PE && !IPE && !FUSED) {
+            if constexpr (ray_tile<P>::value) {
+                // ray tile: the paired prologue below with the ray found and fetched once per wave -- lane (j, h) is sample m0 + lane.  The
+                // ray's direction ENCODING (the 64 bytes that dir_table_kernel left at the head of this wave's block of rgbo; lane half h
+                // reads its 32) arrives with the other loads and is parked where the plain kernel parks the raw direction: slab k of the
+                // wave = K group k, the same for both column tiles.
+                static_assert(NT == 2 && P::FAST_PE && !TRAIN && !IPE && !F8 && !FUSED, "the ray tile is an inference form of the wide bf16 tile");
+                const int64_t m0 = tile * TS + wave * 64;                      // (wave-uniform; the output index is re-formed from it at the tile end: m[] unused)
+                int64_t n; int si0;
+                const int64_t m0c = m0 < s.M ? m0 : s.M - 64;                  // (M is a multiple of 64: a wave is all inside or all outside; one outside computes on the last block's inputs and stores nothing)
+                split_wave_index(s, m0c, n, si0);
+                const BReg* row = reinterpret_cast<const BReg*>(reinterpret_cast<const char*>(rgbo + m0c * 4) + h * (DIR_TABLE_ROW / 2));
+                const BReg row0 = row[0], row1 = row[1];
+                const Sample sm = fetch_ray_sample<true>(s, n, si0 + lane);
+                P::stash(dir_lds(0), row0);                                   // (parked before the encoding starts: the rows are the oldest loads)
+                P::stash(dir_lds(1), row1);
+                encode_pair<P, 10, 4>(sm.x, sm.y, sm.z, enc[0], enc[1]);
+                half_swap_groups<4>(enc[0], enc[1]);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) P::stash(enc_lds(t) + k * P::BREG_LDS, enc[t][k]);
+                }
+            } else if constexpr (NT == 2 && P::FAST_PE && !IPE && !FUSED) {
                 // paired prologue (see encode_pair): lane (j, h) fetches and encodes sample j of column tile h, the halves then trade
                 m[0] = tile * TS + (wave * NT) * 32 + j;
                 m[1] = m[0] + 32;
@@ -734,6 +826,10 @@ __global__ __launch_bounds__(P::NW * 64) void mip_kernel(const void* __restrict_
         if constexpr (TRAIN) mask_flush<P, F8>(dump, macc, 6, sub0, lane, sacc);
         // direction: d/|d| and PE4 (mip_model.py:43-46,51)
         BReg denc[NT][2];
+        if constexpr (ray_tile<P>::value) {
+            // the ray's encoding is in LDS, from the table: rgb_layer.0 reads its two K groups there, the same for both column tiles
+            // (held in registers from here on they cost the allocator a spilled VGPR; read at their K steps they cost none)
+        } else {
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             const f32x4 dv = *reinterpret_cast<const f32x4*>(smem + dir_lds(t));
@@ -743,6 +839,7 @@ __global__ __launch_bounds__(P::NW * 64) void mip_kernel(const void* __restrict_
                 dump_breg<P>(dump, 8, sub0 + t, 4, lane, denc[t][0]);
                 dump_breg<P>(dump, 8, sub0 + t, 5, lane, denc[t][1]);
             }
+        }
         }
         // rgb_layer.0 with bottle_neck.0 folded in (mlp_layout.h): cat(g 256, dir 27) -> 128, ReLU
         BReg c[NT][8];
@@ -754,7 +851,10 @@ __global__ __launch_bounds__(P::NW * 64) void mip_kernel(const void* __restrict_
             }
         };
         const auto dc = dense<P, 18, 4, L::START[8]>(ws, bias0 + L::BIAS_OFF[8] * 4,
-            [&](int kg, int t) -> BReg { if (kg < 16) return a[t][kg < 16 ? kg : 0]; return denc[t][kg >= 16 ? kg - 16 : 0]; },
+            [&](int kg, int t) -> BReg {
+                if (kg < 16) return a[t][kg < 16 ? kg : 0];
+                if constexpr (ray_tile<P>::value) return P::unstash(dir_lds(kg >= 16 ? kg - 16 : 0));
+                return denc[t][kg >= 16 ? kg - 16 : 0]; },
             OC, prev_of(dsig, OSIG));
         // rgb_layer.2 : 128 -> 3, sigmoid
         float r[NT], g[NT], bl[NT];
@@ -769,7 +869,10 @@ __global__ __launch_bounds__(P::NW * 64) void mip_kernel(const void* __restrict_
             o[t][1] = 1.0f / (1.0f + expf(-g[t]));
             o[t][2] = 1.0f / (1.0f + expf(-bl[t]));
             o[t][3] = sigma[t];
-            if constexpr (!FUSED) {
+            if constexpr (ray_tile<P>::value) {
+                const int64_t m0 = tile * TS + wave * 64;
+                if (h == 0 && m0 < s.M) *reinterpret_cast<f32x4*>(rgbo + (m0 + t * 32 + j) * 4) = o[t];
+            } else if constexpr (!FUSED) {
                 if (h == 0 && m[t] < s.M) *reinterpret_cast<f32x4*>(rgbo + m[t] * 4) = o[t];
             }
         }
@@ -1289,6 +1392,31 @@ __global__ __launch_bounds__(P::NW * 64) void ref_kernel(const void* __restrict_
     ws.drain();
 }
 
+// The direction encodings of the ray-tile fine kernel: thread (row r, lane half h) computes what lane half h of mip_kernel computes for
+// every sample of ray r / rows_per_ray -- norm3, the three divisions, encode<P, 4, 2> -- and writes its two K groups to
+// out + r * row_stride (DIR_TABLE_ROW bytes: [lane half][K group]).  rows_per_ray = 1, row_stride = 64: the (N, 32) bf16 table of
+// nerf_amd_direction_table; rows_per_ray = S / 64, row_stride = 1024: one row at the head of every 64-sample block of rgbo.
+#if MLP_TU == 0 || MLP_TU == 2
+__global__ __launch_bounds__(256) void dir_table_kernel(const float* __restrict__ rays, int64_t n_rows, int rows_per_ray, int row_stride, char* __restrict__ out) {
+    using P = PBF16W;
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t r = i >> 1;
+    const int h = (int)(i & 1);
+    if (r >= n_rows) return;
+    const float* ry = rays + (r / rows_per_ray) * 6;
+    const float dx = ry[3], dy = ry[4], dz = ry[5];
+    const float nrm = norm3(dx, dy, dz);
+    P::BReg denc[2];
+    encode<P, 4, 2>(dx / nrm, dy / nrm, dz / nrm, h, denc);
+    P::BReg* row = reinterpret_cast<P::BReg*>(out + r * row_stride + h * (DIR_TABLE_ROW / 2));
+    row[0] = denc[0];
+    row[1] = denc[1];
+}
+#endif
+
+// descriptors of the ray-tile instantiations: rays + depths, no contraction, a wave's 64 samples on one ray
+bool ray_tile_descriptor(const nerf_amd_samples& s) { return s.mode == 1 && !s.contract && !s.ipe && s.S > 0 && s.S % 64 == 0 && s.M % s.S == 0; }
+
 int grid_for(int64_t n_tiles) {
     const int n_cu = nerf_host::cu_count();
     return (int)(n_tiles < n_cu ? n_tiles : n_cu);
@@ -1323,14 +1451,30 @@ using PB16 = PBF16W;
 #endif
 #if MLP_TU == 0 || MLP_TU == 1
 int nk::mlp_launch_proposal(const void* packed, int precision, const nerf_amd_samples& s, float* density, hipStream_t st) {
+#if MLP_RAY_TILE_PROP
+    if (precision == NERF_AMD_BF16 && ray_tile_descriptor(s))
+        return launch<PBF16WR, PropLayout, false, false, (MLP_RESIDENT_PROP ? PropResident::TOTAL : 0)>(proposal_kernel<PBF16WR, false>, packed, s, density, st, NO_DUMP);
+#endif
     if (precision == NERF_AMD_BF16)
         return launch<PB16, PropLayout, false, false, (MLP_RESIDENT_PROP ? PropResident::TOTAL : 0)>(proposal_kernel<PB16, false>, packed, s, density, st, NO_DUMP);
     return launch<PF32, PropLayout>(proposal_kernel<PF32, false>, packed, s, density, st, NO_DUMP);
 }
 #endif
 #if MLP_TU == 0 || MLP_TU == 2
+static int launch_dir_rows(const float* rays, int64_t n_rows, int rows_per_ray, int row_stride, void* out, hipStream_t st) {
+    if (n_rows <= 0) return 0;
+    hipLaunchKernelGGL(dir_table_kernel, dim3((unsigned)((2 * n_rows + 255) / 256)), dim3(256), 0, st, rays, n_rows, rows_per_ray, row_stride, reinterpret_cast<char*>(out));
+    return (int)hipGetLastError();
+}
+int nk::mlp_launch_dir_table(const float* rays, int64_t N, void* table, hipStream_t st) { return launch_dir_rows(rays, N, 1, DIR_TABLE_ROW, table, st); }
 int nk::mlp_launch_mip(const void* packed, int precision, const nerf_amd_samples& s, float* rgbo, hipStream_t st) {
     const FusedComposite off{nullptr, nullptr, nullptr, 0, 0.0f, 1.0f};
+#if MLP_RAY_TILE_MIP
+    if (precision == NERF_AMD_BF16 && s.z && ray_tile_descriptor(s)) {      // one small launch leaves every wave its ray's direction encoding in rgbo
+        if (int e = launch_dir_rows(s.rays, s.M / 64, s.S / 64, 64 * 16, rgbo, st)) return e;
+        return launch<PBF16WR, MipLayout, false, false, (MLP_RESIDENT_MIP ? MipResident::TOTAL : 0)>(mip_kernel<PBF16WR, false>, packed, s, rgbo, st, off, NO_DUMP);
+    }
+#endif
     if (s.ipe) {                                            // integrated positional encoding (validated by the C-ABI: mode 1, z, dir norm)
         if (precision == NERF_AMD_BF16) return launch<PB16, MipLayout>(mip_kernel<PB16, false, true>, packed, s, rgbo, st, off, NO_DUMP);
         return launch<PF32, MipLayout>(mip_kernel<PF32, false, true>, packed, s, rgbo, st, off, NO_DUMP);

@@ -259,6 +259,14 @@ def mip_forward_samples(packed, precision, s: Samples, shape, device) -> torch.T
     return out
 
 
+def direction_table(rays: torch.Tensor) -> torch.Tensor:
+    """rays (N, 6) -> (N, 32) bf16: each ray's PE4(d/|d|) in the B-operand order of rgb_layer.0's direction columns (include/nerf_amd.h)"""
+    rays = _dev(rays, "rays")
+    out = torch.empty((rays.shape[0], 32), dtype=torch.bfloat16, device=rays.device)
+    check(lib.nerf_amd_direction_table(_ptr(rays), rays.shape[0], _ptr(out), _stream()), "nerf_amd_direction_table")
+    return out
+
+
 def mip_forward_composite(packed, precision, rays: torch.Tensor, z: torch.Tensor, n_samples: int, white_bkg: bool, near: float,
                           far: float, want_depth: bool = True, want_weights: bool = False):
     """Fine MLP + alpha compositing in one launch (rows 8-10); z (N, >= n_samples) row stride = z.shape[-1].  A NET_MIP_128 blob (the
