@@ -556,6 +556,30 @@ int    nerf_amd_render_rays_warped(const void* packed_prop, const void* packed_m
                                    int n_fine, int spacing, float near, float far, int white_bkg, float* rgb, float* depth, float* weights,
                                    void* workspace, void* stream);
 
+/* Mip-NeRF 360's TWO proposal rounds behind one entry point (non-Ref; in-kernel Philox uniforms only: `camera` is required and carries
+ * rng_seed, rng_ray_offset, contract and the ipe fields as in the two entry points above).  `spacing`: NERF_AMD_SPACING_LINEAR or
+ * NERF_AMD_SPACING_DISPARITY; z_base (64 floats) is read under linear spacing only.
+ *   linear:    [ray generation] -> [IPE direction norm] -> proposal MLP (stratified draw fused) -> resample to prop_pnum sorted depths z_mid
+ *              -> proposal MLP at z_mid -> resample to n_fine + 1 depths -> fine MLP -> composite
+ *   disparity: coarse draw in s -> proposal MLP -> warped resample to s_mid, z_mid = W(s_mid) -> proposal MLP at z_mid -> warped resample
+ *              from s_mid -> fine MLP -> composite (near = 0, far = 1) -> depth = W^-1(sum w z |d|)
+ * Uniforms: the stratified stream as in nerf_amd_render_rays; the ray's inverse-CDF stream (words 1..3 of its 'RS' blocks, column k =
+ * nerf_amd_philox_stream's column k) has prop_pnum + n_fine + 1 columns: columns [0, prop_pnum) feed the first resampling, columns
+ * [prop_pnum, prop_pnum + n_fine + 1) the second -- both keyed by the global ray index n + rng_ray_offset, so any split of a ray list
+ * reproduces the whole bit for bit.  The image equals the same chain written with the single-stage entry points on those columns.
+ * Limits (NERF_AMD_EINVAL before the first launch): 3 <= prop_pnum <= 256, 1 <= n_fine <= 1023, and both resampling launches within
+ * 64 KiB of LDS: linear 4 (5 * 64 + 2 prop_pnum + 1280) and 4 (5 prop_pnum + 3 (n_fine + 1) + 1280) floats, disparity
+ * 4 (5 * 64 + 4 prop_pnum + 1280) and 4 (5 prop_pnum + 4 (n_fine + 1) + 1280); the 128-wide fine layout takes no IPE.
+ * Workspace (nerf_amd_render_rounds_workspace_bytes; 0 for arguments outside the limits), every part rounded up to 256 bytes:
+ *   density (N,64) [| s_c (N,64) | z_c (N,64), disparity] | density2 (N,prop_pnum) | z_mid (N,prop_pnum) [| s_mid (N,prop_pnum), disparity]
+ *   | z_fine (N, n_fine+1) | rgbo (N, n_fine, 4) [| raw depth (N), disparity] | rays (N,6) | 512 bytes (scalar slot, alignment slack)
+ * No allocation, no synchronisation: capturable like the other render entry points. */
+size_t nerf_amd_render_rounds_workspace_bytes(int64_t N, int n_fine, int prop_pnum, int spacing);
+int    nerf_amd_render_rays_rounds(const void* packed_prop, const void* packed_mip, int precision, const float* rays,
+                                   const nerf_amd_samples* camera, int64_t ray_offset, const float* z_base, int64_t N, int n_fine,
+                                   int prop_pnum, int spacing, float near, float far, int white_bkg, float* rgb, float* depth,
+                                   float* weights, void* workspace, void* stream);
+
 /* The same tile body for a Ref-NeRF fine network (procedures.py:64-85 with the is_ref_model branch, lines 71-74): proposal pass,
  * resampling, the n_fine+1 fine and 64 coarse depths merged (the last one dropped), Ref-NeRF MLP on the n_fine+64 samples,
  * compositing with sigma -> softplus(sigma + 0.5).  normal_img (N) and cam_dir (3 floats on the device: render_pose[:, -2]) are

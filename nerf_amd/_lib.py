@@ -132,6 +132,9 @@ SIGNATURES = {
     "nerf_amd_render_warped_workspace_bytes": (C.c_size_t, [i64, C.c_int]),
     "nerf_amd_render_rays_warped": (C.c_int, [c_void, c_void, C.c_int, c_void, C.POINTER(Samples), i64, c_void, c_void, i64, C.c_int, C.c_int,
                                               C.c_float, C.c_float, C.c_int, c_void, c_void, c_void, c_void, c_void]),
+    "nerf_amd_render_rounds_workspace_bytes": (C.c_size_t, [i64, C.c_int, C.c_int, C.c_int]),
+    "nerf_amd_render_rays_rounds": (C.c_int, [c_void, c_void, C.c_int, c_void, C.POINTER(Samples), i64, c_void, i64, C.c_int, C.c_int, C.c_int,
+                                              C.c_float, C.c_float, C.c_int, c_void, c_void, c_void, c_void, c_void]),
     "nerf_amd_gemm_workspace_bytes": (C.c_size_t, [i64, i64, i64]),
     "nerf_amd_gemm": (C.c_int, [C.c_int, i64, i64, i64, c_void, i64, i64, c_void, i64, i64, c_void, i64, c_void, C.c_int, c_void, i64, c_void, c_void]),
     "nerf_amd_sigmoid_backward": (C.c_int, [c_void, i64, c_void, i64, i64, C.c_int, c_void, i64, c_void]),
@@ -148,7 +151,7 @@ SIGNATURES = {
 
 
 # additive entry points that a library named by NERF_AMD_LIB may predate
-ADDED_AFTER_125 = ("nerf_amd_direction_table",)
+ADDED_AFTER_125 = ("nerf_amd_direction_table", "nerf_amd_render_rounds_workspace_bytes", "nerf_amd_render_rays_rounds")
 
 
 def _load():

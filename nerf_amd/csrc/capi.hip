@@ -667,27 +667,32 @@ int nerf_amd_get_bounds_backward(const int64_t* below, const float* d_bounds, in
 // ------------------------------------------------------------------------------------------------ whole-ray rendering
 namespace {
 constexpr int RENDER_C = 64;                                // procedures.py:22 RENDER_COARSE_PNUM
-// The workspace of the three render entry points, described ONCE: the constructor walks the parts in order, each rounded up to 256 bytes.
+// The workspace of the four render entry points, described ONCE: the constructor walks the parts in order, each rounded up to 256 bytes.
 // Walked from NULL it gives the size (nerf_amd_render*_workspace_bytes), from the caller's pointer the parts.
 //   plain:   density (N,64) | z_fine (N, n_fine+1) | rgbo (N, n_fine, 4) | rays (N, 6) | one scalar slot (direction norm of the IPE mode)
 //   warped:  density | s_c (N,64) | z_c (N,64) | z_fine | rgbo | raw depth (N) | rays | the scalar slot
 //   ref:     density | z_fine | z_coarse (N,64) | z_all (N, n_fine+64) | rgbo (N, n_fine+64, 4) | normals (N, n_fine+64, 3) | rays (unrounded)
-enum WsKind { WS_PLAIN, WS_WARPED, WS_REF };
+//   rounds (two proposal rounds, P = prop_pnum): plain resp. warped with  density2 (N,P) | z_mid (N,P) [| s_mid (N,P), warped]  in front of z_fine
+enum WsKind { WS_PLAIN, WS_WARPED, WS_REF, WS_ROUNDS, WS_ROUNDS_WARPED };
 struct RenderWs {
-    float *density, *s_c = nullptr, *z_c = nullptr, *z_fine, *z_coarse = nullptr, *z_all = nullptr, *rgbo, *normals = nullptr, *depth_raw = nullptr, *rays, *dir_norm;
+    float *density, *s_c = nullptr, *z_c = nullptr, *density2 = nullptr, *z_mid = nullptr, *s_mid = nullptr, *z_fine, *z_coarse = nullptr, *z_all = nullptr, *rgbo,
+          *normals = nullptr, *depth_raw = nullptr, *rays, *dir_norm;
     size_t bytes;
-    RenderWs(WsKind kind, void* base, int64_t N, int n_fine) {
+    RenderWs(WsKind kind, void* base, int64_t N, int n_fine, int prop_pnum = 0) {
         const uintptr_t start = (reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255;
         uintptr_t p = start;
         auto take = [&p](size_t part) { float* r = reinterpret_cast<float*>(p); p += (part + 255) & ~(size_t)255; return r; };
         const size_t n = (size_t)N, S = (size_t)n_fine + (kind == WS_REF ? RENDER_C : 0);    // samples per ray of the fine pass
+        const bool warped = kind == WS_WARPED || kind == WS_ROUNDS_WARPED, rounds = kind == WS_ROUNDS || kind == WS_ROUNDS_WARPED;
         density = take(n * RENDER_C * 4);
-        if (kind == WS_WARPED) { s_c = take(n * RENDER_C * 4); z_c = take(n * RENDER_C * 4); }
+        if (warped) { s_c = take(n * RENDER_C * 4); z_c = take(n * RENDER_C * 4); }
+        if (rounds) { density2 = take(n * prop_pnum * 4); z_mid = take(n * prop_pnum * 4); }
+        if (rounds && warped) s_mid = take(n * prop_pnum * 4);
         z_fine = take(n * (n_fine + 1) * 4);
         if (kind == WS_REF) { z_coarse = take(n * RENDER_C * 4); z_all = take(n * S * 4); }
         rgbo = take(n * S * 16);
         if (kind == WS_REF) normals = take(n * S * 12);
-        if (kind == WS_WARPED) depth_raw = take(n * 4);
+        if (warped) depth_raw = take(n * 4);
         rays = kind == WS_REF ? reinterpret_cast<float*>(p) : take(n * 24);   // ref: the ray table is the unrounded tail
         dir_norm = reinterpret_cast<float*>(p);             // plain, warped: the scalar slot behind the ray table
         bytes = (size_t)(p - start) + (kind == WS_REF ? n * 24 + 256 : 512);   // + alignment slack (+ the scalar slot)
@@ -843,6 +848,81 @@ int nerf_amd_render_rays_warped(const void* packed_prop, const void* packed_mip,
     if (int e = sk_composite(ws.rgbo, ws.z_fine, n_fine + 1, rays + 3, 6, N, n_fine, flags, NERF_AMD_ACT_RELU, 0.0f, 0.0f, 1.0f, nullptr, nullptr, rgb, weights,
                              depth ? ws.depth_raw : nullptr, nullptr, st)) return hip_status(e, "composite");
     if (depth) {
+        if (int e = sk_warp_depths(ws.depth_raw, nullptr, N, 1, 1, near, far, gn, gf, depth, nullptr, st)) return hip_status(e, "depth un-warp");
+    }
+    return NERF_AMD_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ two proposal rounds
+static bool bad_rounds_shape(int64_t N, int n_fine, int prop_pnum, int spacing) {
+    return N < 0 || n_fine < 1 || n_fine > 1023 || prop_pnum < 3 || prop_pnum > 256 || (spacing != NERF_AMD_SPACING_LINEAR && spacing != NERF_AMD_SPACING_DISPARITY);
+}
+size_t nerf_amd_render_rounds_workspace_bytes(int64_t N, int n_fine, int prop_pnum, int spacing) {
+    if (bad_rounds_shape(N, n_fine, prop_pnum, spacing)) return 0;
+    return RenderWs(spacing == NERF_AMD_SPACING_DISPARITY ? WS_ROUNDS_WARPED : WS_ROUNDS, nullptr, N, n_fine, prop_pnum).bytes;
+}
+int nerf_amd_render_rays_rounds(const void* packed_prop, const void* packed_mip, int precision, const float* rays, const nerf_amd_samples* camera,
+                                int64_t ray_offset, const float* z_base, int64_t N, int n_fine, int prop_pnum, int spacing, float near, float far, int white_bkg,
+                                float* rgb, float* depth, float* weights, void* workspace, void* stream) {
+    int lflags;
+    if (split_precision(precision, lflags, NERF_AMD_PROP_W128 | NERF_AMD_FINE_W128)) return fail(NERF_AMD_EINVAL, "unknown precision");
+    if (spacing != NERF_AMD_SPACING_LINEAR && spacing != NERF_AMD_SPACING_DISPARITY)
+        return fail(NERF_AMD_EINVAL, "unknown spacing (NERF_AMD_SPACING_LINEAR or NERF_AMD_SPACING_DISPARITY)");
+    const bool warped = spacing == NERF_AMD_SPACING_DISPARITY;
+    float gn = 0.0f, gf = 0.0f;
+    if (warped)
+        if (int e = check_spacing(spacing, near, far, &gn, &gf)) return e;
+    if ((lflags & NERF_AMD_FINE_W128) && camera && camera->ipe) return fail(NERF_AMD_EINVAL, "the 128-wide fine layout has no integrated-PE kernel: pack the network 256-wide");
+    if (N < 0 || n_fine < 1 || n_fine > 1023) return fail(NERF_AMD_EINVAL, "bad N or n_fine (1 <= n_fine <= 1023)");
+    if (prop_pnum < 3 || prop_pnum > 256) return fail(NERF_AMD_EINVAL, "bad prop_pnum (3 <= prop_pnum <= 256: the second round's histogram)");
+    constexpr int C = RENDER_C;
+    const int P = prop_pnum, K = n_fine + 1;
+    if (warped) {
+        if (int e = check_warped_resample_shape(C, P)) return e;
+        if (int e = check_lds(sk_resample_window_lds_bytes(P, K, 1), "prop_pnum and n_fine")) return e;
+    } else {
+        if (int e = check_lds(sk_resample_lds_bytes(C, P), "prop_pnum")) return e;
+        if (int e = check_lds(sk_resample_window_lds_bytes(P, K, 0), "prop_pnum and n_fine")) return e;
+    }
+    if (N == 0) return NERF_AMD_OK;
+    if (!camera) return fail(NERF_AMD_EINVAL, "NULL argument: in-kernel uniforms need the descriptor (rng_seed, rng_ray_offset)");
+    if (int e = check_render_inputs(packed_prop && packed_mip && (warped || z_base) && rgb && workspace, rays, camera, nullptr, nullptr)) return e;
+    if (warped && camera->ipe && !rays) return fail(NERF_AMD_EINVAL, "integrated PE needs an explicit ray table");
+    const uint64_t seed = camera->rng_seed;
+    const int64_t ray0 = camera->rng_ray_offset;
+    const RenderWs ws(warped ? WS_ROUNDS_WARPED : WS_ROUNDS, workspace, N, n_fine, P);
+    hipStream_t st = S(stream);
+    if (int e = provide_rays(rays, camera, ray_offset, N, ws.rays, st)) return e;
+    const float* dir_norm;
+    if (int e = provide_dir_norm(camera, rays, N, ws.dir_norm, ws.density, st, &dir_norm)) return e;
+    const nerf_amd_samples mid = ray_samples(rays, N, P, ws.z_mid, P, camera);      // the second proposal pass: P samples per ray at the first round's depths
+    if (warped) {
+        if (int e = sk_warped_stratified(rays, nullptr, N, C, seed, ray0, near, far, gn, gf, ws.s_c, ws.z_c, nullptr, st)) return hip_status(e, "warped stratified draw");
+        const nerf_amd_samples sc = ray_samples(rays, N, C, ws.z_c, C, camera);
+        if (int e = launch_proposal_any(lflags, packed_prop, precision, sc, ws.density, st)) return hip_status(e, "proposal MLP");
+        // columns [0, P) of the inverse-CDF stream -> s_mid, z_mid = W(s_mid)
+        if (int e = sk_warped_resample(ws.density, ws.s_c, rays + 3, 6, nullptr, N, C, P, 0, 0.01f, near, far, gn, gf, seed, ray0, ws.z_mid, ws.s_mid, nullptr, nullptr,
+                                       st)) return hip_status(e, "warped resample");
+        if (int e = launch_proposal_any(lflags, packed_prop, precision, mid, ws.density2, st)) return hip_status(e, "proposal MLP, second round");
+        // columns [P, P + n_fine + 1)
+        if (int e = sk_warped_resample_window(ws.density2, ws.s_mid, rays + 3, 6, N, P, K, P, 0.01f, near, far, gn, gf, seed, ray0, ws.z_fine, nullptr, st))
+            return hip_status(e, "warped resample, second round");
+    } else {
+        const float jitter = (far - near) / (float)n_fine;      // procedures.py:59
+        nerf_amd_samples sc = ray_samples(rays, N, C, nullptr, C, camera);
+        sc.z_base = z_base; sc.z_jitter = jitter; sc.rng_seed = seed; sc.rng_ray_offset = ray0;
+        if (int e = launch_proposal_any(lflags, packed_prop, precision, sc, ws.density, st)) return hip_status(e, "proposal MLP");
+        if (int e = sk_resample(ws.density, nullptr, z_base, nullptr, jitter, rays + 3, 6, nullptr, N, C, P, 0, 0.01f, seed, ray0, ws.z_mid, nullptr, nullptr, nullptr,
+                                st)) return hip_status(e, "resample");
+        if (int e = launch_proposal_any(lflags, packed_prop, precision, mid, ws.density2, st)) return hip_status(e, "proposal MLP, second round");
+        if (int e = sk_resample_window(ws.density2, ws.z_mid, rays + 3, 6, N, P, K, P, 0.01f, seed, ray0, ws.z_fine, st)) return hip_status(e, "resample, second round");
+    }
+    if (int e = fine_pass(lflags, packed_mip, precision, rays, camera, N, n_fine, dir_norm, ws, st)) return e;
+    const int flags = 1 | (white_bkg ? 2 : 0);
+    // warped: near = 0, far = 1 -- the composite kernel's depth is then the raw expected metric depth sum w z |d|, un-warped below
+    if (int e = sk_composite(ws.rgbo, ws.z_fine, K, rays + 3, 6, N, n_fine, flags, NERF_AMD_ACT_RELU, 0.0f, warped ? 0.0f : near, warped ? 1.0f : far, nullptr, nullptr,
+                             rgb, weights, (warped && depth) ? ws.depth_raw : depth, nullptr, st)) return hip_status(e, "composite");
+    if (warped && depth) {
         if (int e = sk_warp_depths(ws.depth_raw, nullptr, N, 1, 1, near, far, gn, gf, depth, nullptr, st)) return hip_status(e, "depth un-warp");
     }
     return NERF_AMD_OK;

@@ -51,6 +51,7 @@ int pack_mfma_stream(int iters, int workgroups, int mode, float* sink, hipStream
 size_t sk_inverse_sample_lds_bytes(int C, int K);
 size_t sk_resample_lds_bytes(int C, int K);
 size_t sk_warped_resample_lds_bytes(int C, int K);
+size_t sk_resample_window_lds_bytes(int C, int K, int warped);
 size_t sk_get_bounds_lds_bytes(int C);
 size_t sk_get_bounds_backward_lds_bytes(int K);
 size_t sk_merge_sorted_lds_bytes(int K, int C, int order);
@@ -80,6 +81,10 @@ int sk_warped_stratified(const float* rays, const float* u, int64_t N, int C, ui
                          float* pts, hipStream_t st);
 int sk_warped_resample(const float* density, const float* s_c, const float* dirs, int dirs_stride, const float* u_inv, int64_t N, int C, int K, int softplus, float alpha, float near,
                        float far, float gn, float gf, uint64_t rng_seed, int64_t rng_ray_offset, float* z_fine, float* s_fine, int64_t* below, float* w_prop, hipStream_t st);
+int sk_resample_window(const float* density, const float* z, const float* dirs, int dirs_stride, int64_t N, int C, int K, int u_col0, float alpha, uint64_t rng_seed,
+                       int64_t rng_ray_offset, float* z_fine, hipStream_t st);
+int sk_warped_resample_window(const float* density, const float* s_c, const float* dirs, int dirs_stride, int64_t N, int C, int K, int u_col0, float alpha, float near,
+                              float far, float gn, float gf, uint64_t rng_seed, int64_t rng_ray_offset, float* z_fine, float* s_fine, hipStream_t st);
 int sk_composite(const float* rgbo, const float* z, int z_stride, const float* dirs, int dirs_stride, int64_t N, int S, int flags, int act, float sigma_shift, float near, float far,
                  const float* normal, const float* cam_dir, float* rgb, float* weights, float* depth, float* normal_img, hipStream_t st);
 int sk_get_bounds(const float* w, const int64_t* below, int64_t N, int C, int K, float* bounds, hipStream_t st);

@@ -802,6 +802,119 @@ __global__ __launch_bounds__(256) void warped_resample_kernel(WarpedResampleArgs
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// The second proposal round (Mip-NeRF 360): the fused resampling step on EXPLICIT sorted coordinates -- the first round's output -- with
+// the K inverse-CDF uniforms of columns u_col0 .. u_col0 + K - 1 of the ray's Philox stream instead of its first K (the two-round stream
+// has prop_pnum + n_fine + 1 columns; the fine resampling reads behind the first prop_pnum).
+// ------------------------------------------------------------------------------------------------
+// uu[k] = philox_u_inv(seed, nn, u_col0 + k) for k < K.  One wavefront; lane j runs only those of its own blocks 64 b + j that carry a
+// column of the window -- a block holds columns 192 b + j + {0, 64, 128} in words 1..3 (device_common.h) -- so the window costs about
+// K / 192 + 1 blocks per lane where philox_u_inv per column would cost K / 64.
+DEVINL void wave_window_uniforms(float* uu, uint64_t seed, int64_t nn, int u_col0, int K) {
+    const int lane = lane_id();
+    for (int b = u_col0 / 192; 192 * b < u_col0 + K; ++b) {
+        const int k0 = 192 * b + lane - u_col0;                                // window index of the block's word 1
+        const bool in0 = k0 >= 0 && k0 < K, in1 = k0 + 64 >= 0 && k0 + 64 < K, in2 = k0 + 128 >= 0 && k0 + 128 < K;
+        if (!(in0 || in1 || in2)) continue;
+        const Philox4 p = philox_ray_block(seed, nn, 64 * b + lane);
+        if (in0) uu[k0] = u01_from_bits(p.w[1]);
+        if (in1) uu[k0 + 64] = u01_from_bits(p.w[2]);
+        if (in2) uu[k0 + 128] = u01_from_bits(p.w[3]);
+    }
+}
+
+// resample_kernel (WARPED = false: x = metric depths z) and warped_resample_kernel (WARPED = true: x = s, weights from W(s) |d|, bins in s,
+// z_fine = W(s_fine)) behind the window: the same device functions for weights, max-blur and inverse sampling in the same order, so a
+// round-two call equals the single-stage call given the same columns as a tensor.  resample_kernel binds lane j to ONE Philox block, which
+// holds only at u_col0 = 0; here a lane's samples come from other blocks, so the uniforms go through an LDS row and only the ray's global
+// loads -- direction, coordinates, densities -- stay one ray ahead in registers (C <= 128).  Kernels of their own: the one-round kernels'
+// code, register budget and occupancy stay exactly as they are.
+struct ResampleWindowArgs {
+    const float* density; const float* x; const float* dirs; int dirs_stride; int64_t N; int C; int K; int u_col0; float alpha; WarpConsts c;
+    float* z_fine; float* s_fine; uint64_t rng_seed; int64_t rng_ray_offset;
+};
+// LDS floats per wave: the rows of resample_kernel | uu[K] | sf[K] (WARPED)
+static inline __host__ __device__ size_t rsw_lds_floats(int C, int K, bool warped) { return rs_lds_floats(C, K) + (size_t)(warped ? 2 : 1) * K; }
+
+template <bool WARPED>
+__global__ __launch_bounds__(256) void resample_window_kernel(ResampleWindowArgs a) {
+    const int C = a.C, K = a.K;
+    float* base = reinterpret_cast<float*>(smem) + wave_in_block() * rsw_lds_floats(C, K, WARPED);
+    float* pw = base; float* bins = pw + C; float* cdf = bins + C; float* samp = cdf + C;
+    int* bel = reinterpret_cast<int*>(samp + K);
+    int* sortbuf = bel + K;
+    float* zl = reinterpret_cast<float*>(sortbuf + SORT_LDS_FLOATS);
+    float* wraw = zl + C;
+    float* uu = wraw + C;
+    float* sf = uu + K;                                                          // (WARPED only)
+    float* xl = WARPED ? cdf : zl;                                               // the bin coordinates: s parks in the cdf row, free until the inverse sampling writes it
+    const int lane = lane_id();
+    const WarpConsts c = a.c;
+    struct RayIn { float dx, dy, dz, x0, x1, dens0, dens1; };                    // scalars only: indexed members end up in scratch
+    const bool fits = C <= 128;
+    auto load_in = [&](int64_t n) -> RayIn {
+        RayIn r;
+        const float* dd = a.dirs + n * a.dirs_stride;
+        r.dx = dd[0]; r.dy = dd[1]; r.dz = dd[2];
+        r.x0 = r.x1 = r.dens0 = r.dens1 = 0.0f;
+        if (lane < C) { r.x0 = a.x[n * C + lane]; r.dens0 = a.density[n * C + lane]; }
+        if (lane + 64 < C) { r.x1 = a.x[n * C + lane + 64]; r.dens1 = a.density[n * C + lane + 64]; }
+        return r;
+    };
+    const int64_t stride = (int64_t)gridDim.x * WAVES_PER_BLOCK;
+    int64_t n = blockIdx.x * (int64_t)WAVES_PER_BLOCK + wave_in_block();
+    if (n >= a.N) return;
+    RayIn cur = {};
+    if (fits) cur = load_in(n);
+    for (; n < a.N; n += stride) {
+        RayIn nxt = cur;
+        if (fits && n + stride < a.N) nxt = load_in(n + stride);
+        lds_wave_sync();
+        float nrm;
+        if (fits) {
+            nrm = norm3(cur.dx, cur.dy, cur.dz);
+            if (lane < C) { zl[lane] = WARPED ? warp_s_to_z(cur.x0, c) : cur.x0; if (WARPED) xl[lane] = cur.x0; }
+            if (lane + 64 < C) { zl[lane + 64] = WARPED ? warp_s_to_z(cur.x1, c) : cur.x1; if (WARPED) xl[lane + 64] = cur.x1; }
+        } else {
+            const float* dd = a.dirs + n * a.dirs_stride;
+            nrm = norm3(dd[0], dd[1], dd[2]);
+            for (int j = lane; j < C; j += 64) {
+                const float xv = a.x[n * C + j];
+                zl[j] = WARPED ? warp_s_to_z(xv, c) : xv;
+                if (WARPED) xl[j] = xv;
+            }
+        }
+        wave_window_uniforms(uu, a.rng_seed, n + a.rng_ray_offset, a.u_col0, K);
+        lds_wave_sync();
+        const float* sg = a.density + n * C;
+        const float dens0 = cur.dens0, dens1 = cur.dens1;                        // by-value captures: a reference to `cur` pins it in scratch
+        wave_sigma_to_weights(C, NERF_AMD_ACT_RELU,
+                              [=](int s) { return fits ? ((s >> 6) ? dens1 : dens0) : sg[s]; },
+                              [=](int s) { return zl[s] * nrm; },
+                              [=](int s, float wv, float) { wraw[s] = wv; });
+        lds_wave_sync();
+        for (int j = lane; j < C; j += 64) {                                     // max-blur (mip_methods.py:61-66)
+            const float cw = wraw[j];
+            const float front = (j == 0) ? cw : fmaxf(wraw[j - 1], cw);
+            const float rear = (j == C - 1) ? cw : fmaxf(cw, wraw[j + 1]);
+            if (j >= 1 && j <= C - 2) pw[j - 1] = 0.5f * (front + rear) + a.alpha;   // pdf over weights[1:-1]
+        }
+        for (int j = lane; j < C - 1; j += 64) bins[j] = 0.5f * (xl[j + 1] + xl[j]);   // mid-points of the coordinates
+        lds_wave_sync();
+        float* out = a.z_fine + n * K;
+        wave_inverse_sample(pw, bins, C - 2, cdf, samp, bel, sortbuf, [=](int, int k) { return uu[k]; }, K, 1, WARPED ? sf : out, nullptr, nullptr);
+        if (WARPED) {
+            lds_wave_sync();
+            for (int k = lane; k < K; k += 64) {
+                const float sv = sf[k];
+                if (a.s_fine) a.s_fine[n * K + k] = sv;
+                out[k] = warp_s_to_z(sv, c);
+            }
+        }
+        cur = nxt;
+    }
+}
+
 // ---------------------------------------------------------------------------------------- row 10
 struct CompositeArgs {
     const float* rgbo; const float* z; int z_stride; const float* dirs; int dirs_stride; int64_t N; int S;
@@ -1879,6 +1992,7 @@ static size_t wave_rows_bytes(size_t floats_per_wave) { return WAVES_PER_BLOCK *
 size_t nk::sk_inverse_sample_lds_bytes(int C, int K) { return wave_rows_bytes(inv_lds_floats(C, K)); }
 size_t nk::sk_resample_lds_bytes(int C, int K) { return wave_rows_bytes(rs_lds_floats(C, K)); }
 size_t nk::sk_warped_resample_lds_bytes(int C, int K) { return wave_rows_bytes(warped_lds_floats(C, K)); }
+size_t nk::sk_resample_window_lds_bytes(int C, int K, int warped) { return wave_rows_bytes(rsw_lds_floats(C, K, warped != 0)); }
 size_t nk::sk_get_bounds_lds_bytes(int C) { return wave_rows_bytes(gb_lds_floats((size_t)C)); }
 size_t nk::sk_get_bounds_backward_lds_bytes(int K) { return wave_rows_bytes(gbb_lds_words((size_t)K)); }
 size_t nk::sk_merge_sorted_lds_bytes(int K, int C, int order) { return wave_rows_bytes(merge_lds_floats((size_t)K, (size_t)C, order != 0)); }
@@ -2060,6 +2174,21 @@ int nk::sk_warped_resample(const float* density, const float* s_c, const float* 
     WarpedResampleArgs a{density, s_c, dirs, dirs_stride, u_inv, N, C, K, softplus, alpha, WarpConsts{near, far, gn, gf}, z_fine, s_fine, below, w_prop,
                          rng_seed, rng_ray_offset};
     hipLaunchKernelGGL(warped_resample_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), sk_warped_resample_lds_bytes(C, K), st, a);
+    return (int)hipGetLastError();
+}
+// ---- the second proposal round: explicit depths, in-kernel uniforms of columns u_col0 .. u_col0 + K - 1 of the inverse-CDF stream ----
+int nk::sk_resample_window(const float* density, const float* z, const float* dirs, int dirs_stride, int64_t N, int C, int K, int u_col0, float alpha,
+                       uint64_t rng_seed, int64_t rng_ray_offset, float* z_fine, hipStream_t st) {
+    if (N == 0) return 0;
+    ResampleWindowArgs a{density, z, dirs, dirs_stride, N, C, K, u_col0, alpha, WarpConsts{}, z_fine, nullptr, rng_seed, rng_ray_offset};
+    hipLaunchKernelGGL(resample_window_kernel<false>, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), sk_resample_window_lds_bytes(C, K, 0), st, a);
+    return (int)hipGetLastError();
+}
+int nk::sk_warped_resample_window(const float* density, const float* s_c, const float* dirs, int dirs_stride, int64_t N, int C, int K, int u_col0, float alpha,
+                              float near, float far, float gn, float gf, uint64_t rng_seed, int64_t rng_ray_offset, float* z_fine, float* s_fine, hipStream_t st) {
+    if (N == 0) return 0;
+    ResampleWindowArgs a{density, s_c, dirs, dirs_stride, N, C, K, u_col0, alpha, WarpConsts{near, far, gn, gf}, z_fine, s_fine, rng_seed, rng_ray_offset};
+    hipLaunchKernelGGL(resample_window_kernel<true>, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), sk_resample_window_lds_bytes(C, K, 1), st, a);
     return (int)hipGetLastError();
 }
 int nk::sk_composite(const float* rgbo, const float* z, int z_stride, const float* dirs, int dirs_stride, int64_t N, int S, int flags,

@@ -915,6 +915,43 @@ def render_rays_warped(packed_prop, packed_mip, precision, rays, u_strat, u_inv,
     return rgb, depth, w, workspace
 
 
+ROUNDS_PNUM_MIN, ROUNDS_PNUM_MAX = 3, 256      # prop_pnum of nerf_amd_render_rays_rounds (include/nerf_amd.h)
+
+
+def render_rays_rounds(packed_prop, packed_mip, precision, rays, z_base, n_fine, near, far, white_bkg, *, prop_pnum, seed, rng_ray_offset: int = 0,
+                       spacing: str = "linear", contract: bool = False, ipe_radius: Optional[float] = None, ipe_dir_norm: Optional[torch.Tensor] = None,
+                       want_depth=True, want_weights=False, workspace: Optional[torch.Tensor] = None):
+    """ops.render_rays / ops.render_rays_warped with Mip-NeRF 360's two proposal rounds (nerf_amd_render_rays_rounds): explicit rays (N,6),
+    in-kernel Philox uniforms of ``seed`` only.  ``prop_pnum`` (3..256) sorted depths are resampled from the first histogram with columns
+    [0, prop_pnum) of each ray's inverse-CDF stream, the proposal network is evaluated there, and the n_fine + 1 fine depths are drawn from
+    that second histogram with columns [prop_pnum, prop_pnum + n_fine + 1).  ``z_base`` (64) is read under spacing="linear" only; under
+    "disparity" ``depth`` is W^-1 of the expected metric depth.  -> (rgb, depth | None, weights | None, workspace)"""
+    rays = _dev(rays, "rays")
+    dev = rays.device
+    N = rays.shape[0]
+    kind = _spacing_kind(spacing)
+    if kind == _lib.SPACING_LINEAR:
+        z_base = _dev(z_base, "z_base")
+    camera = Samples()                                       # carries only the flags and the Philox key next to explicit rays
+    camera.contract = int(bool(contract))
+    camera.rng_seed, camera.rng_ray_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(rng_ray_offset)
+    dir_norm = None                                          # a converted copy lives in this local until the call has returned: the descriptor holds only its address
+    if ipe_radius is not None:
+        camera.ipe, camera.ipe_radius = 1, float(ipe_radius)
+        dir_norm = _dev(ipe_dir_norm, "ipe_dir_norm") if ipe_dir_norm is not None else None
+        camera.ipe_dir_norm = dir_norm.data_ptr() if dir_norm is not None else None
+    need = lib.nerf_amd_render_rounds_workspace_bytes(N, int(n_fine), int(prop_pnum), kind)
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    rgb = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    depth = torch.empty((N,), dtype=torch.float32, device=dev) if want_depth else None
+    w = torch.empty((N, n_fine), dtype=torch.float32, device=dev) if want_weights else None
+    check(lib.nerf_amd_render_rays_rounds(_ptr(packed_prop), _ptr(packed_mip), _prop_prec(packed_prop, precision, packed_mip), _ptr(rays), C.byref(camera), 0,
+                                          _ptr(z_base) if kind == _lib.SPACING_LINEAR else None, N, int(n_fine), int(prop_pnum), kind, float(near), float(far),
+                                          int(white_bkg), _ptr(rgb), _ptr(depth), _ptr(w), _ptr(workspace), _stream()), "nerf_amd_render_rays_rounds")
+    return rgb, depth, w, workspace
+
+
 def render_rays_ref(packed_prop, packed_ref, precision, rays, z_base, u_strat, u_inv, n_fine, near, far, white_bkg,
                     want_depth=True, cam_dir: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
                     camera: Optional[Samples] = None, ray_offset: int = 0, n_rays: Optional[int] = None, flags: int = 0,

@@ -167,8 +167,9 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
     raises; "linear" takes up to 1023).
     ``prop_rounds`` (keyword-only; an addition): 2 = Mip-NeRF 360's two proposal rounds, for a model trained with
     ``TrainStep(prop_rounds=2)``: ``prop_pnum`` (default: the 64 coarse samples' count) sorted depths are resampled from the first proposal
-    histogram, the same proposal network is evaluated there, and the fine depths are drawn from that second histogram.  Every network
-    then takes the call-by-call route (no fused two-round entry point: well below the fused rate, profiles/interlevel_summary.md);
+    histogram, the same proposal network is evaluated there, and the fine depths are drawn from that second histogram.  Compiled-shape
+    networks with 3 <= prop_pnum <= 256 go through nerf_amd_render_rays_rounds under both spacings (profiles/two_round_render_summary.md);
+    layer-by-layer networks and other histogram sizes take the call-by-call route, which computes the same image on the same streams;
     ``rng="philox"`` only -- each ray's inverse-CDF stream simply has prop_pnum more columns, still a pure function of (seed, global ray
     index), so shards reproduce the whole image bit for bit; not available for Ref-NeRF."""
     if prop_rounds not in (1, 2):
@@ -225,8 +226,13 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
         ipe_radius = (2.0 / (12.0 ** 0.5) / fx) if ipe is True else float(ipe)
     generic = network._generic() or prop_net._generic()
     warped = _check_spacing(spacing, near, far)
-    if prop_rounds == 2:
-        # no fused two-round entry point: the tile body call by call for every network, on the Philox streams of the global ray index
+    if prop_rounds == 2 and not generic and ops.ROUNDS_PNUM_MIN <= prop_pnum <= ops.ROUNDS_PNUM_MAX:
+        # both rounds behind one entry point (nerf_amd_render_rays_rounds): the same kernels on the same Philox columns as the tile body below
+        rgb, depth, _, _ = ops.render_rays_rounds(prop_net.packed(prec), network.packed(prec, wide=bool(ipe)), prec, rays, z_base, sample_num, near, far,
+                                                  white_bkg, prop_pnum=prop_pnum, seed=seed, rng_ray_offset=off, spacing=spacing, contract=contract,
+                                                  ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, want_depth=bool(render_depth))
+    elif prop_rounds == 2:
+        # a generic network, or a histogram size outside the entry point's: the tile body call by call, on the Philox streams of the global ray index
         rgb, depth, _ = _render_rays_by_calls(network, prop_net, rays, z_base, None, None, sample_num, near, far, white_bkg, bool(render_depth),
                                               seed=seed, ray_offset=off, contract=contract, ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm,
                                               spacing=spacing, prop_rounds=2, prop_pnum=prop_pnum)
