@@ -667,116 +667,184 @@ int nerf_amd_get_bounds_backward(const int64_t* below, const float* d_bounds, in
 // ------------------------------------------------------------------------------------------------ whole-ray rendering
 namespace {
 constexpr int RENDER_C = 64;                                // procedures.py:22 RENDER_COARSE_PNUM
-// The workspace of the four render entry points, described ONCE: the constructor walks the parts in order, each rounded up to 256 bytes.
+// The workspace of the four render entry points, described ONCE and selected by what varies -- disparity spacing, a second proposal round
+// of P = prop_pnum depths (0: one round), the Ref-NeRF tail: the constructor walks the parts in order, each rounded up to 256 bytes.
 // Walked from NULL it gives the size (nerf_amd_render*_workspace_bytes), from the caller's pointer the parts.
-//   plain:   density (N,64) | z_fine (N, n_fine+1) | rgbo (N, n_fine, 4) | rays (N, 6) | one scalar slot (direction norm of the IPE mode)
-//   warped:  density | s_c (N,64) | z_c (N,64) | z_fine | rgbo | raw depth (N) | rays | the scalar slot
-//   ref:     density | z_fine | z_coarse (N,64) | z_all (N, n_fine+64) | rgbo (N, n_fine+64, 4) | normals (N, n_fine+64, 3) | rays (unrounded)
-//   rounds (two proposal rounds, P = prop_pnum): plain resp. warped with  density2 (N,P) | z_mid (N,P) [| s_mid (N,P), warped]  in front of z_fine
-enum WsKind { WS_PLAIN, WS_WARPED, WS_REF, WS_ROUNDS, WS_ROUNDS_WARPED };
+//   density (N,64) [| s_c (N,64) | z_c (N,64), warped] [| density2 (N,P) | z_mid (N,P) [| s_mid (N,P), warped], two rounds] | z_fine (N, n_fine+1)
+//   MipNeRF:  | rgbo (N, n_fine, 4) [| raw depth (N), warped] | rays (N, 6) | one scalar slot (direction norm of the IPE mode)
+//   Ref-NeRF: | z_coarse (N,64) | z_all (N, n_fine+64) | rgbo (N, n_fine+64, 4) | normals (N, n_fine+64, 3) | rays (unrounded)
 struct RenderWs {
     float *density, *s_c = nullptr, *z_c = nullptr, *density2 = nullptr, *z_mid = nullptr, *s_mid = nullptr, *z_fine, *z_coarse = nullptr, *z_all = nullptr, *rgbo,
           *normals = nullptr, *depth_raw = nullptr, *rays, *dir_norm;
     size_t bytes;
-    RenderWs(WsKind kind, void* base, int64_t N, int n_fine, int prop_pnum = 0) {
+    RenderWs(bool warped, int prop_pnum, bool ref, void* base, int64_t N, int n_fine) {
         const uintptr_t start = (reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255;
         uintptr_t p = start;
         auto take = [&p](size_t part) { float* r = reinterpret_cast<float*>(p); p += (part + 255) & ~(size_t)255; return r; };
-        const size_t n = (size_t)N, S = (size_t)n_fine + (kind == WS_REF ? RENDER_C : 0);    // samples per ray of the fine pass
-        const bool warped = kind == WS_WARPED || kind == WS_ROUNDS_WARPED, rounds = kind == WS_ROUNDS || kind == WS_ROUNDS_WARPED;
+        const size_t n = (size_t)N, S = (size_t)n_fine + (ref ? RENDER_C : 0);    // samples per ray of the fine pass
         density = take(n * RENDER_C * 4);
         if (warped) { s_c = take(n * RENDER_C * 4); z_c = take(n * RENDER_C * 4); }
-        if (rounds) { density2 = take(n * prop_pnum * 4); z_mid = take(n * prop_pnum * 4); }
-        if (rounds && warped) s_mid = take(n * prop_pnum * 4);
+        if (prop_pnum) { density2 = take(n * prop_pnum * 4); z_mid = take(n * prop_pnum * 4); }
+        if (prop_pnum && warped) s_mid = take(n * prop_pnum * 4);
         z_fine = take(n * (n_fine + 1) * 4);
-        if (kind == WS_REF) { z_coarse = take(n * RENDER_C * 4); z_all = take(n * S * 4); }
+        if (ref) { z_coarse = take(n * RENDER_C * 4); z_all = take(n * S * 4); }
         rgbo = take(n * S * 16);
-        if (kind == WS_REF) normals = take(n * S * 12);
+        if (ref) normals = take(n * S * 12);
         if (warped) depth_raw = take(n * 4);
-        rays = kind == WS_REF ? reinterpret_cast<float*>(p) : take(n * 24);   // ref: the ray table is the unrounded tail
-        dir_norm = reinterpret_cast<float*>(p);             // plain, warped: the scalar slot behind the ray table
-        bytes = (size_t)(p - start) + (kind == WS_REF ? n * 24 + 256 : 512);   // + alignment slack (+ the scalar slot)
+        rays = ref ? reinterpret_cast<float*>(p) : take(n * 24);   // ref: the ray table is the unrounded tail
+        dir_norm = reinterpret_cast<float*>(p);             // MipNeRF: the scalar slot behind the ray table
+        bytes = (size_t)(p - start) + (ref ? n * 24 + 256 : 512);   // + alignment slack (+ the scalar slot)
     }
 };
-size_t render_ws_bytes(WsKind kind, int64_t N, int n_fine) { return (N < 0 || n_fine < 1) ? 0 : RenderWs(kind, nullptr, N, n_fine).bytes; }
+size_t render_ws_bytes(bool warped, bool ref, int64_t N, int n_fine) { return (N < 0 || n_fine < 1) ? 0 : RenderWs(warped, 0, ref, nullptr, N, n_fine).bytes; }
 
-// ---- what the render entry points check and do alike ----
-int check_render_inputs(bool have_all, const float* rays, const nerf_amd_samples* camera, const float* u_strat, const float* u_inv) {
-    if (!have_all) return fail(NERF_AMD_EINVAL, "NULL argument");   // (have_all: none of the entry point's own required pointers is NULL)
-    if ((u_strat == nullptr) != (u_inv == nullptr)) return fail(NERF_AMD_EINVAL, "u_strat and u_inv are both given or both NULL (in-kernel uniforms)");
-    if (!u_strat && !camera) return fail(NERF_AMD_EINVAL, "in-kernel uniforms need the descriptor (rng_seed, rng_ray_offset)");
-    if (!rays && !camera) return fail(NERF_AMD_EINVAL, "need rays or camera");
+// One call of any of the four entry points.  The MipNeRF pipeline (render_mip) is: ray table -> direction norm (IPE) -> coarse draw +
+// proposal pass -> resampling [-> second proposal pass -> second resampling] -> fine pass -> compositing [-> depth un-warp]; an entry point
+// fixes `warped`, `prop_pnum` and where the uniforms come from.  Ref-NeRF shares everything up to the first resampling.
+struct RenderPlan {
+    const void *packed_prop, *packed_fine;
+    int precision, lflags;                                  // lflags: the layout bits, split off `precision` by check_plan_shape
+    const float* rays;
+    const nerf_amd_samples* camera;
+    int64_t ray_offset;
+    const float *z_base, *u_strat, *u_inv;                  // z_base: linear spacing only; u_* = NULL: Philox streams of (seed(), ray + ray0())
+    int64_t N;
+    int n_fine, prop_pnum;                                  // prop_pnum = 0: one proposal round
+    bool warped, ref;
+    float near, far, gn, gf;                                // gn, gf: check_spacing (warped)
+    int white_bkg;
+    float *rgb, *depth, *weights;
+    bool ipe() const { return !ref && camera && camera->ipe; }
+    uint64_t seed() const { return camera ? camera->rng_seed : 0; }     // (read only when a uniform tensor is NULL)
+    int64_t ray0() const { return camera ? camera->rng_ray_offset : 0; }
+    RenderWs ws(void* base) const { return RenderWs(warped, prop_pnum, ref, base, N, n_fine); }
+};
+
+// ---- the checks: everything is refused here, before the first launch ----
+// what must hold even for N == 0: precision and layout bits, sizes, and that every resampling launch fits the LDS
+int check_plan_shape(RenderPlan& p, int layouts, const char* bad_precision) {
+    if (split_precision(p.precision, p.lflags, layouts)) return fail(NERF_AMD_EINVAL, bad_precision);
+    if ((p.lflags & NERF_AMD_FINE_W128) && p.ipe()) return fail(NERF_AMD_EINVAL, "the 128-wide fine layout has no integrated-PE kernel: pack the network 256-wide");
+    if (p.N < 0 || p.n_fine < 1 || p.n_fine > 1023) return fail(NERF_AMD_EINVAL, "bad N or n_fine");
+    const int K = p.n_fine + 1, K1 = p.prop_pnum ? p.prop_pnum : K;                  // depths drawn by the first resampling
+    if (int e = p.warped ? check_warped_resample_shape(RENDER_C, K1) : check_lds(sk_resample_lds_bytes(RENDER_C, K1), "prop_pnum")) return e;
+    return p.prop_pnum ? check_lds(sk_resample_window_lds_bytes(p.prop_pnum, K, p.warped ? 1 : 0), "prop_pnum and n_fine") : NERF_AMD_OK;
+}
+// what a call with rays to render needs: its pointers, a source of rays and of uniforms, a usable IPE descriptor
+int check_plan_inputs(const RenderPlan& p, const void* workspace) {
+    if (!(p.packed_prop && p.packed_fine && (p.warped || p.z_base) && p.rgb && workspace)) return fail(NERF_AMD_EINVAL, "NULL argument");
+    if ((p.u_strat == nullptr) != (p.u_inv == nullptr)) return fail(NERF_AMD_EINVAL, "u_strat and u_inv are both given or both NULL (in-kernel uniforms)");
+    if (!p.u_strat && !p.camera) return fail(NERF_AMD_EINVAL, "in-kernel uniforms need the descriptor (rng_seed, rng_ray_offset)");
+    if (!p.rays && !p.camera) return fail(NERF_AMD_EINVAL, "need rays or camera");
+    if (p.warped && p.ipe() && !p.rays) return fail(NERF_AMD_EINVAL, "integrated PE needs an explicit ray table");
+    if (!p.rays && (p.camera->H <= 0 || p.camera->W <= 0 || p.ray_offset < 0 || p.ray_offset + p.N > (int64_t)p.camera->H * p.camera->W))
+        return fail(NERF_AMD_EINVAL, "ray range outside the camera image");
+    if (p.ipe() && !(p.camera->ipe_radius > 0.0f)) return fail(NERF_AMD_EINVAL, "integrated PE needs a positive ipe_radius");
     return NERF_AMD_OK;
 }
+
+// ---- the stages: each exists once ----
 // row 1 (procedures.py:43-51,64): without a ray table, the camera's rays ray_offset .. ray_offset + N - 1 are generated into the workspace
-int provide_rays(const float*& rays, const nerf_amd_samples* camera, int64_t ray_offset, int64_t N, float* gen, hipStream_t st) {
-    if (rays) return NERF_AMD_OK;
-    if (camera->H <= 0 || camera->W <= 0 || ray_offset < 0 || ray_offset + N > (int64_t)camera->H * camera->W) return fail(NERF_AMD_EINVAL, "ray range outside the camera image");
-    if (int e = sk_generate_rays(camera->pose, camera->H, camera->W, camera->fx, camera->fy, ray_offset, N, gen, st)) return hip_status(e, "ray generation");
-    rays = gen;
-    return NERF_AMD_OK;
+int provide_rays(const RenderPlan& p, const RenderWs& ws, hipStream_t st, const float** rays) {
+    *rays = p.rays ? p.rays : ws.rays;
+    if (p.rays) return NERF_AMD_OK;
+    const nerf_amd_samples* c = p.camera;
+    return hip_status(sk_generate_rays(c->pose, c->H, c->W, c->fx, c->fy, p.ray_offset, p.N, ws.rays, st), "ray generation");
 }
-// row 12 inside the fine pass (IPE mode; else *dir_norm = NULL): the direction norm of this ray batch, into `slot` (`scratch`, the density
-// buffer, is free until the proposal pass writes it: room for the 256 fp64 workgroup partials when N >= 8).  A caller that renders a SHARD
-// of a ray list hands over the norm of the whole list (camera->ipe_dir_norm): mip_methods.py:31 norms all rays of the reference's call.
-int provide_dir_norm(const nerf_amd_samples* camera, const float* rays, int64_t N, float* slot, void* scratch, hipStream_t st, const float** dir_norm) {
-    *dir_norm = nullptr;
-    if (!camera || !camera->ipe) return NERF_AMD_OK;
-    if (!(camera->ipe_radius > 0.0f)) return fail(NERF_AMD_EINVAL, "integrated PE needs a positive ipe_radius");
-    *dir_norm = camera->ipe_dir_norm ? camera->ipe_dir_norm : slot;
-    if (camera->ipe_dir_norm) return NERF_AMD_OK;
-    return hip_status((N >= 8) ? sk_dirs_norm_scratch(rays, N, slot, scratch, st) : sk_dirs_norm(rays, N, slot, st), "direction norm");
+// row 12 inside the fine pass (IPE mode; else *dir_norm = NULL): the direction norm of this ray batch, into the workspace's scalar slot (the
+// density buffer is free until the proposal pass writes it: room for the 256 fp64 workgroup partials when N >= 8).  A caller that renders a
+// SHARD of a ray list hands over the norm of the whole list (camera->ipe_dir_norm): mip_methods.py:31 norms all rays of the reference's call.
+int provide_dir_norm(const RenderPlan& p, const float* rays, const RenderWs& ws, hipStream_t st, const float** dir_norm) {
+    *dir_norm = !p.ipe() ? nullptr : (p.camera->ipe_dir_norm ? p.camera->ipe_dir_norm : ws.dir_norm);
+    if (*dir_norm != ws.dir_norm) return NERF_AMD_OK;
+    return hip_status((p.N >= 8) ? sk_dirs_norm_scratch(rays, p.N, ws.dir_norm, ws.density, st) : sk_dirs_norm(rays, p.N, ws.dir_norm, st), "direction norm");
 }
 // S samples per ray at the depths z (row stride z_stride); the descriptor may accompany explicit rays just to carry `contract`
-nerf_amd_samples ray_samples(const float* rays, int64_t N, int S, const float* z, int z_stride, const nerf_amd_samples* camera) {
+nerf_amd_samples ray_samples(const RenderPlan& p, const float* rays, int S, const float* z, int z_stride) {
     nerf_amd_samples s{};
-    s.mode = 1; s.rays = rays; s.S = S; s.M = N * S; s.z = z; s.z_stride = z_stride; s.contract = camera ? camera->contract : 0;
+    s.mode = 1; s.rays = rays; s.S = S; s.M = p.N * S; s.z = z; s.z_stride = z_stride; s.contract = p.camera ? p.camera->contract : 0;
     return s;
 }
-// rows 2-7 under linear spacing: stratified z fused into the proposal MLP, then weights -> max-blur(0.01) -> inverse sampling of n_fine + 1
-// sorted depths (procedures.py:59,68-70); ws.z_coarse (Ref-NeRF) also receives the stratified depths the proposal pass used
-int coarse_pass(int lflags, const void* packed_prop, int precision, const float* rays, const nerf_amd_samples* camera, const float* z_base, const float* u_strat,
-                const float* u_inv, int64_t N, int n_fine, float near, float far, const RenderWs& ws, hipStream_t st) {
-    const float jitter = (far - near) / (float)n_fine;      // procedures.py:59
-    nerf_amd_samples sc = ray_samples(rays, N, RENDER_C, nullptr, RENDER_C, camera);
-    sc.z_base = z_base; sc.u = u_strat; sc.z_jitter = jitter;
-    sc.rng_seed = camera ? camera->rng_seed : 0; sc.rng_ray_offset = camera ? camera->rng_ray_offset : 0;   // (read only when u_strat == NULL)
-    if (int e = launch_proposal_any(lflags, packed_prop, precision, sc, ws.density, st)) return hip_status(e, "proposal MLP");
-    return hip_status(sk_resample(ws.density, nullptr, z_base, u_strat, jitter, rays + 3, 6, u_inv, N, RENDER_C, n_fine + 1, 0, 0.01f, sc.rng_seed, sc.rng_ray_offset,
-                                  ws.z_fine, nullptr, nullptr, ws.z_coarse, st), "resample");
+// rows 2-7: the coarse draw and the proposal pass, then weights -> max-blur(0.01) -> inverse sampling of K sorted depths into z_out
+// (procedures.py:59,68-70).  Linear spacing: the stratified z is fused into the proposal MLP, and ws.z_coarse (Ref-NeRF) also receives the
+// depths it used.  Disparity spacing: the draw happens in s (no position tensor: the proposal MLP forms o + z d itself), s_out receives the
+// resampled s next to z_out = W(s).
+int coarse_pass(const RenderPlan& p, const float* rays, int K, float* z_out, float* s_out, const RenderWs& ws, hipStream_t st) {
+    constexpr int C = RENDER_C;
+    if (p.warped) {
+        if (int e = sk_warped_stratified(rays, p.u_strat, p.N, C, p.seed(), p.ray0(), p.near, p.far, p.gn, p.gf, ws.s_c, ws.z_c, nullptr, st))
+            return hip_status(e, "warped stratified draw");
+        const nerf_amd_samples sc = ray_samples(p, rays, C, ws.z_c, C);
+        if (int e = launch_proposal_any(p.lflags, p.packed_prop, p.precision, sc, ws.density, st)) return hip_status(e, "proposal MLP");
+        return hip_status(sk_warped_resample(ws.density, ws.s_c, rays + 3, 6, p.u_inv, p.N, C, K, 0, 0.01f, p.near, p.far, p.gn, p.gf, p.seed(), p.ray0(), z_out, s_out,
+                                             nullptr, nullptr, st), "warped resample");
+    }
+    const float jitter = (p.far - p.near) / (float)p.n_fine;      // procedures.py:59
+    nerf_amd_samples sc = ray_samples(p, rays, C, nullptr, C);
+    sc.z_base = p.z_base; sc.u = p.u_strat; sc.z_jitter = jitter; sc.rng_seed = p.seed(); sc.rng_ray_offset = p.ray0();
+    if (int e = launch_proposal_any(p.lflags, p.packed_prop, p.precision, sc, ws.density, st)) return hip_status(e, "proposal MLP");
+    return hip_status(sk_resample(ws.density, nullptr, p.z_base, p.u_strat, jitter, rays + 3, 6, p.u_inv, p.N, C, K, 0, 0.01f, p.seed(), p.ray0(), z_out, nullptr, nullptr,
+                                  ws.z_coarse, st), "resample");
+}
+// the second round: the proposal network at the first round's P depths, then the n_fine + 1 fine depths from that histogram with columns
+// [P, P + n_fine + 1) of each ray's inverse-CDF stream (the first round used [0, P))
+int second_round(const RenderPlan& p, const float* rays, const RenderWs& ws, hipStream_t st) {
+    const int P = p.prop_pnum, K = p.n_fine + 1;
+    const nerf_amd_samples mid = ray_samples(p, rays, P, ws.z_mid, P);
+    if (int e = launch_proposal_any(p.lflags, p.packed_prop, p.precision, mid, ws.density2, st)) return hip_status(e, "proposal MLP, second round");
+    if (p.warped)
+        return hip_status(sk_warped_resample_window(ws.density2, ws.s_mid, rays + 3, 6, p.N, P, K, P, 0.01f, p.near, p.far, p.gn, p.gf, p.seed(), p.ray0(), ws.z_fine,
+                                                    nullptr, st), "warped resample, second round");
+    return hip_status(sk_resample_window(ws.density2, ws.z_mid, rays + 3, 6, p.N, P, K, P, 0.01f, p.seed(), p.ray0(), ws.z_fine, st), "resample, second round");
 }
 // rows 8-9: drop the last depth, length2pts fused into the fine MLP (`dir_norm`: integrated PE, frustum s = [z_fine[s], z_fine[s+1]])
-int fine_pass(int lflags, const void* packed_mip, int precision, const float* rays, const nerf_amd_samples* camera, int64_t N, int n_fine, const float* dir_norm,
-              const RenderWs& ws, hipStream_t st) {
-    nerf_amd_samples sf = ray_samples(rays, N, n_fine, ws.z_fine, n_fine + 1, camera);
-    if (dir_norm) { sf.ipe = 1; sf.ipe_radius = camera->ipe_radius; sf.ipe_dir_norm = dir_norm; }
-    return hip_status(launch_mip_any(lflags, packed_mip, precision, sf, ws.rgbo, st), "fine MLP");
+int fine_pass(const RenderPlan& p, const float* rays, const float* dir_norm, const RenderWs& ws, hipStream_t st) {
+    nerf_amd_samples sf = ray_samples(p, rays, p.n_fine, ws.z_fine, p.n_fine + 1);
+    if (dir_norm) { sf.ipe = 1; sf.ipe_radius = p.camera->ipe_radius; sf.ipe_dir_norm = dir_norm; }
+    return hip_status(launch_mip_any(p.lflags, p.packed_fine, p.precision, sf, ws.rgbo, st), "fine MLP");
+}
+// row 10.  Rows 9 and 10 are two launches: measured 2-3 % faster than the fused epilogue of nerf_amd_mip_forward_composite on MI355X
+// (DESIGN.md section 3.3), and the composite kernel's HBM rate stays individually measurable.  Disparity spacing: composited with near = 0,
+// far = 1 -- the kernel's depth is then the raw expected metric depth sum w z |d| -- and un-warped by one more launch.
+int composite_pass(const RenderPlan& p, const float* rays, const RenderWs& ws, hipStream_t st) {
+    const int flags = 1 | (p.white_bkg ? 2 : 0);
+    const bool unwarp = p.warped && p.depth;
+    if (int e = sk_composite(ws.rgbo, ws.z_fine, p.n_fine + 1, rays + 3, 6, p.N, p.n_fine, flags, NERF_AMD_ACT_RELU, 0.0f, p.warped ? 0.0f : p.near,
+                             p.warped ? 1.0f : p.far, nullptr, nullptr, p.rgb, p.weights, unwarp ? ws.depth_raw : p.depth, nullptr, st)) return hip_status(e, "composite");
+    return unwarp ? hip_status(sk_warp_depths(ws.depth_raw, nullptr, p.N, 1, 1, p.near, p.far, p.gn, p.gf, p.depth, nullptr, st), "depth un-warp") : NERF_AMD_OK;
+}
+// the three MipNeRF entry points behind their own checks: shape, N == 0, inputs, then the launches in pipeline order
+int render_mip(RenderPlan& p, void* workspace, hipStream_t st) {
+    if (int e = check_plan_shape(p, NERF_AMD_PROP_W128 | NERF_AMD_FINE_W128, "unknown precision")) return e;
+    if (p.N == 0) return NERF_AMD_OK;
+    if (int e = check_plan_inputs(p, workspace)) return e;
+    const RenderWs ws = p.ws(workspace);
+    const float *rays, *dir_norm;
+    if (int e = provide_rays(p, ws, st, &rays)) return e;
+    if (int e = provide_dir_norm(p, rays, ws, st, &dir_norm)) return e;
+    const int P = p.prop_pnum;
+    if (int e = coarse_pass(p, rays, P ? P : p.n_fine + 1, P ? ws.z_mid : ws.z_fine, P ? ws.s_mid : nullptr, ws, st)) return e;
+    if (P)
+        if (int e = second_round(p, rays, ws, st)) return e;
+    if (int e = fine_pass(p, rays, dir_norm, ws, st)) return e;
+    return composite_pass(p, rays, ws, st);
+}
+// the sizes nerf_amd_render_rays_rounds takes, for the entry point and its workspace query alike: NULL, or what is wrong
+const char* rounds_shape_error(int64_t N, int n_fine, int prop_pnum, int spacing) {
+    if (spacing != NERF_AMD_SPACING_LINEAR && spacing != NERF_AMD_SPACING_DISPARITY) return "unknown spacing (NERF_AMD_SPACING_LINEAR or NERF_AMD_SPACING_DISPARITY)";
+    if (N < 0 || n_fine < 1 || n_fine > 1023) return "bad N or n_fine (1 <= n_fine <= 1023)";
+    if (prop_pnum < 3 || prop_pnum > 256) return "bad prop_pnum (3 <= prop_pnum <= 256: the second round's histogram)";
+    return nullptr;
 }
 }  // namespace
 
-size_t nerf_amd_render_workspace_bytes(int64_t N, int n_fine) { return render_ws_bytes(WS_PLAIN, N, n_fine); }
+size_t nerf_amd_render_workspace_bytes(int64_t N, int n_fine) { return render_ws_bytes(false, false, N, n_fine); }
 int nerf_amd_render_rays(const void* packed_prop, const void* packed_mip, int precision, const float* rays, const nerf_amd_samples* camera,
                          int64_t ray_offset, const float* z_base, const float* u_strat, const float* u_inv, int64_t N, int n_fine, float near, float far,
                          int white_bkg, float* rgb, float* depth, float* weights, void* workspace, void* stream) {
-    int lflags;
-    if (split_precision(precision, lflags, NERF_AMD_PROP_W128 | NERF_AMD_FINE_W128)) return fail(NERF_AMD_EINVAL, "unknown precision");
-    if ((lflags & NERF_AMD_FINE_W128) && camera && camera->ipe) return fail(NERF_AMD_EINVAL, "the 128-wide fine layout has no integrated-PE kernel: pack the network 256-wide");
-    if (N < 0 || n_fine < 1 || n_fine > 1023) return fail(NERF_AMD_EINVAL, "bad N or n_fine");
-    if (N == 0) return NERF_AMD_OK;
-    if (int e = check_render_inputs(packed_prop && packed_mip && z_base && rgb && workspace, rays, camera, u_strat, u_inv)) return e;
-    const RenderWs ws(WS_PLAIN, workspace, N, n_fine);
-    hipStream_t st = S(stream);
-    if (int e = provide_rays(rays, camera, ray_offset, N, ws.rays, st)) return e;
-    const float* dir_norm;
-    if (int e = provide_dir_norm(camera, rays, N, ws.dir_norm, ws.density, st, &dir_norm)) return e;
-    if (int e = coarse_pass(lflags, packed_prop, precision, rays, camera, z_base, u_strat, u_inv, N, n_fine, near, far, ws, st)) return e;
-    // rows 9 and 10 as two launches: measured 2-3 % faster than the fused epilogue of nerf_amd_mip_forward_composite on
-    // MI355X, and the composite kernel's HBM rate stays individually measurable
-    if (int e = fine_pass(lflags, packed_mip, precision, rays, camera, N, n_fine, dir_norm, ws, st)) return e;
-    const int flags = 1 | (white_bkg ? 2 : 0);              // row 10
-    if (int e = sk_composite(ws.rgbo, ws.z_fine, n_fine + 1, rays + 3, 6, N, n_fine, flags, NERF_AMD_ACT_RELU, 0.0f, near, far, nullptr,
-                             nullptr, rgb, weights, depth, nullptr, st)) return hip_status(e, "composite");
-    return NERF_AMD_OK;
+    RenderPlan p{packed_prop, packed_mip, precision, 0, rays, camera, ray_offset, z_base, u_strat, u_inv, N, n_fine, 0, false, false, near, far, 0.0f, 0.0f,
+                 white_bkg, rgb, depth, weights};
+    return render_mip(p, workspace, S(stream));
 }
 
 // ------------------------------------------------------------------------------------------------ disparity ray spacing
@@ -813,146 +881,57 @@ int nerf_amd_warped_resample(const float* density, const float* s_c, const float
                                          rng_ray_offset, z_fine, s_fine, below, w_prop, S(stream)), "nerf_amd_warped_resample");
 }
 
-size_t nerf_amd_render_warped_workspace_bytes(int64_t N, int n_fine) { return render_ws_bytes(WS_WARPED, N, n_fine); }
+size_t nerf_amd_render_warped_workspace_bytes(int64_t N, int n_fine) { return render_ws_bytes(true, false, N, n_fine); }
 int nerf_amd_render_rays_warped(const void* packed_prop, const void* packed_mip, int precision, const float* rays, const nerf_amd_samples* camera,
                                 int64_t ray_offset, const float* u_strat, const float* u_inv, int64_t N, int n_fine, int spacing, float near, float far,
                                 int white_bkg, float* rgb, float* depth, float* weights, void* workspace, void* stream) {
-    int lflags;
-    const bool bad_precision = split_precision(precision, lflags, NERF_AMD_PROP_W128 | NERF_AMD_FINE_W128);
-    float gn, gf;
-    if (int e = check_spacing(spacing, near, far, &gn, &gf)) return e;
-    if (bad_precision) return fail(NERF_AMD_EINVAL, "unknown precision");
-    if ((lflags & NERF_AMD_FINE_W128) && camera && camera->ipe) return fail(NERF_AMD_EINVAL, "the 128-wide fine layout has no integrated-PE kernel: pack the network 256-wide");
-    if (N < 0 || n_fine < 1 || n_fine > 1023) return fail(NERF_AMD_EINVAL, "bad N or n_fine");
-    constexpr int C = RENDER_C;
-    if (int e = check_warped_resample_shape(C, n_fine + 1)) return e;
-    if (N == 0) return NERF_AMD_OK;
-    if (int e = check_render_inputs(packed_prop && packed_mip && rgb && workspace, rays, camera, u_strat, u_inv)) return e;
-    if (camera && camera->ipe && !rays) return fail(NERF_AMD_EINVAL, "integrated PE needs an explicit ray table");
-    const uint64_t seed = camera ? camera->rng_seed : 0;
-    const int64_t ray0 = camera ? camera->rng_ray_offset : 0;
-    const RenderWs ws(WS_WARPED, workspace, N, n_fine);
-    hipStream_t st = S(stream);
-    if (int e = provide_rays(rays, camera, ray_offset, N, ws.rays, st)) return e;
-    const float* dir_norm;
-    if (int e = provide_dir_norm(camera, rays, N, ws.dir_norm, ws.density, st, &dir_norm)) return e;
-    // the coarse draw in s and its metric depths (no position tensor: the proposal MLP forms o + z d itself)
-    if (int e = sk_warped_stratified(rays, u_strat, N, C, seed, ray0, near, far, gn, gf, ws.s_c, ws.z_c, nullptr, st)) return hip_status(e, "warped stratified draw");
-    const nerf_amd_samples sc = ray_samples(rays, N, C, ws.z_c, C, camera);
-    if (int e = launch_proposal_any(lflags, packed_prop, precision, sc, ws.density, st)) return hip_status(e, "proposal MLP");
-    if (int e = sk_warped_resample(ws.density, ws.s_c, rays + 3, 6, u_inv, N, C, n_fine + 1, 0, 0.01f, near, far, gn, gf, seed, ray0, ws.z_fine, nullptr, nullptr,
-                                   nullptr, st)) return hip_status(e, "warped resample");
-    if (int e = fine_pass(lflags, packed_mip, precision, rays, camera, N, n_fine, dir_norm, ws, st)) return e;
-    const int flags = 1 | (white_bkg ? 2 : 0);
-    // near = 0, far = 1: the composite kernel's depth is then the raw expected metric depth sum w z |d|
-    if (int e = sk_composite(ws.rgbo, ws.z_fine, n_fine + 1, rays + 3, 6, N, n_fine, flags, NERF_AMD_ACT_RELU, 0.0f, 0.0f, 1.0f, nullptr, nullptr, rgb, weights,
-                             depth ? ws.depth_raw : nullptr, nullptr, st)) return hip_status(e, "composite");
-    if (depth) {
-        if (int e = sk_warp_depths(ws.depth_raw, nullptr, N, 1, 1, near, far, gn, gf, depth, nullptr, st)) return hip_status(e, "depth un-warp");
-    }
-    return NERF_AMD_OK;
+    RenderPlan p{packed_prop, packed_mip, precision, 0, rays, camera, ray_offset, nullptr, u_strat, u_inv, N, n_fine, 0, true, false, near, far, 0.0f, 0.0f,
+                 white_bkg, rgb, depth, weights};
+    if (int e = check_spacing(spacing, near, far, &p.gn, &p.gf)) return e;
+    return render_mip(p, workspace, S(stream));
 }
 
 // ------------------------------------------------------------------------------------------------ two proposal rounds
-static bool bad_rounds_shape(int64_t N, int n_fine, int prop_pnum, int spacing) {
-    return N < 0 || n_fine < 1 || n_fine > 1023 || prop_pnum < 3 || prop_pnum > 256 || (spacing != NERF_AMD_SPACING_LINEAR && spacing != NERF_AMD_SPACING_DISPARITY);
-}
 size_t nerf_amd_render_rounds_workspace_bytes(int64_t N, int n_fine, int prop_pnum, int spacing) {
-    if (bad_rounds_shape(N, n_fine, prop_pnum, spacing)) return 0;
-    return RenderWs(spacing == NERF_AMD_SPACING_DISPARITY ? WS_ROUNDS_WARPED : WS_ROUNDS, nullptr, N, n_fine, prop_pnum).bytes;
+    return rounds_shape_error(N, n_fine, prop_pnum, spacing) ? 0 : RenderWs(spacing == NERF_AMD_SPACING_DISPARITY, prop_pnum, false, nullptr, N, n_fine).bytes;
 }
 int nerf_amd_render_rays_rounds(const void* packed_prop, const void* packed_mip, int precision, const float* rays, const nerf_amd_samples* camera,
                                 int64_t ray_offset, const float* z_base, int64_t N, int n_fine, int prop_pnum, int spacing, float near, float far, int white_bkg,
                                 float* rgb, float* depth, float* weights, void* workspace, void* stream) {
-    int lflags;
-    if (split_precision(precision, lflags, NERF_AMD_PROP_W128 | NERF_AMD_FINE_W128)) return fail(NERF_AMD_EINVAL, "unknown precision");
-    if (spacing != NERF_AMD_SPACING_LINEAR && spacing != NERF_AMD_SPACING_DISPARITY)
-        return fail(NERF_AMD_EINVAL, "unknown spacing (NERF_AMD_SPACING_LINEAR or NERF_AMD_SPACING_DISPARITY)");
-    const bool warped = spacing == NERF_AMD_SPACING_DISPARITY;
-    float gn = 0.0f, gf = 0.0f;
-    if (warped)
-        if (int e = check_spacing(spacing, near, far, &gn, &gf)) return e;
-    if ((lflags & NERF_AMD_FINE_W128) && camera && camera->ipe) return fail(NERF_AMD_EINVAL, "the 128-wide fine layout has no integrated-PE kernel: pack the network 256-wide");
-    if (N < 0 || n_fine < 1 || n_fine > 1023) return fail(NERF_AMD_EINVAL, "bad N or n_fine (1 <= n_fine <= 1023)");
-    if (prop_pnum < 3 || prop_pnum > 256) return fail(NERF_AMD_EINVAL, "bad prop_pnum (3 <= prop_pnum <= 256: the second round's histogram)");
-    constexpr int C = RENDER_C;
-    const int P = prop_pnum, K = n_fine + 1;
-    if (warped) {
-        if (int e = check_warped_resample_shape(C, P)) return e;
-        if (int e = check_lds(sk_resample_window_lds_bytes(P, K, 1), "prop_pnum and n_fine")) return e;
-    } else {
-        if (int e = check_lds(sk_resample_lds_bytes(C, P), "prop_pnum")) return e;
-        if (int e = check_lds(sk_resample_window_lds_bytes(P, K, 0), "prop_pnum and n_fine")) return e;
-    }
-    if (N == 0) return NERF_AMD_OK;
-    if (!camera) return fail(NERF_AMD_EINVAL, "NULL argument: in-kernel uniforms need the descriptor (rng_seed, rng_ray_offset)");
-    if (int e = check_render_inputs(packed_prop && packed_mip && (warped || z_base) && rgb && workspace, rays, camera, nullptr, nullptr)) return e;
-    if (warped && camera->ipe && !rays) return fail(NERF_AMD_EINVAL, "integrated PE needs an explicit ray table");
-    const uint64_t seed = camera->rng_seed;
-    const int64_t ray0 = camera->rng_ray_offset;
-    const RenderWs ws(warped ? WS_ROUNDS_WARPED : WS_ROUNDS, workspace, N, n_fine, P);
-    hipStream_t st = S(stream);
-    if (int e = provide_rays(rays, camera, ray_offset, N, ws.rays, st)) return e;
-    const float* dir_norm;
-    if (int e = provide_dir_norm(camera, rays, N, ws.dir_norm, ws.density, st, &dir_norm)) return e;
-    const nerf_amd_samples mid = ray_samples(rays, N, P, ws.z_mid, P, camera);      // the second proposal pass: P samples per ray at the first round's depths
-    if (warped) {
-        if (int e = sk_warped_stratified(rays, nullptr, N, C, seed, ray0, near, far, gn, gf, ws.s_c, ws.z_c, nullptr, st)) return hip_status(e, "warped stratified draw");
-        const nerf_amd_samples sc = ray_samples(rays, N, C, ws.z_c, C, camera);
-        if (int e = launch_proposal_any(lflags, packed_prop, precision, sc, ws.density, st)) return hip_status(e, "proposal MLP");
-        // columns [0, P) of the inverse-CDF stream -> s_mid, z_mid = W(s_mid)
-        if (int e = sk_warped_resample(ws.density, ws.s_c, rays + 3, 6, nullptr, N, C, P, 0, 0.01f, near, far, gn, gf, seed, ray0, ws.z_mid, ws.s_mid, nullptr, nullptr,
-                                       st)) return hip_status(e, "warped resample");
-        if (int e = launch_proposal_any(lflags, packed_prop, precision, mid, ws.density2, st)) return hip_status(e, "proposal MLP, second round");
-        // columns [P, P + n_fine + 1)
-        if (int e = sk_warped_resample_window(ws.density2, ws.s_mid, rays + 3, 6, N, P, K, P, 0.01f, near, far, gn, gf, seed, ray0, ws.z_fine, nullptr, st))
-            return hip_status(e, "warped resample, second round");
-    } else {
-        const float jitter = (far - near) / (float)n_fine;      // procedures.py:59
-        nerf_amd_samples sc = ray_samples(rays, N, C, nullptr, C, camera);
-        sc.z_base = z_base; sc.z_jitter = jitter; sc.rng_seed = seed; sc.rng_ray_offset = ray0;
-        if (int e = launch_proposal_any(lflags, packed_prop, precision, sc, ws.density, st)) return hip_status(e, "proposal MLP");
-        if (int e = sk_resample(ws.density, nullptr, z_base, nullptr, jitter, rays + 3, 6, nullptr, N, C, P, 0, 0.01f, seed, ray0, ws.z_mid, nullptr, nullptr, nullptr,
-                                st)) return hip_status(e, "resample");
-        if (int e = launch_proposal_any(lflags, packed_prop, precision, mid, ws.density2, st)) return hip_status(e, "proposal MLP, second round");
-        if (int e = sk_resample_window(ws.density2, ws.z_mid, rays + 3, 6, N, P, K, P, 0.01f, seed, ray0, ws.z_fine, st)) return hip_status(e, "resample, second round");
-    }
-    if (int e = fine_pass(lflags, packed_mip, precision, rays, camera, N, n_fine, dir_norm, ws, st)) return e;
-    const int flags = 1 | (white_bkg ? 2 : 0);
-    // warped: near = 0, far = 1 -- the composite kernel's depth is then the raw expected metric depth sum w z |d|, un-warped below
-    if (int e = sk_composite(ws.rgbo, ws.z_fine, K, rays + 3, 6, N, n_fine, flags, NERF_AMD_ACT_RELU, 0.0f, warped ? 0.0f : near, warped ? 1.0f : far, nullptr, nullptr,
-                             rgb, weights, (warped && depth) ? ws.depth_raw : depth, nullptr, st)) return hip_status(e, "composite");
-    if (warped && depth) {
-        if (int e = sk_warp_depths(ws.depth_raw, nullptr, N, 1, 1, near, far, gn, gf, depth, nullptr, st)) return hip_status(e, "depth un-warp");
-    }
-    return NERF_AMD_OK;
+    if (const char* bad_shape = rounds_shape_error(N, n_fine, prop_pnum, spacing)) return fail(NERF_AMD_EINVAL, bad_shape);
+    RenderPlan p{packed_prop, packed_mip, precision, 0, rays, camera, ray_offset, z_base, nullptr, nullptr, N, n_fine, prop_pnum,
+                 spacing == NERF_AMD_SPACING_DISPARITY, false, near, far, 0.0f, 0.0f, white_bkg, rgb, depth, weights};
+    if (p.warped)
+        if (int e = check_spacing(spacing, near, far, &p.gn, &p.gf)) return e;
+    if (N && !camera) return fail(NERF_AMD_EINVAL, "NULL argument: in-kernel uniforms need the descriptor (rng_seed, rng_ray_offset)");
+    return render_mip(p, workspace, S(stream));
 }
 
-size_t nerf_amd_render_ref_workspace_bytes(int64_t N, int n_fine) { return render_ws_bytes(WS_REF, N, n_fine); }
+size_t nerf_amd_render_ref_workspace_bytes(int64_t N, int n_fine) { return render_ws_bytes(false, true, N, n_fine); }
 int nerf_amd_render_rays_ref(const void* packed_prop, const void* packed_ref, int precision, int ref_flags, const float* rays, const nerf_amd_samples* camera,
                              int64_t ray_offset, const float* z_base, const float* u_strat, const float* u_inv, int64_t N, int n_fine, float near, float far,
                              int white_bkg, const float* cam_dir, float* rgb, float* depth, float* normal_img, void* workspace, void* stream) {
-    int lflags;
-    if (split_precision(precision, lflags, NERF_AMD_PROP_W128) || bad_ref_flags(ref_flags)) return fail(NERF_AMD_EINVAL, "unknown precision or ref_flags");
-    if (N < 0 || n_fine < 1 || n_fine > 1023) return fail(NERF_AMD_EINVAL, "bad N or n_fine");
+    RenderPlan p{packed_prop, packed_ref, precision, 0, rays, camera, ray_offset, z_base, u_strat, u_inv, N, n_fine, 0, false, true, near, far, 0.0f, 0.0f,
+                 white_bkg, rgb, depth, nullptr};
+    if (bad_ref_flags(ref_flags)) return fail(NERF_AMD_EINVAL, "unknown precision or ref_flags");
+    if (int e = check_plan_shape(p, NERF_AMD_PROP_W128, "unknown precision or ref_flags")) return e;
     if (N == 0) return NERF_AMD_OK;
-    if (int e = check_render_inputs(packed_prop && packed_ref && z_base && rgb && workspace, rays, camera, u_strat, u_inv)) return e;
+    if (int e = check_plan_inputs(p, workspace)) return e;
     if ((normal_img != nullptr) != (cam_dir != nullptr)) return fail(NERF_AMD_EINVAL, "normal_img and cam_dir go together");
     constexpr int C = RENDER_C;
     const int S_all = n_fine + C;                           // (n_fine + 1) fine + 64 coarse depths, the last one dropped
-    const RenderWs ws(WS_REF, workspace, N, n_fine);
+    const RenderWs ws = p.ws(workspace);
     hipStream_t st = S(stream);
-    if (int e = provide_rays(rays, camera, ray_offset, N, ws.rays, st)) return e;
-    if (int e = coarse_pass(lflags, packed_prop, precision, rays, camera, z_base, u_strat, u_inv, N, n_fine, near, far, ws, st)) return e;
+    if (int e = provide_rays(p, ws, st, &rays)) return e;
+    if (int e = coarse_pass(p, rays, n_fine + 1, ws.z_fine, nullptr, ws, st)) return e;
     // row 8, Ref-NeRF branch (procedures.py:71-74): fine and coarse depths merged, the last one dropped
     if (int e = sk_merge_sorted(ws.z_fine, ws.z_coarse, N, n_fine + 1, C, ws.z_all, st)) return hip_status(e, "depth merge");
-    const nerf_amd_samples sf = ray_samples(rays, N, S_all, ws.z_all, S_all, camera);   // row 13
+    const nerf_amd_samples sf = ray_samples(p, rays, S_all, ws.z_all, S_all);   // row 13
     float* normals = normal_img ? ws.normals : nullptr;
-    if (int e = mlp_launch_ref(packed_ref, precision, sf, ws.rgbo, normals, nullptr, ref_flags, st)) return hip_status(e, "Ref-NeRF MLP");
+    if (int e = mlp_launch_ref(packed_ref, p.precision, sf, ws.rgbo, normals, nullptr, ref_flags, st)) return hip_status(e, "Ref-NeRF MLP");
     const int flags = 1 | (white_bkg ? 2 : 0);              // row 10 with sigma -> softplus(sigma + 0.5) (procedures.py:73)
-    if (int e = sk_composite(ws.rgbo, ws.z_all, S_all, rays + 3, 6, N, S_all, flags, NERF_AMD_ACT_SOFTPLUS, 0.5f, near, far, normals, cam_dir, rgb, nullptr, depth,
-                             normal_img, st)) return hip_status(e, "composite");
-    return NERF_AMD_OK;
+    return hip_status(sk_composite(ws.rgbo, ws.z_all, S_all, rays + 3, 6, N, S_all, flags, NERF_AMD_ACT_SOFTPLUS, 0.5f, near, far, normals, cam_dir, rgb, nullptr, depth,
+                                   normal_img, st), "composite");
 }
 
 size_t nerf_amd_gemm_workspace_bytes(int64_t M, int64_t N, int64_t P) {

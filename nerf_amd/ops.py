@@ -768,6 +768,49 @@ def resample(density, z, z_base, u_strat, z_jitter, rays, u_inv, K, softplus=Fal
     return z_fine, below, w, zc
 
 
+def _render_batch(rays, z_base, u_strat, u_inv, seed, n_rays):
+    """The uniforms of a render call, explicit (both tensors) or Philox (both None, with a `seed`) -> (u_strat, u_inv, seed | None, device, N)"""
+    if u_strat is None:
+        if u_inv is not None or seed is None:
+            raise ValueError("nerf_amd: u_strat and u_inv are both tensors, or both None with a `seed`")
+        dev = rays.device if rays is not None else z_base.device
+        N = rays.shape[0] if n_rays is None else n_rays
+        return None, None, seed, dev, N
+    u_strat, u_inv = _dev(u_strat, "u_strat"), (_dev(u_inv, "u_inv") if u_inv is not None else None)
+    return u_strat, u_inv, None, u_strat.device, (u_strat.shape[0] if n_rays is None else n_rays)
+
+
+def _render_descriptor(camera: Optional[Samples], contract, ipe_radius, ipe_dir_norm, seed, rng_ray_offset):
+    """The descriptor of a render call: the caller's `camera`, or a new one when a flag or the Philox key needs a carrier next to explicit
+    rays (else None).  contract: True / False is written, None leaves the descriptor's flag alone; ipe_radius: the integrated PE;
+    seed: the Philox key, None with explicit uniforms.  -> (descriptor | None, keepalive): the descriptor holds only the ADDRESS of the
+    direction norm -- the caller keeps `keepalive`, the converted tensor, until the call has returned."""
+    if camera is None and (contract or ipe_radius is not None or seed is not None):
+        camera = Samples()
+    keepalive = None
+    if camera is not None:
+        if contract is not None:
+            camera.contract = int(bool(contract))
+        if ipe_radius is not None:
+            # the direction norm of mip_methods.py:31 is over ALL rays of the reference's call: a caller holding only a shard of them
+            # passes the whole list's norm (ops.dirs_norm of it); default = the norm of the call's rays, computed by the entry point
+            keepalive = _dev(ipe_dir_norm, "ipe_dir_norm") if ipe_dir_norm is not None else None
+            camera.ipe, camera.ipe_radius, camera.ipe_dir_norm = 1, float(ipe_radius), (keepalive.data_ptr() if keepalive is not None else None)
+        if seed is not None:
+            camera.rng_seed, camera.rng_ray_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(rng_ray_offset)
+    return camera, keepalive
+
+
+def _render_buffers(need: int, workspace: Optional[torch.Tensor], dev, N: int, want_depth, third_shape):
+    """-> (workspace: the caller's if it holds `need` bytes, else a new one; rgb (N,3); depth (N,) | None; a third output of third_shape | None)"""
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    rgb = torch.empty((N, 3), dtype=torch.float32, device=dev)
+    depth = torch.empty((N,), dtype=torch.float32, device=dev) if want_depth else None
+    third = torch.empty(third_shape, dtype=torch.float32, device=dev) if third_shape is not None else None
+    return workspace, rgb, depth, third
+
+
 def render_rays(packed_prop, packed_mip, precision, rays, z_base, u_strat, u_inv, n_fine, near, far, white_bkg,
                 want_depth=True, want_weights=False, workspace: Optional[torch.Tensor] = None, camera: Optional[Samples] = None,
                 ray_offset: int = 0, n_rays: Optional[int] = None, contract: bool = False, ipe_radius: Optional[float] = None,
@@ -777,36 +820,11 @@ def render_rays(packed_prop, packed_mip, precision, rays, z_base, u_strat, u_inv
     between consecutive fine depths with the integrated PE (mip_methods.py:15-58; explicit `rays` required).
     u_strat = u_inv = None with `seed`: every uniform is drawn inside the kernels (Philox4x32-10 keyed by `seed`, a pure function of
     (ray index + rng_ray_offset, sample)); pass `n_rays` (or rays) for the ray count."""
-    in_kernel_rng = u_strat is None
-    if in_kernel_rng:
-        if u_inv is not None or seed is None:
-            raise ValueError("nerf_amd: u_strat and u_inv are both tensors, or both None with a `seed`")
-        dev = rays.device if rays is not None else z_base.device
-    else:
-        dev = u_strat.device
-    if (contract or ipe_radius is not None or in_kernel_rng) and camera is None:
-        camera = Samples()                                   # carries only the flags next to explicit rays
-    if camera is not None:
-        camera.contract = int(bool(contract))
-        if ipe_radius is not None:
-            if rays is None:
-                raise ValueError("nerf_amd: integrated PE needs an explicit ray table")
-            camera.ipe, camera.ipe_radius = 1, float(ipe_radius)
-            # the direction norm of mip_methods.py:31 is over ALL rays of the reference's call: a caller holding only a shard of them
-            # passes the whole list's norm (ops.dirs_norm of it); default = the norm of `rays`, computed by the entry point
-            camera.ipe_dir_norm = _dev(ipe_dir_norm, "ipe_dir_norm").data_ptr() if ipe_dir_norm is not None else None
-        if in_kernel_rng:
-            camera.rng_seed, camera.rng_ray_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(rng_ray_offset)
-    if n_rays is None:
-        N = u_strat.shape[0] if not in_kernel_rng else rays.shape[0]
-    else:
-        N = n_rays
-    need = lib.nerf_amd_render_workspace_bytes(N, n_fine)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    rgb = torch.empty((N, 3), dtype=torch.float32, device=dev)
-    depth = torch.empty((N,), dtype=torch.float32, device=dev) if want_depth else None
-    w = torch.empty((N, n_fine), dtype=torch.float32, device=dev) if want_weights else None
+    u_strat, u_inv, seed, dev, N = _render_batch(rays, z_base, u_strat, u_inv, seed, n_rays)
+    if ipe_radius is not None and rays is None:
+        raise ValueError("nerf_amd: integrated PE needs an explicit ray table")
+    camera, _keep = _render_descriptor(camera, contract, ipe_radius, ipe_dir_norm, seed, rng_ray_offset)
+    workspace, rgb, depth, w = _render_buffers(lib.nerf_amd_render_workspace_bytes(N, n_fine), workspace, dev, N, want_depth, (N, n_fine) if want_weights else None)
     check(lib.nerf_amd_render_rays(_ptr(packed_prop), _ptr(packed_mip), _prop_prec(packed_prop, precision, packed_mip), _ptr(rays),
                                    C.byref(camera) if camera is not None else None, ray_offset, _ptr(z_base), _ptr(u_strat),
                                    _ptr(u_inv), N, n_fine, float(near), float(far), int(white_bkg), _ptr(rgb), _ptr(depth),
@@ -888,30 +906,15 @@ def render_rays_warped(packed_prop, packed_mip, precision, rays, u_strat, u_inv,
     """ops.render_rays under disparity spacing (nerf_amd_render_rays_warped): explicit rays (N,6); ``depth`` is W^-1 of the expected
     metric depth, in [0, 1].  u_strat = u_inv = None with ``seed``: in-kernel Philox uniforms, as in render_rays.  n_fine <= 623 (the
     resampling kernel's LDS rows, include/nerf_amd.h)."""
-    in_kernel_rng = u_strat is None
-    if in_kernel_rng and (u_inv is not None or seed is None):
-        raise ValueError("nerf_amd: u_strat and u_inv are both tensors, or both None with a `seed`")
     rays = _dev(rays, "rays")
-    dev = rays.device
-    N = rays.shape[0]
-    camera = Samples()                                       # carries only the flags next to explicit rays
-    camera.contract = int(bool(contract))
-    if ipe_radius is not None:
-        camera.ipe, camera.ipe_radius = 1, float(ipe_radius)
-        camera.ipe_dir_norm = _dev(ipe_dir_norm, "ipe_dir_norm").data_ptr() if ipe_dir_norm is not None else None
-    if in_kernel_rng:
-        camera.rng_seed, camera.rng_ray_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(rng_ray_offset)
-    else:
-        u_strat, u_inv = _dev(u_strat, "u_strat"), _dev(u_inv, "u_inv")
-    need = lib.nerf_amd_render_warped_workspace_bytes(N, n_fine)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    rgb = torch.empty((N, 3), dtype=torch.float32, device=dev)
-    depth = torch.empty((N,), dtype=torch.float32, device=dev) if want_depth else None
-    w = torch.empty((N, n_fine), dtype=torch.float32, device=dev) if want_weights else None
+    u_strat, u_inv, seed, dev, N = _render_batch(rays, None, u_strat, u_inv, seed, rays.shape[0])
+    camera, _keep = _render_descriptor(None, contract, ipe_radius, ipe_dir_norm, seed, rng_ray_offset)
+    workspace, rgb, depth, w = _render_buffers(lib.nerf_amd_render_warped_workspace_bytes(N, n_fine), workspace, dev, N, want_depth,
+                                               (N, n_fine) if want_weights else None)
     check(lib.nerf_amd_render_rays_warped(_ptr(packed_prop), _ptr(packed_mip), _prop_prec(packed_prop, precision, packed_mip), _ptr(rays),
-                                          C.byref(camera), 0, _ptr(u_strat), _ptr(u_inv), N, int(n_fine), _spacing_kind(spacing), float(near), float(far),
-                                          int(white_bkg), _ptr(rgb), _ptr(depth), _ptr(w), _ptr(workspace), _stream()), "nerf_amd_render_rays_warped")
+                                          C.byref(camera) if camera is not None else None, 0, _ptr(u_strat), _ptr(u_inv), N, int(n_fine), _spacing_kind(spacing),
+                                          float(near), float(far), int(white_bkg), _ptr(rgb), _ptr(depth), _ptr(w), _ptr(workspace), _stream()),
+          "nerf_amd_render_rays_warped")
     return rgb, depth, w, workspace
 
 
@@ -927,25 +930,13 @@ def render_rays_rounds(packed_prop, packed_mip, precision, rays, z_base, n_fine,
     that second histogram with columns [prop_pnum, prop_pnum + n_fine + 1).  ``z_base`` (64) is read under spacing="linear" only; under
     "disparity" ``depth`` is W^-1 of the expected metric depth.  -> (rgb, depth | None, weights | None, workspace)"""
     rays = _dev(rays, "rays")
-    dev = rays.device
     N = rays.shape[0]
     kind = _spacing_kind(spacing)
     if kind == _lib.SPACING_LINEAR:
         z_base = _dev(z_base, "z_base")
-    camera = Samples()                                       # carries only the flags and the Philox key next to explicit rays
-    camera.contract = int(bool(contract))
-    camera.rng_seed, camera.rng_ray_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(rng_ray_offset)
-    dir_norm = None                                          # a converted copy lives in this local until the call has returned: the descriptor holds only its address
-    if ipe_radius is not None:
-        camera.ipe, camera.ipe_radius = 1, float(ipe_radius)
-        dir_norm = _dev(ipe_dir_norm, "ipe_dir_norm") if ipe_dir_norm is not None else None
-        camera.ipe_dir_norm = dir_norm.data_ptr() if dir_norm is not None else None
-    need = lib.nerf_amd_render_rounds_workspace_bytes(N, int(n_fine), int(prop_pnum), kind)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    rgb = torch.empty((N, 3), dtype=torch.float32, device=dev)
-    depth = torch.empty((N,), dtype=torch.float32, device=dev) if want_depth else None
-    w = torch.empty((N, n_fine), dtype=torch.float32, device=dev) if want_weights else None
+    camera, _keep = _render_descriptor(None, contract, ipe_radius, ipe_dir_norm, seed, rng_ray_offset)
+    workspace, rgb, depth, w = _render_buffers(lib.nerf_amd_render_rounds_workspace_bytes(N, int(n_fine), int(prop_pnum), kind), workspace, rays.device, N,
+                                               want_depth, (N, n_fine) if want_weights else None)
     check(lib.nerf_amd_render_rays_rounds(_ptr(packed_prop), _ptr(packed_mip), _prop_prec(packed_prop, precision, packed_mip), _ptr(rays), C.byref(camera), 0,
                                           _ptr(z_base) if kind == _lib.SPACING_LINEAR else None, N, int(n_fine), int(prop_pnum), kind, float(near), float(far),
                                           int(white_bkg), _ptr(rgb), _ptr(depth), _ptr(w), _ptr(workspace), _stream()), "nerf_amd_render_rays_rounds")
@@ -959,28 +950,12 @@ def render_rays_ref(packed_prop, packed_ref, precision, rays, z_base, u_strat, u
     """The tile body of render_image for a Ref-NeRF fine network (procedures.py:64-85, is_ref_model branch) in six launches.
     `cam_dir` (3,) = render_pose[:, -2] asks for the normal image (procedures.py:79-81).  u_strat = u_inv = None with `seed`: in-kernel
     uniforms as in render_rays."""
-    in_kernel_rng = u_strat is None
-    if in_kernel_rng:
-        if u_inv is not None or seed is None:
-            raise ValueError("nerf_amd: u_strat and u_inv are both tensors, or both None with a `seed`")
-        dev = rays.device if rays is not None else z_base.device
-        if camera is None:
-            camera = Samples()
-        camera.rng_seed, camera.rng_ray_offset = int(seed) & 0xFFFFFFFFFFFFFFFF, int(rng_ray_offset)
-    else:
-        dev = u_strat.device
-    if contract:                                             # Mip-NeRF 360 scene contraction of every sample position (the build's own definition)
-        if camera is None:
-            camera = Samples()
-        camera.contract = 1
-    N = n_rays if n_rays is not None else (rays.shape[0] if in_kernel_rng else u_strat.shape[0])
-    need = lib.nerf_amd_render_ref_workspace_bytes(N, n_fine)
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    rgb = torch.empty((N, 3), dtype=torch.float32, device=dev)
-    depth = torch.empty((N,), dtype=torch.float32, device=dev) if want_depth else None
+    u_strat, u_inv, seed, dev, N = _render_batch(rays, z_base, u_strat, u_inv, seed, n_rays)
+    # contract: Mip-NeRF 360 scene contraction of every sample position (the build's own definition); a caller's descriptor keeps its own flag
+    camera, _keep = _render_descriptor(camera, True if contract else None, None, None, seed, rng_ray_offset)
     cam_dir = _dev(cam_dir, "cam_dir") if cam_dir is not None else None
-    normal_img = torch.empty((N,), dtype=torch.float32, device=dev) if cam_dir is not None else None
+    workspace, rgb, depth, normal_img = _render_buffers(lib.nerf_amd_render_ref_workspace_bytes(N, n_fine), workspace, dev, N, want_depth,
+                                                        (N,) if cam_dir is not None else None)
     check(lib.nerf_amd_render_rays_ref(_ptr(packed_prop), _ptr(packed_ref), _prop_prec(packed_prop, precision), int(flags), _ptr(rays),
                                        C.byref(camera) if camera is not None else None, ray_offset, _ptr(z_base), _ptr(u_strat),
                                        _ptr(u_inv), N, n_fine, float(near), float(far), int(white_bkg), _ptr(cam_dir), _ptr(rgb),

@@ -124,6 +124,30 @@ def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sampl
     return rgb, depth, normal_px
 
 
+def _render_route(is_ref_model: bool, generic: bool, warped: bool, prop_rounds: int, prop_pnum: int) -> str:
+    """Which way render_image renders its rays.  ``generic``: a network the fused kernels have no packed layout for (hidden width > 256,
+    > 10 octaves); ``warped``: disparity spacing.  (Ref-NeRF with two rounds or with the integrated PE is refused before this is asked.)
+
+        generic   prop_rounds          fine network   spacing      route      renders through
+        yes       any                  any            any          "calls"    _render_rays_by_calls: the tile body call by call, layer by layer
+        no        2, prop_pnum 3..256  MipNeRF        any          "rounds"   ops.render_rays_rounds
+        no        2, other prop_pnum   MipNeRF        any          "calls"    (no fused entry point for that histogram size)
+        no        1                    Ref-NeRF       linear       "ref"      ops.render_rays_ref
+        no        1                    Ref-NeRF       disparity    "calls"    (the fused Ref-NeRF entry point has no disparity twin)
+        no        1                    MipNeRF        disparity    "warped"   ops.render_rays_warped
+        no        1                    MipNeRF        linear       "plain"    ops.render_rays
+
+    Every route draws from the same uniforms -- the tensors of rng="reference" / "device", or the Philox streams of the global ray index --
+    so the image does not depend on the route."""
+    if generic:
+        return "calls"
+    if prop_rounds == 2:
+        return "rounds" if ops.ROUNDS_PNUM_MIN <= prop_pnum <= ops.ROUNDS_PNUM_MAX else "calls"
+    if is_ref_model:
+        return "calls" if warped else "ref"
+    return "warped" if warped else "plain"
+
+
 def _check_spacing(spacing, near, far) -> bool:
     """True for "disparity", False for "linear" (which must not reach any of the warped code); anything else raises."""
     if spacing == "linear":
@@ -226,46 +250,29 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
         ipe_radius = (2.0 / (12.0 ** 0.5) / fx) if ipe is True else float(ipe)
     generic = network._generic() or prop_net._generic()
     warped = _check_spacing(spacing, near, far)
-    if prop_rounds == 2 and not generic and ops.ROUNDS_PNUM_MIN <= prop_pnum <= ops.ROUNDS_PNUM_MAX:
-        # both rounds behind one entry point (nerf_amd_render_rays_rounds): the same kernels on the same Philox columns as the tile body below
-        rgb, depth, _, _ = ops.render_rays_rounds(prop_net.packed(prec), network.packed(prec, wide=bool(ipe)), prec, rays, z_base, sample_num, near, far,
-                                                  white_bkg, prop_pnum=prop_pnum, seed=seed, rng_ray_offset=off, spacing=spacing, contract=contract,
-                                                  ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, want_depth=bool(render_depth))
-    elif prop_rounds == 2:
-        # a generic network, or a histogram size outside the entry point's: the tile body call by call, on the Philox streams of the global ray index
-        rgb, depth, _ = _render_rays_by_calls(network, prop_net, rays, z_base, None, None, sample_num, near, far, white_bkg, bool(render_depth),
-                                              seed=seed, ray_offset=off, contract=contract, ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm,
-                                              spacing=spacing, prop_rounds=2, prop_pnum=prop_pnum)
-    elif warped and is_ref_model and not generic:
-        # the fused Ref-NeRF entry point has no disparity twin: the call-by-call tile body on the packed kernels, same Philox streams
+    route = _render_route(is_ref_model, generic, warped, prop_rounds, prop_pnum)
+    cam_dir = render_pose[:, -2].contiguous() if render_normal else None
+    if route == "calls":
         rgb, depth, normal_px = _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, bool(render_depth),
-                                                      is_ref_model=True, cam_dir=render_pose[:, -2].contiguous() if render_normal else None, seed=seed,
-                                                      ray_offset=off, contract=contract, spacing=spacing)
-    elif warped and not generic:
-        rgb, depth, _, _ = ops.render_rays_warped(prop_net.packed(prec), network.packed(prec, wide=bool(ipe)), prec, rays, u_strat, u_inv, sample_num, near,
-                                                  far, white_bkg, want_depth=bool(render_depth), contract=contract, ipe_radius=ipe_radius, seed=seed,
-                                                  rng_ray_offset=off, ipe_dir_norm=ipe_dir_norm, spacing=spacing)
-    elif generic:
-        # a network LARGER than the fused kernels' compiled shapes (hidden width > 256, > 10 octaves): the reference's tile body
-        # (procedures.py:62-85) call by call on the mirrored ops -- the networks run layer by layer (nerf_amd/generic_path.py)
-        rgb, depth, normal_px = _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, bool(render_depth),
-                                                      is_ref_model=is_ref_model,
-                                                      cam_dir=render_pose[:, -2].contiguous() if (render_normal and is_ref_model) else None, seed=seed,
-                                                      ray_offset=off, contract=contract, ipe_radius=ipe_radius,
-                                                      ipe_dir_norm=ipe_dir_norm, spacing=spacing)
-    elif not is_ref_model:
-        # (a narrow fine network has no integrated-PE kernel: with ipe its 256-wide -- zero-padded -- blob is used)
-        rgb, depth, _, _ = ops.render_rays(prop_net.packed(prec), network.packed(prec, wide=bool(ipe)), prec, rays, z_base, u_strat, u_inv,
-                                           sample_num, near, far, white_bkg, want_depth=bool(render_depth), contract=contract,
-                                           ipe_radius=ipe_radius, seed=seed, rng_ray_offset=off, ipe_dir_norm=ipe_dir_norm)
+                                                      is_ref_model=is_ref_model, cam_dir=cam_dir, seed=seed, ray_offset=off, contract=contract,
+                                                      ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, spacing=spacing, prop_rounds=prop_rounds,
+                                                      prop_pnum=prop_pnum)
+    elif route == "ref":
+        # procedures.py:71-74: coarse and fine depths are merged and sorted (a merge of two ascending sets), the last one dropped,
+        # sigma -> softplus(sigma + 0.5) before compositing (nerf_amd_render_rays_ref: six launches)
+        rgb, depth, normal_px, _ = ops.render_rays_ref(prop_net.packed(prec), network.packed(prec), prec, rays, z_base, u_strat, u_inv, sample_num, near, far,
+                                                       white_bkg, want_depth=bool(render_depth), cam_dir=cam_dir, flags=network.kernel_flags, seed=seed,
+                                                       contract=contract, rng_ray_offset=off)
     else:
-        # Ref-NeRF branch (procedures.py:71-74): coarse and fine depths are merged and sorted, the last one dropped,
-        # sigma -> softplus(sigma + 0.5) before compositing (nerf_amd_render_rays_ref: six launches; the sort is a merge of two
-        # ascending sets).
-        rgb, depth, normal_px, _ = ops.render_rays_ref(prop_net.packed(prec), network.packed(prec), prec, rays, z_base, u_strat, u_inv,
-                                                       sample_num, near, far, white_bkg, want_depth=bool(render_depth),
-                                                       cam_dir=render_pose[:, -2].contiguous() if render_normal else None, flags=network.kernel_flags,
-                                                       seed=seed, contract=contract, rng_ray_offset=off)
+        # (a narrow fine network has no integrated-PE kernel: with ipe its 256-wide -- zero-padded -- blob is used)
+        packed = (prop_net.packed(prec), network.packed(prec, wide=bool(ipe)), prec, rays)
+        common = dict(want_depth=bool(render_depth), contract=contract, ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, seed=seed, rng_ray_offset=off)
+        if route == "rounds":
+            rgb, depth, _, _ = ops.render_rays_rounds(*packed, z_base, sample_num, near, far, white_bkg, prop_pnum=prop_pnum, spacing=spacing, **common)
+        elif route == "warped":
+            rgb, depth, _, _ = ops.render_rays_warped(*packed, u_strat, u_inv, sample_num, near, far, white_bkg, spacing=spacing, **common)
+        else:
+            rgb, depth, _, _ = ops.render_rays(*packed, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, **common)
 
     def to_image(t, ch):
         if sz is None:

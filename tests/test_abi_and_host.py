@@ -443,7 +443,18 @@ def test_render_workspace_sizes_are_the_documented_closed_forms():
                 assert table[name]["%d,%d" % (N, F)] == want, (name, N, F)
                 assert getattr(_lib.lib, name)(N, F) == want, (name, N, F)
                 n_checked += 1
-    assert n_checked == 72 and sum(len(t) for t in table.values()) == 72
+    # ... and the two-round query, recorded before the entry points were folded into one pipeline: density2 | z_mid (N,P each) join the plain
+    # parts in front of z_fine, under disparity spacing also s_mid (N,P)
+    rounds = "nerf_amd_render_rounds_workspace_bytes"
+    for N in (-1, 0, 1, 7, 1000, 640000):
+        for F in (0, 1, 128, 1023):
+            for P in (3, 64, 256):
+                for spacing, one_round in ((0, "nerf_amd_render_workspace_bytes"), (1, "nerf_amd_render_warped_workspace_bytes")):
+                    want = 0 if N < 0 or F < 1 else _WORKSPACE_FORMS[one_round](N, F) + (2 + spacing) * _ws256(N * P * 4)
+                    assert table[rounds]["%d,%d,%d,%d" % (N, F, P, spacing)] == want, (N, F, P, spacing)
+                    assert _lib.lib.nerf_amd_render_rounds_workspace_bytes(N, F, P, spacing) == want, (N, F, P, spacing)
+                    n_checked += 1
+    assert n_checked == 72 + 144 and sum(len(t) for t in table.values()) == 72 + 144
 
 
 def test_shapes_whose_launch_exceeds_the_lds_are_refused_before_any_hip_call():
