@@ -84,6 +84,7 @@ int         nerf_amd_device_info(int* n_cu, int* arch_is_gfx950);
  *                                   (procedures.py:43-51)
  * M = total samples = N*S in modes 1/2.
  * ------------------------------------------------------------------------------------------------ */
+#define NERF_AMD_CONTRACT_GAUSSIAN 2 /* nerf_amd_samples.contract: contract the frustum mean AND its covariance (integrated PE) */
 typedef struct nerf_amd_samples {
     int32_t      mode;
     int32_t      S;            /* samples per ray (modes 1, 2)                 */
@@ -101,7 +102,13 @@ typedef struct nerf_amd_samples {
     float        pose[12];     /* mode 2: row-major 3x4 camera-to-world (host) */
     int32_t      contract;     /* != 0: Mip-NeRF 360 scene contraction of the sample POSITION before it is encoded
                                   (Barron et al. 2022, eq. 10): x -> x if |x| <= 1 else (2 - 1/|x|) x/|x|.  Not in the
-                                  reference (BASELINE config 5 only); occupies former tail padding, 0 = off.        */
+                                  reference (BASELINE config 5 only); occupies former tail padding, 0 = off.
+                                  NERF_AMD_CONTRACT_GAUSSIAN (2; meaningful with `ipe` on the MipNeRF kernels): the frustum's whole
+                                  Gaussian goes through the linearised contraction (eq. 11-14): mu' = f(mu), Sigma' = J Sigma J^T,
+                                  and the encoder attenuates with diag Sigma' -- with 1 only the mean is contracted and the
+                                  covariance stays metric.  Inside the unit ball both are the same bits.  Every point-encoding
+                                  kernel (proposal, Ref-NeRF, MipNeRF without `ipe` inside a render) reads 2 as 1; the entry
+                                  points refuse any other value, and 2 on a bare MipNeRF descriptor without `ipe`.  */
     int32_t      ipe;          /* != 0 (modes 1 with z only, MipNeRF kernels): integrated positional encoding.  Sample s of ray n is the
                                   conical frustum between z[n*z_stride+s] and z[n*z_stride+s+1] (so z rows hold S+1 depths); the network
                                   input is [mu | ipe_feature(mu, diag Sigma)] (mip_methods.py:15-58) instead of [x | PE(x)].        */
@@ -185,6 +192,12 @@ int nerf_amd_ipe_feature(const float* z, const float* rays, int64_t N, int S, in
  * The layer-by-layer route of networks larger than the compiled shapes encodes with it. */
 int nerf_amd_ipe_feature_contracted(const float* z, const float* rays, int64_t N, int S, int L, float r, const float* dir_norm,
                                     float* feat, float* mu, float* mu_t, void* stream);
+/* (ABI 125, additive) the same with the whole Gaussian contracted (Mip-NeRF 360 eq. 11-14; nerf_amd_samples.contract =
+ * NERF_AMD_CONTRACT_GAUSSIAN): mu' = contract(mu) as above, and the attenuation reads diag(J Sigma J^T) with
+ * Sigma = (var_t - var_r / dir_norm) d d^T + var_r I and J the contraction's Jacobian at the metric mean.  Frusta
+ * whose metric mean lies inside the unit ball give the bits of nerf_amd_ipe_feature_contracted. */
+int nerf_amd_ipe_feature_gaussian(const float* z, const float* rays, int64_t N, int S, int L, float r, const float* dir_norm,
+                                  float* feat, float* mu, float* mu_t, void* stream);
 /* coneParameters (mip_methods.py:15-23): z (N, S+1) -> mu_t, sigma_t^2, sigma_r^2, each (N, S). */
 int nerf_amd_cone_parameters(const float* z, int64_t N, int S, float r, float* mu_t, float* var_t, float* var_r, void* stream);
 /* sqrt(sum of squares) of the direction halves of rays (N,6) -> out (1 float on the device); fp64 accumulation, fixed order. */

@@ -19,6 +19,7 @@ PROP_W128 = 0x100     # layout flag OR-ed into `precision`: packed_prop is a NET
 ACT_RELU, ACT_IDENTITY, ACT_SOFTPLUS = 0, 1, 2
 SPACING_LINEAR, SPACING_DISPARITY = 0, 1   # NERF_AMD_SPACING_*: "disparity" = the Mip-NeRF 360 s-space entry points (nerf_amd_warp*)
 SPACINGS = {"linear": SPACING_LINEAR, "disparity": SPACING_DISPARITY}
+CONTRACT_GAUSSIAN = 2  # NERF_AMD_CONTRACT_GAUSSIAN: nerf_amd_samples.contract that also contracts the frustum covariance (integrated PE)
 
 c_float_p = C.POINTER(C.c_float)
 c_void = C.c_void_p
@@ -51,6 +52,7 @@ SIGNATURES = {
     "nerf_amd_positional_encoding": (C.c_int, [c_void, i64, C.c_int, c_void, c_void]),
     "nerf_amd_ipe_feature": (C.c_int, [c_void, c_void, i64, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void, c_void, c_void]),
     "nerf_amd_ipe_feature_contracted": (C.c_int, [c_void, c_void, i64, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void, c_void, c_void]),
+    "nerf_amd_ipe_feature_gaussian": (C.c_int, [c_void, c_void, i64, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void, c_void, c_void]),
     "nerf_amd_cone_parameters": (C.c_int, [c_void, i64, C.c_int, C.c_float, c_void, c_void, c_void, c_void]),
     "nerf_amd_dirs_norm": (C.c_int, [c_void, i64, c_void, c_void]),
     "nerf_amd_generate_rays": (C.c_int, [c_float_p, C.c_int, C.c_int, C.c_float, C.c_float, i64, i64, c_void, c_void]),
@@ -151,7 +153,8 @@ SIGNATURES = {
 
 
 # additive entry points that a library named by NERF_AMD_LIB may predate
-ADDED_AFTER_125 = ("nerf_amd_direction_table", "nerf_amd_render_rounds_workspace_bytes", "nerf_amd_render_rays_rounds")
+ADDED_AFTER_125 = ("nerf_amd_direction_table", "nerf_amd_render_rounds_workspace_bytes", "nerf_amd_render_rays_rounds",
+                   "nerf_amd_ipe_feature_gaussian")
 
 
 def _load():

@@ -38,12 +38,18 @@ int check_samples(const nerf_amd_samples* s, bool need_dir) {
     } else {
         return fail(NERF_AMD_EINVAL, "unknown sample mode");
     }
+    if (s->contract < 0 || s->contract > NERF_AMD_CONTRACT_GAUSSIAN) return fail(NERF_AMD_EINVAL, "contract must be 0, 1 or NERF_AMD_CONTRACT_GAUSSIAN");
     if (s->ipe) {
         if (!need_dir) return fail(NERF_AMD_EUNSUPPORTED, "integrated PE is wired for the MipNeRF kernel only");
         if (s->mode != 1 || !s->z || s->z_stride < s->S + 1) return fail(NERF_AMD_EINVAL, "integrated PE needs mode 1 with S+1 depths per ray (z, z_stride > S)");
         if (!s->ipe_dir_norm || !(s->ipe_radius > 0.0f)) return fail(NERF_AMD_EINVAL, "integrated PE needs ipe_dir_norm (device) and a positive ipe_radius");
     }
     return NERF_AMD_OK;
+}
+// a bare descriptor for the MipNeRF network: the Gaussian contraction acts on the frustum of the integrated PE and has no meaning without it
+// (the proposal and Ref-NeRF kernels, and the point-encoding passes of a render, read NERF_AMD_CONTRACT_GAUSSIAN as 1)
+int check_gaussian(const nerf_amd_samples* s) {
+    return (s->contract == NERF_AMD_CONTRACT_GAUSSIAN && !s->ipe) ? fail(NERF_AMD_EINVAL, "contract = NERF_AMD_CONTRACT_GAUSSIAN needs the integrated PE (ipe != 0)") : NERF_AMD_OK;
 }
 bool bad_prec(int p) { return p != NERF_AMD_F32 && p != NERF_AMD_BF16; }
 // layout flags ride above the low byte of a `precision` argument (nerf_amd.h): split them off; true = unknown precision or a flag not in `allowed`
@@ -151,6 +157,7 @@ int nerf_amd_mip_forward(const void* packed, int precision, const nerf_amd_sampl
     int lflags;
     if (split_precision(precision, lflags, NERF_AMD_FINE_W128)) return fail(NERF_AMD_EINVAL, "unknown precision");
     if (int c = check_samples(src, true)) return c;
+    if (int c = check_gaussian(src)) return c;
     if (src->M == 0) return NERF_AMD_OK;
     if (!packed || !rgbo) return fail(NERF_AMD_EINVAL, "NULL argument");
     if ((lflags & NERF_AMD_FINE_W128) && src->ipe) return fail(NERF_AMD_EINVAL, "the 128-wide fine layout has no integrated-PE kernel: pack the network 256-wide");
@@ -171,6 +178,7 @@ int nerf_amd_mip_forward_composite(const void* packed, int precision, const nerf
     if (lflags & NERF_AMD_FINE_W128)
         return fail(NERF_AMD_EUNSUPPORTED, "the 128-wide fine layout has no fused-compositing kernel: use nerf_amd_mip_forward + nerf_amd_composite");
     if (int c = check_samples(src, true)) return c;
+    if (int c = check_gaussian(src)) return c;
     if (src->mode != 1 || !src->z) return fail(NERF_AMD_EUNSUPPORTED, "fused compositing needs mode 1 (rays + z)");
     if (src->ipe) return fail(NERF_AMD_EUNSUPPORTED, "integrated PE: use nerf_amd_mip_forward + nerf_amd_composite");
     if (src->S != 32 && src->S != 64 && src->S != 128) return fail(NERF_AMD_EUNSUPPORTED, "fused compositing needs S in {32, 64, 128}");
@@ -217,6 +225,10 @@ int nerf_amd_ipe_feature(const float* z, const float* rays, int64_t N, int Sn, i
 int nerf_amd_ipe_feature_contracted(const float* z, const float* rays, int64_t N, int Sn, int L, float r, const float* dir_norm, float* feat, float* mu,
                                     float* mu_t, void* stream) {
     return ipe_feature_any(z, rays, N, Sn, L, r, dir_norm, feat, mu, mu_t, 1, stream, "nerf_amd_ipe_feature_contracted");
+}
+int nerf_amd_ipe_feature_gaussian(const float* z, const float* rays, int64_t N, int Sn, int L, float r, const float* dir_norm, float* feat, float* mu,
+                                  float* mu_t, void* stream) {
+    return ipe_feature_any(z, rays, N, Sn, L, r, dir_norm, feat, mu, mu_t, NERF_AMD_CONTRACT_GAUSSIAN, stream, "nerf_amd_ipe_feature_gaussian");
 }
 int nerf_amd_cone_parameters(const float* z, int64_t N, int Sn, float r, float* mu_t, float* var_t, float* var_r, void* stream) {
     if (N < 0 || Sn < 0) return fail(NERF_AMD_EINVAL, "negative size");
@@ -459,6 +471,7 @@ int nerf_amd_mip_forward_train(const void* packed, int precision, const nerf_amd
     if (bad_train_prec(precision)) return fail(NERF_AMD_EINVAL, "bad precision");
     if (src->M && !rgbo) return fail(NERF_AMD_EINVAL, "NULL output");
     if (int c = check_samples(src, true)) return c;         // (every sample mode, integrated PE and scene contraction included)
+    if (int c = check_gaussian(src)) return c;
     return hip_status(mlp_launch_mip_train(packed, precision, *src, rgbo, dump, S(stream)), "nerf_amd_mip_forward_train");
 }
 int nerf_amd_train_dump_to_rows(const void* dump, int net, int precision, int64_t M, int layer, int n_features, void* out, void* stream) {
@@ -726,6 +739,9 @@ int check_plan_shape(RenderPlan& p, int layouts, const char* bad_precision) {
     if (split_precision(p.precision, p.lflags, layouts)) return fail(NERF_AMD_EINVAL, bad_precision);
     if ((p.lflags & NERF_AMD_FINE_W128) && p.ipe()) return fail(NERF_AMD_EINVAL, "the 128-wide fine layout has no integrated-PE kernel: pack the network 256-wide");
     if (p.N < 0 || p.n_fine < 1 || p.n_fine > 1023) return fail(NERF_AMD_EINVAL, "bad N or n_fine");
+    if (p.camera && (p.camera->contract < 0 || p.camera->contract > NERF_AMD_CONTRACT_GAUSSIAN)) return fail(NERF_AMD_EINVAL, "contract must be 0, 1 or NERF_AMD_CONTRACT_GAUSSIAN");
+    if (p.camera && !p.ref && p.camera->contract == NERF_AMD_CONTRACT_GAUSSIAN && !p.camera->ipe)
+        return fail(NERF_AMD_EINVAL, "contract = NERF_AMD_CONTRACT_GAUSSIAN needs the integrated PE (camera->ipe != 0)");
     const int K = p.n_fine + 1, K1 = p.prop_pnum ? p.prop_pnum : K;                  // depths drawn by the first resampling
     if (int e = p.warped ? check_warped_resample_shape(RENDER_C, K1) : check_lds(sk_resample_lds_bytes(RENDER_C, K1), "prop_pnum")) return e;
     return p.prop_pnum ? check_lds(sk_resample_window_lds_bytes(p.prop_pnum, K, p.warped ? 1 : 0), "prop_pnum and n_fine") : NERF_AMD_OK;

@@ -159,6 +159,40 @@ DEVINL void cone_mean_cov(const ConeMoments& c, float o, float d, float dir_norm
     const float dd = d * d;
     diag = c.var_t * dd + c.var_r * (1.0f - dd / dir_norm);
 }
+// The frustum's Gaussian under the Mip-NeRF 360 scene contraction (Barron et al. 2022, eq. 10-14; not in the reference: the build's own
+// definition; NERF_AMD_CONTRACT_GAUSSIAN): the mean goes through the contraction (the bits of contract_position on the
+// metric mean) and the covariance Sigma = (var_t - var_r / dn) d d^T + var_r I through its linearisation, Sigma' = J Sigma J^T, of which
+// the diagonal is returned.  With x the metric mean, n = |x| > 1, xh = x / n, k = (2 - 1/n) / n:
+//   J = k (I - xh xh^T) + xh xh^T / n^2            (tangential scale k, radial scale 1 / n^2)
+//   Jd = k (d - xh (xh.d)) + xh (xh.d) / n^2
+//   (J J^T)_cc = k^2 (xh_a^2 + xh_b^2) + xh_c^2 / n^4            (a, b: the other two coordinates -- no 1 - xh_c^2 cancellation)
+//   var'_c = var_t (Jd)_c^2 + var_r ((J J^T)_cc - (Jd)_c^2 / dn)
+// Written in the tangential / radial split because k d and the x x^T term of J = k I + a x x^T nearly cancel along the ray in fp32.
+// Inside the unit ball J = I: the values of cone_mean_cov are returned untouched, the same bits as with the mean-only contraction.
+// Straight-line code with selects (the lanes of a wave straddle the ball): what is computed for n <= 1 is discarded, nothing traps.
+DEVINL float norm3(float x, float y, float z);
+DEVINL void cone_mean_cov_gaussian(const ConeMoments& c, const float* o, const float* d, float dir_norm, float (&mu)[3], float (&var)[3]) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) cone_mean_cov(c, o[k], d[k], dir_norm, mu[k], var[k]);
+    const float n = norm3(mu[0], mu[1], mu[2]);
+    const bool outside = n > 1.0f;
+    const float t = 1.0f / n;
+    const float kk = (2.0f - t) / n;
+    const float xh[3] = {mu[0] * t, mu[1] * t, mu[2] * t};
+    const float xd = (xh[0] * d[0] + xh[1] * d[1]) + xh[2] * d[2];
+    const float t2 = t * t, k2 = kk * kk;
+    const float rad = xd * t2, t4 = t2 * t2;
+    const float sq[3] = {xh[0] * xh[0], xh[1] * xh[1], xh[2] * xh[2]};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const float jd = kk * (d[k] - xh[k] * xd) + xh[k] * rad;
+        const float jd2 = jd * jd;
+        const float jj = k2 * (sq[(k + 1) % 3] + sq[(k + 2) % 3]) + sq[k] * t4;
+        const float pushed = c.var_t * jd2 + c.var_r * (jj - jd2 / dir_norm);
+        var[k] = outside ? pushed : var[k];
+        mu[k] = outside ? mu[k] * kk : mu[k];
+    }
+}
 
 // ------------------------------------------------------------------------------------------------
 // 64-lane inclusive scans.  fp64 versions mirror torch's CPU cumsum/cumprod, which accumulate float inputs in double and round

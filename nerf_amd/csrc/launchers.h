@@ -56,6 +56,7 @@ size_t sk_get_bounds_lds_bytes(int C);
 size_t sk_get_bounds_backward_lds_bytes(int K);
 size_t sk_merge_sorted_lds_bytes(int K, int C, int order);
 int sk_positional_encoding(const float* x, int64_t M, int L, float* out, hipStream_t st);
+// contract: 0 | 1 (the frustum mean) | NERF_AMD_CONTRACT_GAUSSIAN (mean and covariance) -- nerf_amd_ipe_feature, _contracted, _gaussian
 int sk_ipe_feature(const float* z, const float* rays, int64_t N, int Sn, int L, float r2, const float* dir_norm, float* feat, float* mu, float* mu_t, int contract, hipStream_t st);
 int sk_cone_parameters(const float* z, int64_t N, int Sn, float r2, float* mu_t, float* var_t, float* var_r, hipStream_t st);
 int sk_dirs_norm(const float* rays, int64_t N, float* out, hipStream_t st);

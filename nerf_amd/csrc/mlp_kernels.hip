@@ -238,9 +238,13 @@ DEVINL IpeSample fetch_sample_ipe(const nerf_amd_samples& s, int64_t m) {
     const float rr = s.ipe_radius;
     const ConeMoments c = cone_moments(zz[0], zz[1], (float)((double)rr * (double)rr));
     const float dn = s.ipe_dir_norm[0];
+    r.dx = ry[3]; r.dy = ry[4]; r.dz = ry[5];
+    if (s.contract == NERF_AMD_CONTRACT_GAUSSIAN) {        // mean and covariance through the contraction (wave-uniform)
+        cone_mean_cov_gaussian(c, ry, ry + 3, dn, r.mu, r.var);
+        return r;
+    }
 #pragma unroll
     for (int k = 0; k < 3; ++k) cone_mean_cov(c, ry[k], ry[3 + k], dn, r.mu[k], r.var[k]);
-    r.dx = ry[3]; r.dy = ry[4]; r.dz = ry[5];
     if (s.contract) {                                      // (mean only; the covariance is left in metric space)
         Sample p{r.mu[0], r.mu[1], r.mu[2], 0.0f, 0.0f, 0.0f};
         contract_position(p);

@@ -83,13 +83,20 @@ __global__ __launch_bounds__(256) void ipe_feature_kernel(const float* __restric
             const float* zz = z + n * (S + 1) + si;
             const ConeMoments c = cone_moments(zz[0], zz[1], r2);
             const float* ry = rays + n * 6;
+            if (contract == NERF_AMD_CONTRACT_GAUSSIAN) {    // the whole Gaussian through the contraction: the function of the fused kernels' sample fetch
+                float mu[3], var[3];
+                cone_mean_cov_gaussian(c, ry, ry + 3, dn, mu, var);
 #pragma unroll
-            for (int k = 0; k < 3; ++k) cone_mean_cov(c, ry[k], ry[3 + k], dn, mom[sl][k], mom[sl][3 + k]);
-            if (contract) {                                  // Mip-NeRF 360 contraction of the frustum MEAN (the covariance stays metric): the fused
-                const float nn = norm3(mom[sl][0], mom[sl][1], mom[sl][2]);   // kernels' sample fetch does the same (mlp_kernels.hip contract_position)
-                if (nn > 1.0f) {
-                    const float kk = (2.0f - 1.0f / nn) / nn;
-                    mom[sl][0] *= kk; mom[sl][1] *= kk; mom[sl][2] *= kk;
+                for (int k = 0; k < 3; ++k) { mom[sl][k] = mu[k]; mom[sl][3 + k] = var[k]; }
+            } else {
+#pragma unroll
+                for (int k = 0; k < 3; ++k) cone_mean_cov(c, ry[k], ry[3 + k], dn, mom[sl][k], mom[sl][3 + k]);
+                if (contract) {                              // Mip-NeRF 360 contraction of the frustum MEAN (the covariance stays metric): the fused
+                    const float nn = norm3(mom[sl][0], mom[sl][1], mom[sl][2]);   // kernels' sample fetch does the same (mlp_kernels.hip contract_position)
+                    if (nn > 1.0f) {
+                        const float kk = (2.0f - 1.0f / nn) / nn;
+                        mom[sl][0] *= kk; mom[sl][1] *= kk; mom[sl][2] *= kk;
+                    }
                 }
             }
             if (mu_out) { mu_out[m * 3] = mom[sl][0]; mu_out[m * 3 + 1] = mom[sl][1]; mu_out[m * 3 + 2] = mom[sl][2]; }

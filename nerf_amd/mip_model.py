@@ -129,14 +129,18 @@ class MipNeRF(PackedWeightsMixin, NeRF):
         return ops.mip_forward(self.packed(prec), prec, pts, contract=contract)
 
     def forward_rays(self, rays: torch.Tensor, z: torch.Tensor, n_samples: int, ipe_radius=None, ipe_dir_norm: torch.Tensor = None,
-                     contract: bool = False) -> torch.Tensor:
+                     contract: bool = False, *, ipe_cov: str = "metric") -> torch.Tensor:
         """Same as ``forward(NeRF.length2pts(rays, z[:, :n_samples]))`` without materialising the points -- and the entry of the two
         sample-fetch modes the reference has no caller for:
           * `ipe_radius` (BASELINE configs[2]): integrated PE (mip_methods.py:15-58) of the `n_samples` conical frusta between consecutive
             depths (z has >= n_samples + 1 columns); `ipe_dir_norm` = ops.dirs_norm(rays) (default: computed here);
-          * `contract` (configs[4]): scene contraction of the sample positions (of the frustum means with IPE).
+          * `contract` (configs[4]): scene contraction of the sample positions (of the frustum means with IPE);
+          * `ipe_cov` (keyword-only; with `ipe_radius` and `contract`): "metric" (default) leaves the frustum covariance in metric space,
+            "contracted" pushes it through the linearised contraction with the mean (Mip-NeRF 360 eq. 11-14: Sigma' = J Sigma J^T), on
+            the fused route (nerf_amd_samples.contract = NERF_AMD_CONTRACT_GAUSSIAN) and the layer-by-layer one (nerf_amd_ipe_feature_gaussian).
         Differentiable w.r.t. the parameters (training forward + HIP backward); rays and depths carry no gradient, like the reference's
         detached fine depths (utils.py:35-36)."""
+        contract = ops.ipe_contract(contract, ipe_radius, ipe_cov, "nerf_amd: MipNeRF.forward_rays")
         self._check_config()
         prec = ops.current_precision()
         if rays.requires_grad or z.requires_grad:
@@ -144,11 +148,11 @@ class MipNeRF(PackedWeightsMixin, NeRF):
         if self._generic():
             if ipe_radius is not None:
                 # layer-by-layer route: the stand-alone integrated-PE encoder (nerf_amd_ipe_feature) feeds [frustum mean | feature] to the layers
-                # (with `contract` the encoder contracts the frustum mean itself -- nerf_amd_ipe_feature_contracted, round 6; the layers then
+                # (with `contract` the encoder contracts the frustum mean itself -- nerf_amd_ipe_feature_contracted, round 6; or the whole Gaussian; the layers then
                 #  see [contracted mean | feature] and must NOT contract again)
                 from . import generic_path
                 feat, mu, _ = ops.ipe_feature(z[:, : n_samples + 1].contiguous(), rays, self.position_flevel, float(ipe_radius), ipe_dir_norm,
-                                              contract=bool(contract))
+                                              contract=contract)
                 pts = torch.cat((mu, rays[:, None, 3:6].expand(-1, n_samples, -1)), dim=-1).contiguous()
                 return generic_path.mip_forward(self, pts, encoded_x=feat)
             return self.forward(NeRF.length2pts(rays, z[:, :n_samples].contiguous()), contract=contract)

@@ -185,6 +185,31 @@ def pack_weights(net: int, precision: int, weights: Sequence[torch.Tensor], bias
 
 
 # ------------------------------------------------------------------------------------------------ MLPs
+CONTRACT_GAUSSIAN = _lib.CONTRACT_GAUSSIAN     # `contract` of the ray-descriptor ops: the frustum's covariance is contracted with its mean
+IPE_COVS = ("metric", "contracted")
+
+
+def _contract_mode(contract) -> int:
+    """nerf_amd_samples.contract: CONTRACT_GAUSSIAN passes through, anything else is a truth value (0 / 1) as before."""
+    return CONTRACT_GAUSSIAN if (not isinstance(contract, bool) and isinstance(contract, int) and contract == CONTRACT_GAUSSIAN) else int(bool(contract))
+
+
+def ipe_contract(contract, ipe, ipe_cov: str, who: str = "nerf_amd"):
+    """The `contract` value for the integrated-PE ops from the public arguments: ``ipe_cov="metric"`` (default) returns ``contract`` as
+    it is -- with the integrated PE only the frustum MEAN is contracted and the attenuation reads the metric covariance;
+    ``"contracted"`` (needs ``contract`` and the integrated PE, ``ipe`` truthy / a radius) returns CONTRACT_GAUSSIAN: Mip-NeRF 360's
+    mu' = f(mu), Sigma' = J Sigma J^T.  Anything else raises ValueError."""
+    if ipe_cov not in IPE_COVS:
+        raise ValueError("%s: ipe_cov must be 'metric' or 'contracted' (got %r)" % (who, ipe_cov))
+    if ipe_cov == "metric":
+        return contract
+    if not contract:
+        raise ValueError("%s: ipe_cov='contracted' needs contract=True (it is the scene contraction applied to the frustum covariance)" % who)
+    if not ipe:
+        raise ValueError("%s: ipe_cov='contracted' needs the integrated PE (a point sample has no covariance)" % who)
+    return CONTRACT_GAUSSIAN
+
+
 def _samples_pts(pts: torch.Tensor, stride: int, contract: bool = False) -> Samples:
     s = Samples()
     s.mode = 0
@@ -198,11 +223,12 @@ def _samples_pts(pts: torch.Tensor, stride: int, contract: bool = False) -> Samp
 def samples_rays(rays: torch.Tensor, S: int, z: Optional[torch.Tensor] = None, z_base: Optional[torch.Tensor] = None,
                  u: Optional[torch.Tensor] = None, z_jitter: float = 0.0, contract: bool = False, ipe_radius: Optional[float] = None,
                  ipe_dir_norm: Optional[torch.Tensor] = None, seed: int = 0, rng_ray_offset: int = 0) -> Samples:
-    """`contract`: Mip-NeRF 360 scene contraction of the sample positions before encoding (not in the reference; BASELINE config 5).
+    """`contract`: Mip-NeRF 360 scene contraction of the sample positions before encoding (not in the reference; BASELINE config 5);
+    CONTRACT_GAUSSIAN (with `ipe_radius`): of the frustum's mean AND covariance (include/nerf_amd.h NERF_AMD_CONTRACT_GAUSSIAN).
     `ipe_radius` (with explicit z of S+1 depths per ray): integrated PE of the frusta between consecutive depths (mip_methods.py:15-58);
     `ipe_dir_norm` = ops.dirs_norm(rays) -- the caller keeps that tensor alive until the kernel has run."""
     s = Samples()
-    s.contract = int(bool(contract))
+    s.contract = _contract_mode(contract)
     if ipe_radius is not None:
         if z is None or z.shape[-1] < S + 1 or ipe_dir_norm is None:
             raise ValueError("nerf_amd: integrated PE needs explicit z with S+1 depths per ray and ipe_dir_norm")
@@ -349,7 +375,8 @@ def cone_parameters(z: torch.Tensor, r: float):
 
 def ipe_feature(z: torch.Tensor, rays: torch.Tensor, L: int, r: float, dir_norm: Optional[torch.Tensor] = None, contract: bool = False):
     """ipe_feature (mip_methods.py:47-58): z (N,S+1), rays (N,6) -> feat (N,S,6L), mu (N,S,3), mu_t (N,S).  `contract` (an addition): the
-    frustum mean goes through the Mip-NeRF 360 contraction before the lift (nerf_amd_ipe_feature_contracted); `mu` is the contracted mean."""
+    frustum mean goes through the Mip-NeRF 360 contraction before the lift (nerf_amd_ipe_feature_contracted); `mu` is the contracted mean.
+    `contract=CONTRACT_GAUSSIAN`: the covariance is contracted too, Sigma' = J Sigma J^T (nerf_amd_ipe_feature_gaussian)."""
     z, rays = _dev(z, "zvals"), _dev(rays, "cam_rays")
     N, S = z.shape[0], z.shape[1] - 1
     if dir_norm is None:
@@ -357,7 +384,9 @@ def ipe_feature(z: torch.Tensor, rays: torch.Tensor, L: int, r: float, dir_norm:
     feat = torch.empty((N, S, 6 * L), dtype=torch.float32, device=z.device)
     mu = torch.empty((N, S, 3), dtype=torch.float32, device=z.device)
     mu_t = torch.empty((N, S), dtype=torch.float32, device=z.device)
-    fn, name = (lib.nerf_amd_ipe_feature_contracted, "nerf_amd_ipe_feature_contracted") if contract else (lib.nerf_amd_ipe_feature, "nerf_amd_ipe_feature")
+    mode = _contract_mode(contract)
+    fn, name = ((lib.nerf_amd_ipe_feature, "nerf_amd_ipe_feature"), (lib.nerf_amd_ipe_feature_contracted, "nerf_amd_ipe_feature_contracted"),
+                (lib.nerf_amd_ipe_feature_gaussian, "nerf_amd_ipe_feature_gaussian"))[mode]
     check(fn(_ptr(z), _ptr(rays), N, S, L, float(r), _ptr(dir_norm), _ptr(feat), _ptr(mu), _ptr(mu_t), _stream()), name)
     return feat, mu, mu_t
 
@@ -782,7 +811,8 @@ def _render_batch(rays, z_base, u_strat, u_inv, seed, n_rays):
 
 def _render_descriptor(camera: Optional[Samples], contract, ipe_radius, ipe_dir_norm, seed, rng_ray_offset):
     """The descriptor of a render call: the caller's `camera`, or a new one when a flag or the Philox key needs a carrier next to explicit
-    rays (else None).  contract: True / False is written, None leaves the descriptor's flag alone; ipe_radius: the integrated PE;
+    rays (else None).  contract: True / False is written (CONTRACT_GAUSSIAN as it is: with the integrated PE the fine pass contracts the
+    frustum covariance too, the proposal passes read it as True), None leaves the descriptor's flag alone; ipe_radius: the integrated PE;
     seed: the Philox key, None with explicit uniforms.  -> (descriptor | None, keepalive): the descriptor holds only the ADDRESS of the
     direction norm -- the caller keeps `keepalive`, the converted tensor, until the call has returned."""
     if camera is None and (contract or ipe_radius is not None or seed is not None):
@@ -790,7 +820,7 @@ def _render_descriptor(camera: Optional[Samples], contract, ipe_radius, ipe_dir_
     keepalive = None
     if camera is not None:
         if contract is not None:
-            camera.contract = int(bool(contract))
+            camera.contract = _contract_mode(contract)
         if ipe_radius is not None:
             # the direction norm of mip_methods.py:31 is over ALL rays of the reference's call: a caller holding only a shard of them
             # passes the whole list's norm (ops.dirs_norm of it); default = the norm of the call's rays, computed by the entry point

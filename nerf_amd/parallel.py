@@ -236,7 +236,7 @@ def broadcast_parameters(modules: Sequence[torch.nn.Module], src: int = 0, group
 
 def render_image_sharded(network, prop_net, render_pose, image_size, focal, near, far, sample_num=128, white_bkg=False,
                          render_depth=False, gather: bool = True, seed: int = 0, group=None, render_normal=False, contract: bool = False,
-                         ipe=False, *, spacing: str = "linear", prop_rounds: int = 1, prop_pnum: Optional[int] = None) -> dict:
+                         ipe=False, *, spacing: str = "linear", prop_rounds: int = 1, prop_pnum: Optional[int] = None, ipe_cov: str = "metric") -> dict:
     """Ray-sharded whole-image render: rank r renders a contiguous 256-aligned slice of the image's (tile-ordered) ray list through
     ``procedures.render_image``'s own body -- MipNeRF, Ref-NeRF and layer-by-layer networks alike.  Every uniform is drawn in the kernels
     with Philox keyed by (``seed``, GLOBAL ray index), so the gathered image does not depend on the world size: it is bit-identical to
@@ -244,8 +244,11 @@ def render_image_sharded(network, prop_net, render_pose, image_size, focal, near
     that changed with N).  No collective on the data path; one all_gather of rgb (+ depth, + normal) at the end, or none (gather=False:
     ``{"rgb_rays", "depth_rays", "normal_rays", "range"}`` of this rank's slice).  ``spacing`` is render_image's: under "disparity" too every
     uniform is a function of the global ray index, so the shards reproduce the whole image.  ``prop_rounds`` / ``prop_pnum`` likewise (the
-    second proposal round draws further columns of the same per-ray stream)."""
+    second proposal round draws further columns of the same per-ray stream), and ``ipe_cov`` (the contracted frustum covariance is a function
+    of the ray, its depths and the whole image's direction norm)."""
+    from . import ops
     from .procedures import get_patch_size, render_image
+    ops.ipe_contract(contract, ipe, ipe_cov, "nerf_amd.parallel.render_image_sharded")
     rank, world = dist.get_rank(group), dist.get_world_size(group)
     H, W = (image_size, image_size) if not isinstance(image_size, (tuple, list)) else image_size
     sz, patch_num = get_patch_size((H, W))
@@ -253,7 +256,7 @@ def render_image_sharded(network, prop_net, render_pose, image_size, focal, near
     start, end = shard_range(n, rank, world, align=256)
     part = render_image(network, prop_net, render_pose, image_size, focal, near, far, sample_num, white_bkg, render_depth, render_normal,
                         rng="philox", contract=contract, ipe=ipe, seed=int(seed), _shard=(start, end), spacing=spacing,
-                        prop_rounds=prop_rounds, prop_pnum=prop_pnum)
+                        prop_rounds=prop_rounds, prop_pnum=prop_pnum, ipe_cov=ipe_cov)
     if not gather:
         part.pop("to_image")
         return part

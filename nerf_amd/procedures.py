@@ -50,7 +50,7 @@ GENERIC_CHUNK_RAYS = 4096
 def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, render_depth, chunk: Optional[int] = None,
                           is_ref_model: bool = False, cam_dir=None, seed: Optional[int] = None, ray_offset: int = 0, contract: bool = False,
                           ipe_radius: Optional[float] = None, ipe_dir_norm=None, *, spacing: str = "linear", prop_rounds: int = 1,
-                          prop_pnum: Optional[int] = None):
+                          prop_pnum: Optional[int] = None, ipe_cov: str = "metric"):
     """The tile body of procedures.py:62-85 as the reference writes it -- stratified depths, ProposalNetwork.forward, get_weights,
     maxBlurFilter, inverseSample, NeRF.length2pts, network.forward, NeRF.render -- on chunks of rays: the route of networks the fused
     render entry (nerf_amd_render_rays) has no packed layout for.  Every call is a HIP kernel of this package; uniforms that were not
@@ -62,8 +62,11 @@ def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sampl
     ``prop_rounds=2`` (Mip-NeRF 360's two proposal rounds; Philox uniforms only): between the proposal pass and the fine resampling,
     ``prop_pnum`` sorted depths are resampled from the first histogram, the proposal network is evaluated there and the fine depths are
     drawn from that second histogram.  The ray's inverse-CDF stream then has prop_pnum + sample_num + 1 columns: the first prop_pnum feed
-    the second round, the rest the fine resampling."""
+    the second round, the rest the fine resampling.
+    ``ipe_cov`` (with ``ipe_radius`` and ``contract``): "contracted" = the frustum covariance goes through the contraction with its mean
+    (MipNeRF.forward_rays); the proposal passes contract positions as before."""
     from .mip_methods import maxBlurFilter
+    ops.ipe_contract(contract, ipe_radius, ipe_cov, "nerf_amd.render_image")
     from .utils import inverseSample
     N = rays.shape[0]
     chunk = GENERIC_CHUNK_RAYS if chunk is None else chunk
@@ -107,7 +110,7 @@ def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sampl
             rgbo, normal = network.forward(samples, contract=True) if contract else network.forward(samples)
             rgbo[..., -1] = torch.nn.functional.softplus(rgbo[..., -1] + 0.5)
         elif ipe_radius is not None:                                                  # frusta between the sample_num + 1 sorted depths
-            rgbo = network.forward_rays(r, fine.contiguous(), sample_num, ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, contract=contract)
+            rgbo = network.forward_rays(r, fine.contiguous(), sample_num, ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, contract=contract, ipe_cov=ipe_cov)
             fine = fine[..., :-1].contiguous()
         else:
             fine = fine[..., :-1].contiguous()
@@ -162,7 +165,7 @@ def _check_spacing(spacing, near, far) -> bool:
 def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Tensor, image_size, focal,
                  near: float, far: float, sample_num: int = 128, white_bkg: bool = False, render_depth=False,
                  render_normal=False, rng: str = "philox", contract: bool = False, ipe=False, seed: Optional[int] = None,
-                 _shard=None, *, spacing: str = "linear", prop_rounds: int = 1, prop_pnum: Optional[int] = None) -> dict:
+                 _shard=None, *, spacing: str = "linear", prop_rounds: int = 1, prop_pnum: Optional[int] = None, ipe_cov: str = "metric") -> dict:
     """Whole-image inference (procedures.py:34-97) -> {"rgb" (3,H,W) [, "depth_img" (3,H,W)]} on
     ``render_pose.device``.  The caller provides ``no_grad``/``eval()`` like for the reference.
     ``rng``, ``contract`` and ``ipe`` are additions.  ``rng``: where the stratified / inverse-CDF uniforms come from --
@@ -195,7 +198,13 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
     networks with 3 <= prop_pnum <= 256 go through nerf_amd_render_rays_rounds under both spacings (profiles/two_round_render_summary.md);
     layer-by-layer networks and other histogram sizes take the call-by-call route, which computes the same image on the same streams;
     ``rng="philox"`` only -- each ray's inverse-CDF stream simply has prop_pnum more columns, still a pure function of (seed, global ray
-    index), so shards reproduce the whole image bit for bit; not available for Ref-NeRF."""
+    index), so shards reproduce the whole image bit for bit; not available for Ref-NeRF.
+    ``ipe_cov`` (keyword-only; an addition, with ``ipe`` and ``contract=True`` only): "metric" (default) contracts the frustum MEAN and
+    leaves the covariance in metric space; "contracted" pushes the whole Gaussian through the linearised contraction like Mip-NeRF 360
+    (eq. 11-14: mu' = f(mu), Sigma' = J Sigma J^T), so that the attenuation exp(-0.5 4^l var) is measured in the coordinates the mean
+    lives in and the far background keeps its low frequencies.  Every route -- fused, two rounds, disparity,
+    layer by layer, sharded -- computes the same function; frusta inside the unit ball are the same bits under both."""
+    ops.ipe_contract(contract, ipe, ipe_cov, "nerf_amd.render_image")
     if prop_rounds not in (1, 2):
         raise ValueError("nerf_amd.render_image: prop_rounds must be 1 or 2 (got %r)" % (prop_rounds,))
     if prop_pnum is not None and int(prop_pnum) < 1:
@@ -256,7 +265,7 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
         rgb, depth, normal_px = _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, bool(render_depth),
                                                       is_ref_model=is_ref_model, cam_dir=cam_dir, seed=seed, ray_offset=off, contract=contract,
                                                       ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, spacing=spacing, prop_rounds=prop_rounds,
-                                                      prop_pnum=prop_pnum)
+                                                      prop_pnum=prop_pnum, ipe_cov=ipe_cov)
     elif route == "ref":
         # procedures.py:71-74: coarse and fine depths are merged and sorted (a merge of two ascending sets), the last one dropped,
         # sigma -> softplus(sigma + 0.5) before compositing (nerf_amd_render_rays_ref: six launches)
@@ -266,7 +275,7 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
     else:
         # (a narrow fine network has no integrated-PE kernel: with ipe its 256-wide -- zero-padded -- blob is used)
         packed = (prop_net.packed(prec), network.packed(prec, wide=bool(ipe)), prec, rays)
-        common = dict(want_depth=bool(render_depth), contract=contract, ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, seed=seed, rng_ray_offset=off)
+        common = dict(want_depth=bool(render_depth), contract=ops.ipe_contract(contract, ipe, ipe_cov), ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, seed=seed, rng_ray_offset=off)
         if route == "rounds":
             rgb, depth, _, _ = ops.render_rays_rounds(*packed, z_base, sample_num, near, far, white_bkg, prop_pnum=prop_pnum, spacing=spacing, **common)
         elif route == "warped":

@@ -67,7 +67,7 @@ class TrainStep:
                  coarse_pnum: int = 64, fine_pnum: int = 128, crop_xy=(1.0, 1.0), seed: Optional[int] = None, white_bkg: bool = False,
                  prop_normal: bool = False, grad_hook=None, ipe_radius: Optional[float] = None, contract: bool = False, flat_grads=None,
                  *, scene=None, view_ids=None, spacing: str = "linear", prop_loss: str = "reference", prop_rounds: int = 1,
-                 prop_pnum: Optional[int] = None, grad_clip: float = -0.01, distortion: float = 0.0):
+                 prop_pnum: Optional[int] = None, ipe_cov: str = "metric", grad_clip: float = -0.01, distortion: float = 0.0):
         """``grad_hook``: called between ``loss.backward()`` and ``optimizer.step()`` -- the place of ddp_train.py's gradient all-reduce
         (``lambda: parallel.allreduce_gradients([mip_net, prop_net])``).  An iteration with a hook runs eagerly (``capture`` refuses).
         ``ipe_radius`` (BASELINE configs[2]): the fine network encodes the conical frusta between consecutive fine depths with the
@@ -107,8 +107,13 @@ class TrainStep:
         gives w1 over z_c; ``prop_pnum`` (default ``coarse_pnum``) depths z_2 are resampled from it (sorted; in s under "disparity"), the
         same network is evaluated there and gives w2 over z_2, the fine depths are drawn from (w2, z_2); the loss term is
         L(w_fine, z_f; w1, z_c) + L(w_fine, z_f; w2, z_2).  The two resamplings use disjoint columns of one Philox draw for the step's seed.
-        ``scene``, ``view_ids``, ``spacing``, ``grad_clip``, ``distortion``, ``prop_loss``, ``prop_rounds`` and ``prop_pnum`` are
-        keyword-only (their order carries no meaning)."""
+        ``ipe_cov`` (BASELINE configs[4]; with ``ipe_radius`` and ``contract`` only): "metric" (default) leaves the iteration as it is --
+        the frustum mean is contracted, its covariance stays metric; "contracted" = Mip-NeRF 360's Sigma' = J Sigma J^T (eq. 11-14) in
+        the fine network's sample fetch.  The backward is unchanged: the parameters' gradients read the dumped encoding.
+        ``scene``, ``view_ids``, ``spacing``, ``grad_clip``, ``distortion``, ``prop_loss``, ``prop_rounds``, ``prop_pnum`` and ``ipe_cov``
+        are keyword-only (their order carries no meaning)."""
+        ops.ipe_contract(contract, ipe_radius, ipe_cov, "nerf_amd.training.TrainStep")
+        self.ipe_cov = ipe_cov
         if not isinstance(optimizer, Adam) or not optimizer.lr_on_device:
             raise ValueError("nerf_amd.training.TrainStep needs nerf_amd.optim.Adam(..., lr_on_device=True): the step must not read host state")
         self.prop_net, self.mip_net, self.opt = prop_net, mip_net, optimizer
@@ -277,7 +282,7 @@ class TrainStep:
         else:
             edges = s_f if self.warped else z_f                  # the fine_pnum + 1 sorted fine depths: the intervals of L_dist
             if self.ipe_radius is not None:                      # the fine_pnum frusta between the fine_pnum + 1 sorted depths
-                rgbo = self.mip_net.forward_rays(rays, z_f, self.fine_pnum, ipe_radius=self.ipe_radius, contract=self.contract)
+                rgbo = self.mip_net.forward_rays(rays, z_f, self.fine_pnum, ipe_radius=self.ipe_radius, contract=self.contract, ipe_cov=self.ipe_cov)
                 z_f = z_f[..., :-1].contiguous()
             else:
                 z_f = z_f[..., :-1].contiguous()                                                        # :188
