@@ -604,6 +604,80 @@ int    nerf_amd_render_rays_ref(const void* packed_prop, const void* packed_ref,
                                 float* rgb, float* depth, float* normal_img, void* workspace, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * (added after ABI 125; additive) Quantile (median) ray-termination depth and accumulated opacity of composited rays: what Mip-NeRF 360
+ * and the viewers built on it show instead of the expected depth sum w t, which a little weight far out drags through empty space.  Not
+ * in the reference; the build's own definition, restated in fp64 by tests/depth_stats_ref.py.  Per ray:
+ *   weights w_0 .. w_{S-1} (fp32, >= 0); depths z_0 .. z_{E-1}, E = S + 1 (`closed` != 0: the row also holds the edge that closes the last
+ *   interval) or E = S (open); direction d.  t_s = z_s |d| with mul_norm (one fp32 product, |d| as in nerf_amd_composite), else t_s = z_s.
+ *   cumulative mass in fp64: C_0 = 0, C_{s+1} = C_s + (double)w_s;   opacity = (float)C_S
+ *   for each quantile q (fp32, 0 < q < 1, at most NERF_AMD_DEPTH_QUANTILES_MAX per call) -- the mass is ABSOLUTE, not renormalised
+ *   (multinerf's weighted_percentile): k = the smallest s with C_{s+1} >= q;
+ *       no such s (the ray never accumulates q):  D_q = t_{E-1}      (the far edge)
+ *       k = S - 1 of an open row:                 D_q = t_{S-1}
+ *       otherwise                                 D_q = t_k + ((q - C_k) / w_k) (t_{k+1} - t_k)    in fp64, rounded once to fp32
+ *   depth_q = (D_q - near) / (far - near) in fp32, as nerf_amd_composite normalises its depth.
+ * D_q is continuous in the weights except where the crossing sits exactly on an edge next to a zero-weight interval.
+ * weights (N,S); z rows of z_stride >= E floats; dirs rows of dirs_stride floats (read with mul_norm only); quantiles: HOST array;
+ * opacity (N) or NULL; depth_q (N, n_quantiles) or NULL.  Refused before the launch: NULL inputs, N < 0, S < 1, n_quantiles outside
+ * 0..NERF_AMD_DEPTH_QUANTILES_MAX, a q outside (0, 1) or NaN, z_stride < E.  N == 0 is fine.  One launch, one wavefront per ray, any S;
+ * no workspace, no atomics, no host state: deterministic and capturable.
+ * ------------------------------------------------------------------------------------------------ */
+#define NERF_AMD_DEPTH_QUANTILES_MAX 4
+int nerf_amd_ray_depth_stats(const float* weights, const float* z, int z_stride, int closed, const float* dirs, int dirs_stride, int64_t N,
+                             int S, int mul_norm, const float* quantiles, int n_quantiles, float near, float far, float* opacity,
+                             float* depth_q, void* stream);
+
+/* (added after ABI 125; additive) The four render entry points above behind ONE request: the same pipeline, the same launches, plus
+ * optional outputs they have no argument for.  `size` = sizeof(nerf_amd_render_request) of the caller's header (a smaller one is refused:
+ * this is the first layout); zero-fill the struct, then set what the call uses.
+ *   which entry point:  ref != 0 -> nerf_amd_render_rays_ref;  else prop_pnum != 0 -> nerf_amd_render_rays_rounds (in-kernel uniforms only);
+ *                       else spacing == NERF_AMD_SPACING_DISPARITY -> nerf_amd_render_rays_warped;  else nerf_amd_render_rays.
+ *   Every field means what the argument of that name means there (`normal_img` / `cam_dir` / `ref_flags` are read for Ref-NeRF only;
+ *   `weights` is (N, n_fine) for MipNeRF and -- through this entry point alone -- (N, n_fine + 64) for Ref-NeRF; with two rounds u_strat and
+ *   u_inv must be NULL).  With opacity, depth_q and fine_depths NULL the call IS that entry point: same checks, same launches, same bits,
+ *   and nerf_amd_render_request_workspace_bytes equals its workspace query.
+ *   opacity (N), depth_q (N, n_quantiles) with quantiles[0 .. n_quantiles): nerf_amd_ray_depth_stats of the weights and depth row the fine
+ *   pass composited (mul_norm; closed rows of n_fine + 1 depths on the MipNeRF routes, open rows of n_fine + 64 for Ref-NeRF; near, far of
+ *   the request -- under disparity spacing near = 0, far = 1 followed by W^-1 like `depth`, so depth_q lives in the same [0, 1] s-scale).
+ *   fine_depths (N, E): a copy of that depth row, E = n_fine + 1 (MipNeRF) or n_fine + 64 (Ref-NeRF).
+ *   They append to the entry point's launches: the stats launch [-> the un-warp] [-> one device-to-device copy].  The kernel reads the
+ *   weights the compositing kernel wrote: `weights` when given, else a part appended BEHIND the entry point's workspace (as is the raw
+ *   depth_q under disparity spacing) -- nerf_amd_render_request_workspace_bytes grows by those parts, the existing layout does not move.
+ * ------------------------------------------------------------------------------------------------ */
+typedef struct nerf_amd_render_request {
+    size_t size;                       /* sizeof(nerf_amd_render_request) */
+    const void* packed_prop;
+    const void* packed_fine;           /* MipNeRF blob, or the Ref-NeRF blob with ref != 0 */
+    int32_t precision;                 /* NERF_AMD_F32 / NERF_AMD_BF16, layout flags OR-ed in */
+    int32_t ref;                       /* != 0: Ref-NeRF fine network */
+    int32_t ref_flags;                 /* NERF_AMD_REF_SRGB */
+    int32_t white_bkg;
+    const float* rays;                 /* (N,6), or NULL with `camera` */
+    const nerf_amd_samples* camera;
+    int64_t ray_offset;
+    const float* z_base;               /* (64), linear spacing */
+    const float* u_strat;              /* (N,64) and (N, n_fine+1), or both NULL: in-kernel uniforms */
+    const float* u_inv;
+    int64_t N;
+    int32_t n_fine;
+    int32_t prop_pnum;                 /* 0: one proposal round */
+    int32_t spacing;                   /* NERF_AMD_SPACING_LINEAR / NERF_AMD_SPACING_DISPARITY */
+    float near, far;
+    int32_t n_quantiles;               /* 0 .. NERF_AMD_DEPTH_QUANTILES_MAX */
+    float quantiles[NERF_AMD_DEPTH_QUANTILES_MAX];
+    const float* cam_dir;              /* (3) device, with normal_img */
+    float* rgb;                        /* (N,3) */
+    float* depth;                      /* (N) or NULL */
+    float* weights;                    /* (N, n_fine), Ref-NeRF (N, n_fine + 64), or NULL */
+    float* normal_img;                 /* (N) or NULL (Ref-NeRF) */
+    float* opacity;                    /* (N) or NULL */
+    float* depth_q;                    /* (N, n_quantiles) or NULL */
+    float* fine_depths;                /* (N, E) or NULL */
+} nerf_amd_render_request;
+size_t nerf_amd_render_request_workspace_bytes(const nerf_amd_render_request* request);
+int    nerf_amd_render(const nerf_amd_render_request* request, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Generic-shape layer product (ABI 119): the path of networks LARGER than the shapes the fused MLP kernels are compiled for -- hidden
  * widths above 256 (`--nerf_net_width` / `--prop_net_width`, procedures.py:176-177), more than 10 encoding octaves (mip_model.py:15-18,
  * addtional.py:61).  Such a network is evaluated layer by layer (nerf_helper.py:28-36 makeMLP = nn.Linear + activation) with fp32

@@ -35,6 +35,23 @@ class Samples(C.Structure):
                 ("ipe_dir_norm", c_void), ("rng_seed", C.c_uint64), ("rng_ray_offset", C.c_int64)]
 
 
+DEPTH_QUANTILES_MAX = 4   # NERF_AMD_DEPTH_QUANTILES_MAX: quantiles per nerf_amd_ray_depth_stats / nerf_amd_render call
+
+
+class RenderRequest(C.Structure):
+    """struct nerf_amd_render_request (a zero-filled instance has every optional field off; ``size`` is set on construction)"""
+    _fields_ = [("size", C.c_size_t), ("packed_prop", c_void), ("packed_fine", c_void), ("precision", C.c_int32), ("ref", C.c_int32),
+                ("ref_flags", C.c_int32), ("white_bkg", C.c_int32), ("rays", c_void), ("camera", C.POINTER(Samples)), ("ray_offset", C.c_int64),
+                ("z_base", c_void), ("u_strat", c_void), ("u_inv", c_void), ("N", C.c_int64), ("n_fine", C.c_int32), ("prop_pnum", C.c_int32),
+                ("spacing", C.c_int32), ("near", C.c_float), ("far", C.c_float), ("n_quantiles", C.c_int32),
+                ("quantiles", C.c_float * DEPTH_QUANTILES_MAX), ("cam_dir", c_void), ("rgb", c_void), ("depth", c_void), ("weights", c_void),
+                ("normal_img", c_void), ("opacity", c_void), ("depth_q", c_void), ("fine_depths", c_void)]
+
+    def __init__(self, **fields):
+        super().__init__(**fields)
+        self.size = C.sizeof(RenderRequest)
+
+
 # name -> (restype, argtypes); mirrors include/nerf_amd.h one to one (tests check the two agree)
 SIGNATURES = {
     "nerf_amd_last_error": (C.c_char_p, []),
@@ -137,6 +154,10 @@ SIGNATURES = {
     "nerf_amd_render_rounds_workspace_bytes": (C.c_size_t, [i64, C.c_int, C.c_int, C.c_int]),
     "nerf_amd_render_rays_rounds": (C.c_int, [c_void, c_void, C.c_int, c_void, C.POINTER(Samples), i64, c_void, i64, C.c_int, C.c_int, C.c_int,
                                               C.c_float, C.c_float, C.c_int, c_void, c_void, c_void, c_void, c_void]),
+    "nerf_amd_ray_depth_stats": (C.c_int, [c_void, c_void, C.c_int, C.c_int, c_void, C.c_int, i64, C.c_int, C.c_int, c_float_p, C.c_int, C.c_float, C.c_float,
+                                          c_void, c_void, c_void]),
+    "nerf_amd_render_request_workspace_bytes": (C.c_size_t, [C.POINTER(RenderRequest)]),
+    "nerf_amd_render": (C.c_int, [C.POINTER(RenderRequest), c_void, c_void]),
     "nerf_amd_gemm_workspace_bytes": (C.c_size_t, [i64, i64, i64]),
     "nerf_amd_gemm": (C.c_int, [C.c_int, i64, i64, i64, c_void, i64, i64, c_void, i64, i64, c_void, i64, c_void, C.c_int, c_void, i64, c_void, c_void]),
     "nerf_amd_sigmoid_backward": (C.c_int, [c_void, i64, c_void, i64, i64, C.c_int, c_void, i64, c_void]),
@@ -154,7 +175,7 @@ SIGNATURES = {
 
 # additive entry points that a library named by NERF_AMD_LIB may predate
 ADDED_AFTER_125 = ("nerf_amd_direction_table", "nerf_amd_render_rounds_workspace_bytes", "nerf_amd_render_rays_rounds",
-                   "nerf_amd_ipe_feature_gaussian")
+                   "nerf_amd_ipe_feature_gaussian", "nerf_amd_ray_depth_stats", "nerf_amd_render_request_workspace_bytes", "nerf_amd_render")
 
 
 def _load():

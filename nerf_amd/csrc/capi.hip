@@ -727,11 +727,47 @@ struct RenderPlan {
     float near, far, gn, gf;                                // gn, gf: check_spacing (warped)
     int white_bkg;
     float *rgb, *depth, *weights;
+    // Ref-NeRF only (weights: (N, n_fine + 64) there, reachable through nerf_amd_render alone)
+    int ref_flags = 0;
+    const float* cam_dir = nullptr;
+    float* normal_img = nullptr;
+    // nerf_amd_render only: depth quantiles, opacity and the fine depth row (all NULL / 0: the call is the plain entry point)
+    float *opacity = nullptr, *depth_q = nullptr, *fine_depths = nullptr;
+    float quantiles[NERF_AMD_DEPTH_QUANTILES_MAX] = {0.0f, 0.0f, 0.0f, 0.0f};
+    int n_quantiles = 0;
+    bool want_stats() const { return opacity || (depth_q && n_quantiles); }
+    int fine_samples() const { return n_fine + (ref ? RENDER_C : 0); }      // samples per ray of the fine pass
     bool ipe() const { return !ref && camera && camera->ipe; }
     uint64_t seed() const { return camera ? camera->rng_seed : 0; }     // (read only when a uniform tensor is NULL)
     int64_t ray0() const { return camera ? camera->rng_ray_offset : 0; }
     RenderWs ws(void* base) const { return RenderWs(warped, prop_pnum, ref, base, N, n_fine); }
 };
+// What nerf_amd_render appends BEHIND the entry point's workspace (whose layout and size query stay): the weights the stats kernel reads
+// when the caller takes none, and the raw quantile depths that the un-warp reads under disparity spacing; each rounded up to 256 bytes.
+struct RenderExtrasWs {
+    float *weights = nullptr, *depth_q_raw = nullptr;
+    size_t bytes;                                           // of the whole workspace, the entry point's part included
+    RenderExtrasWs(const RenderPlan& p, void* base) {
+        const RenderWs ws = p.ws(base);
+        const size_t n = (size_t)p.N;
+        const size_t w_part = (p.want_stats() && !p.weights) ? ((n * p.fine_samples() * 4 + 255) & ~(size_t)255) : 0;
+        const size_t q_part = (p.warped && p.depth_q && p.n_quantiles) ? ((n * p.n_quantiles * 4 + 255) & ~(size_t)255) : 0;
+        bytes = ws.bytes;
+        if (!(w_part + q_part)) return;
+        const size_t own = (ws.bytes + 255) & ~(size_t)255;    // ws.bytes counts from the caller's pointer, the parts from the aligned start: past its end
+        char* at = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255) + own;
+        if (w_part) { weights = reinterpret_cast<float*>(at); at += w_part; }
+        if (q_part) depth_q_raw = reinterpret_cast<float*>(at);
+        bytes = own + w_part + q_part + 256;
+    }
+};
+int check_quantiles(const float* q, int nq) {
+    if (nq < 0 || nq > NERF_AMD_DEPTH_QUANTILES_MAX) return fail(NERF_AMD_EINVAL, "n_quantiles must be 0..NERF_AMD_DEPTH_QUANTILES_MAX (4)");
+    if (nq && !q) return fail(NERF_AMD_EINVAL, "NULL argument: quantiles");
+    for (int j = 0; j < nq; ++j)
+        if (!(q[j] > 0.0f && q[j] < 1.0f)) return fail(NERF_AMD_EINVAL, "a quantile must lie in (0, 1)");
+    return NERF_AMD_OK;
+}
 
 // ---- the checks: everything is refused here, before the first launch ----
 // what must hold even for N == 0: precision and layout bits, sizes, and that every resampling launch fits the LDS
@@ -829,6 +865,20 @@ int composite_pass(const RenderPlan& p, const float* rays, const RenderWs& ws, h
                              p.warped ? 1.0f : p.far, nullptr, nullptr, p.rgb, p.weights, unwarp ? ws.depth_raw : p.depth, nullptr, st)) return hip_status(e, "composite");
     return unwarp ? hip_status(sk_warp_depths(ws.depth_raw, nullptr, p.N, 1, 1, p.near, p.far, p.gn, p.gf, p.depth, nullptr, st), "depth un-warp") : NERF_AMD_OK;
 }
+// nerf_amd_render's optional outputs, appended to the entry point's launches (nothing is launched when none is asked for): the stats
+// kernel on the weights and the depth row (stride = row length) the fine pass composited [-> un-warp] [-> a copy of the depth row]
+int extras_pass(const RenderPlan& p, const float* rays, const float* z_row, bool closed, const RenderExtrasWs& x, hipStream_t st) {
+    const int S = p.fine_samples(), E = S + (closed ? 1 : 0);
+    if (p.want_stats()) {
+        float* dq = p.depth_q && p.n_quantiles ? (p.warped ? x.depth_q_raw : p.depth_q) : nullptr;
+        if (int e = sk_ray_depth_stats(p.weights, z_row, E, closed, rays + 3, 6, p.N, S, 1, p.quantiles, p.n_quantiles, p.warped ? 0.0f : p.near,
+                                       p.warped ? 1.0f : p.far, p.opacity, dq, st)) return hip_status(e, "depth quantiles and opacity");
+        if (dq && p.warped)
+            if (int e = sk_warp_depths(dq, nullptr, p.N, p.n_quantiles, 1, p.near, p.far, p.gn, p.gf, p.depth_q, nullptr, st)) return hip_status(e, "quantile un-warp");
+    }
+    if (p.fine_depths) return hip_status((int)hipMemcpyAsync(p.fine_depths, z_row, (size_t)p.N * E * 4, hipMemcpyDeviceToDevice, st), "fine depth copy");
+    return NERF_AMD_OK;
+}
 // the three MipNeRF entry points behind their own checks: shape, N == 0, inputs, then the launches in pipeline order
 int render_mip(RenderPlan& p, void* workspace, hipStream_t st) {
     if (int e = check_plan_shape(p, NERF_AMD_PROP_W128 | NERF_AMD_FINE_W128, "unknown precision")) return e;
@@ -843,7 +893,35 @@ int render_mip(RenderPlan& p, void* workspace, hipStream_t st) {
     if (P)
         if (int e = second_round(p, rays, ws, st)) return e;
     if (int e = fine_pass(p, rays, dir_norm, ws, st)) return e;
-    return composite_pass(p, rays, ws, st);
+    const RenderExtrasWs x(p, workspace);
+    if (x.weights) p.weights = x.weights;                   // (nerf_amd_render with stats and no weights output: composited into the appended part)
+    if (int e = composite_pass(p, rays, ws, st)) return e;
+    return extras_pass(p, rays, ws.z_fine, true, x, st);
+}
+// the Ref-NeRF entry point, likewise: the checks, then the launches in pipeline order
+int render_ref(RenderPlan& p, void* workspace, hipStream_t st) {
+    if (bad_ref_flags(p.ref_flags)) return fail(NERF_AMD_EINVAL, "unknown precision or ref_flags");
+    if (int e = check_plan_shape(p, NERF_AMD_PROP_W128, "unknown precision or ref_flags")) return e;
+    if (p.N == 0) return NERF_AMD_OK;
+    if (int e = check_plan_inputs(p, workspace)) return e;
+    if ((p.normal_img != nullptr) != (p.cam_dir != nullptr)) return fail(NERF_AMD_EINVAL, "normal_img and cam_dir go together");
+    constexpr int C = RENDER_C;
+    const int S_all = p.fine_samples();                     // (n_fine + 1) fine + 64 coarse depths, the last one dropped
+    const RenderWs ws = p.ws(workspace);
+    const float* rays;
+    if (int e = provide_rays(p, ws, st, &rays)) return e;
+    if (int e = coarse_pass(p, rays, p.n_fine + 1, ws.z_fine, nullptr, ws, st)) return e;
+    // row 8, Ref-NeRF branch (procedures.py:71-74): fine and coarse depths merged, the last one dropped
+    if (int e = sk_merge_sorted(ws.z_fine, ws.z_coarse, p.N, p.n_fine + 1, C, ws.z_all, st)) return hip_status(e, "depth merge");
+    const nerf_amd_samples sf = ray_samples(p, rays, S_all, ws.z_all, S_all);   // row 13
+    float* normals = p.normal_img ? ws.normals : nullptr;
+    if (int e = mlp_launch_ref(p.packed_fine, p.precision, sf, ws.rgbo, normals, nullptr, p.ref_flags, st)) return hip_status(e, "Ref-NeRF MLP");
+    const RenderExtrasWs x(p, workspace);
+    if (x.weights) p.weights = x.weights;
+    const int flags = 1 | (p.white_bkg ? 2 : 0);            // row 10 with sigma -> softplus(sigma + 0.5) (procedures.py:73)
+    if (int e = sk_composite(ws.rgbo, ws.z_all, S_all, rays + 3, 6, p.N, S_all, flags, NERF_AMD_ACT_SOFTPLUS, 0.5f, p.near, p.far, normals, p.cam_dir, p.rgb, p.weights,
+                             p.depth, p.normal_img, st)) return hip_status(e, "composite");
+    return extras_pass(p, rays, ws.z_all, false, x, st);
 }
 // the sizes nerf_amd_render_rays_rounds takes, for the entry point and its workspace query alike: NULL, or what is wrong
 const char* rounds_shape_error(int64_t N, int n_fine, int prop_pnum, int spacing) {
@@ -929,25 +1007,57 @@ int nerf_amd_render_rays_ref(const void* packed_prop, const void* packed_ref, in
                              int white_bkg, const float* cam_dir, float* rgb, float* depth, float* normal_img, void* workspace, void* stream) {
     RenderPlan p{packed_prop, packed_ref, precision, 0, rays, camera, ray_offset, z_base, u_strat, u_inv, N, n_fine, 0, false, true, near, far, 0.0f, 0.0f,
                  white_bkg, rgb, depth, nullptr};
-    if (bad_ref_flags(ref_flags)) return fail(NERF_AMD_EINVAL, "unknown precision or ref_flags");
-    if (int e = check_plan_shape(p, NERF_AMD_PROP_W128, "unknown precision or ref_flags")) return e;
-    if (N == 0) return NERF_AMD_OK;
-    if (int e = check_plan_inputs(p, workspace)) return e;
-    if ((normal_img != nullptr) != (cam_dir != nullptr)) return fail(NERF_AMD_EINVAL, "normal_img and cam_dir go together");
-    constexpr int C = RENDER_C;
-    const int S_all = n_fine + C;                           // (n_fine + 1) fine + 64 coarse depths, the last one dropped
-    const RenderWs ws = p.ws(workspace);
-    hipStream_t st = S(stream);
-    if (int e = provide_rays(p, ws, st, &rays)) return e;
-    if (int e = coarse_pass(p, rays, n_fine + 1, ws.z_fine, nullptr, ws, st)) return e;
-    // row 8, Ref-NeRF branch (procedures.py:71-74): fine and coarse depths merged, the last one dropped
-    if (int e = sk_merge_sorted(ws.z_fine, ws.z_coarse, N, n_fine + 1, C, ws.z_all, st)) return hip_status(e, "depth merge");
-    const nerf_amd_samples sf = ray_samples(p, rays, S_all, ws.z_all, S_all);   // row 13
-    float* normals = normal_img ? ws.normals : nullptr;
-    if (int e = mlp_launch_ref(packed_ref, p.precision, sf, ws.rgbo, normals, nullptr, ref_flags, st)) return hip_status(e, "Ref-NeRF MLP");
-    const int flags = 1 | (white_bkg ? 2 : 0);              // row 10 with sigma -> softplus(sigma + 0.5) (procedures.py:73)
-    return hip_status(sk_composite(ws.rgbo, ws.z_all, S_all, rays + 3, 6, N, S_all, flags, NERF_AMD_ACT_SOFTPLUS, 0.5f, near, far, normals, cam_dir, rgb, nullptr, depth,
-                                   normal_img, st), "composite");
+    p.ref_flags = ref_flags; p.cam_dir = cam_dir; p.normal_img = normal_img;
+    return render_ref(p, workspace, S(stream));
+}
+
+// ------------------------------------------------------------------------------------------------ one request for all four, with the optional outputs
+namespace {
+// request -> plan; what the four entry points refuse before they fill their plan is refused here in the same order
+int plan_from_request(const nerf_amd_render_request* r, RenderPlan& p, bool sizing) {     // sizing: the workspace query, which needs no descriptor
+    if (!r) return fail(NERF_AMD_EINVAL, "NULL argument: request");
+    if (r->size < sizeof(nerf_amd_render_request)) return fail(NERF_AMD_EINVAL, "request->size is smaller than nerf_amd_render_request");
+    if (r->spacing != NERF_AMD_SPACING_LINEAR && r->spacing != NERF_AMD_SPACING_DISPARITY)
+        return fail(NERF_AMD_EINVAL, "unknown spacing (NERF_AMD_SPACING_LINEAR or NERF_AMD_SPACING_DISPARITY)");
+    const bool warped = r->spacing == NERF_AMD_SPACING_DISPARITY, rounds = !r->ref && r->prop_pnum != 0;
+    if (r->ref && (warped || r->prop_pnum)) return fail(NERF_AMD_EUNSUPPORTED, "the Ref-NeRF pipeline has neither disparity spacing nor a second proposal round");
+    if (rounds) {
+        if (const char* bad_shape = rounds_shape_error(r->N, r->n_fine, r->prop_pnum, r->spacing)) return fail(NERF_AMD_EINVAL, bad_shape);
+        if (r->u_strat || r->u_inv) return fail(NERF_AMD_EINVAL, "two proposal rounds draw their uniforms in the kernels: u_strat and u_inv must be NULL");
+    }
+    p = RenderPlan{r->packed_prop, r->packed_fine, r->precision, 0, r->rays, r->camera, r->ray_offset, warped ? nullptr : r->z_base, r->u_strat, r->u_inv, r->N, r->n_fine,
+                   rounds ? r->prop_pnum : 0, warped, r->ref != 0, r->near, r->far, 0.0f, 0.0f, r->white_bkg, r->rgb, r->depth, r->weights};
+    if (warped)
+        if (int e = check_spacing(r->spacing, r->near, r->far, &p.gn, &p.gf)) return e;
+    if (rounds && !sizing && r->N && !r->camera) return fail(NERF_AMD_EINVAL, "NULL argument: in-kernel uniforms need the descriptor (rng_seed, rng_ray_offset)");
+    if (p.ref) { p.ref_flags = r->ref_flags; p.cam_dir = r->cam_dir; p.normal_img = r->normal_img; }
+    if (int e = check_quantiles(r->quantiles, r->n_quantiles)) return e;
+    p.opacity = r->opacity; p.depth_q = r->depth_q; p.fine_depths = r->fine_depths; p.n_quantiles = r->n_quantiles;
+    for (int j = 0; j < r->n_quantiles; ++j) p.quantiles[j] = r->quantiles[j];
+    return NERF_AMD_OK;
+}
+}  // namespace
+size_t nerf_amd_render_request_workspace_bytes(const nerf_amd_render_request* request) {
+    RenderPlan p{};
+    if (plan_from_request(request, p, true) || p.N < 0 || p.n_fine < 1) return 0;
+    return RenderExtrasWs(p, nullptr).bytes;
+}
+int nerf_amd_render(const nerf_amd_render_request* request, void* workspace, void* stream) {
+    RenderPlan p{};
+    if (int e = plan_from_request(request, p, false)) return e;
+    return p.ref ? render_ref(p, workspace, S(stream)) : render_mip(p, workspace, S(stream));
+}
+
+int nerf_amd_ray_depth_stats(const float* weights, const float* z, int z_stride, int closed, const float* dirs, int dirs_stride, int64_t N, int Sn, int mul_norm,
+                             const float* quantiles, int n_quantiles, float near, float far, float* opacity, float* depth_q, void* stream) {
+    if (N < 0 || Sn < 1) return fail(NERF_AMD_EINVAL, "need N >= 0 and S >= 1");
+    if (int e = check_quantiles(quantiles, n_quantiles)) return e;
+    if (z_stride < Sn + (closed ? 1 : 0)) return fail(NERF_AMD_EINVAL, "z_stride is smaller than the depth row (S + 1 depths of a closed row, S of an open one)");
+    if (mul_norm && dirs_stride < 3) return fail(NERF_AMD_EINVAL, "dirs_stride < 3");
+    if (N && (!weights || !z || (mul_norm && !dirs))) return fail(NERF_AMD_EINVAL, "NULL argument");
+    if (N && n_quantiles && !depth_q) return fail(NERF_AMD_EINVAL, "NULL argument: depth_q (with n_quantiles > 0)");
+    return hip_status(sk_ray_depth_stats(weights, z, z_stride, closed, dirs, dirs_stride, N, Sn, mul_norm, quantiles, n_quantiles, near, far, opacity, depth_q,
+                                         S(stream)), "nerf_amd_ray_depth_stats");
 }
 
 size_t nerf_amd_gemm_workspace_bytes(int64_t M, int64_t N, int64_t P) {

@@ -88,6 +88,9 @@ int sk_warped_resample_window(const float* density, const float* s_c, const floa
                               float far, float gn, float gf, uint64_t rng_seed, int64_t rng_ray_offset, float* z_fine, float* s_fine, hipStream_t st);
 int sk_composite(const float* rgbo, const float* z, int z_stride, const float* dirs, int dirs_stride, int64_t N, int S, int flags, int act, float sigma_shift, float near, float far,
                  const float* normal, const float* cam_dir, float* rgb, float* weights, float* depth, float* normal_img, hipStream_t st);
+// quantiles: host, n_quantiles <= NERF_AMD_DEPTH_QUANTILES_MAX values in (0, 1), passed to the kernel by value (validated by the caller)
+int sk_ray_depth_stats(const float* w, const float* z, int z_stride, int closed, const float* dirs, int dirs_stride, int64_t N, int S, int mul_norm,
+                       const float* quantiles, int n_quantiles, float near, float far, float* opacity, float* depth_q, hipStream_t st);
 int sk_get_bounds(const float* w, const int64_t* below, int64_t N, int C, int K, float* bounds, hipStream_t st);
 int sk_weights_backward(const float* sigma, int sigma_stride, int sigma_off, const float* z, int z_stride, const float* dirs, int dirs_stride, int64_t N, int S, int mul_norm, int act,
                         float sigma_shift, const float* rgbo, const float* d_rgb, const float* d_weights, const float* d_depth, int white_bkg, float near, float far, float* d_sigma,

@@ -1046,6 +1046,66 @@ __global__ __launch_bounds__(256) void composite_kernel(CompositeArgs a) {
     }
 }
 
+// ---------------------------------------------------------------------------------------- depth quantiles and opacity of a composited ray
+// The definition is in include/nerf_amd.h (nerf_amd_ray_depth_stats) and, in fp64, in tests/depth_stats_ref.py.  One wavefront per ray, a
+// ray in 64-sample chunks: the cumulative mass C is an fp64 wave scan plus an fp64 carry, a ballot of C_incl >= q picks the crossing lane,
+// which interpolates in fp64 and stores; t_{k+1} is the next lane's t, or lane 0 of the next chunk (loaded one chunk ahead).  All quantiles
+// are resolved in the one pass.  No LDS, no atomics, no host state: deterministic and capturable; no limit on S.
+struct DepthStatsArgs {
+    const float* w; const float* z; int z_stride; int closed; const float* dirs; int dirs_stride; int64_t N; int S; int mul_norm;
+    float q[NERF_AMD_DEPTH_QUANTILES_MAX]; int nq; float near, far; float* opacity; float* depth_q;
+};
+__global__ __launch_bounds__(256) void ray_depth_stats_kernel(DepthStatsArgs a) {
+    const int lane = lane_id();
+    const int S = a.S, E = a.S + (a.closed ? 1 : 0);
+    for (int64_t n = blockIdx.x * (int64_t)WAVES_PER_BLOCK + wave_in_block(); n < a.N; n += (int64_t)gridDim.x * WAVES_PER_BLOCK) {
+        float nrm = 1.0f;
+        if (a.mul_norm) { const float* dd = a.dirs + n * a.dirs_stride; nrm = norm3(dd[0], dd[1], dd[2]); }
+        const float* ww = a.w + n * S;
+        const float* zz = a.z + n * a.z_stride;
+        float* dq = a.depth_q ? a.depth_q + n * a.nq : nullptr;
+        const float scale = a.far - a.near;
+        double carry = 0.0;
+        int open_q = dq ? (1 << a.nq) - 1 : 0;                  // bit j: quantile j has not crossed yet (wave-uniform)
+        float z_nxt = (lane < E) ? zz[lane] : 0.0f;
+        for (int base = 0; base < S; base += 64) {
+            const int s = base + lane;
+            const float wv = (s < S) ? ww[s] : 0.0f;
+            const float t = a.mul_norm ? z_nxt * nrm : z_nxt;   // the arithmetic of composite_kernel's zn
+            z_nxt = (s + 64 < E) ? zz[s + 64] : 0.0f;
+            float t_up = __shfl_down(t, 1, 64);                  // t of sample s + 1: the next lane, or lane 0 of the next chunk
+            const float first = __shfl(a.mul_norm ? z_nxt * nrm : z_nxt, 0, 64);
+            if (lane == 63) t_up = first;
+            const double incl = wave_incl_scan_add((double)wv) + carry;
+            const double excl = wave_shift_up1(incl, carry);
+            carry = wave_last(incl);
+#pragma unroll
+            for (int j = 0; j < NERF_AMD_DEPTH_QUANTILES_MAX; ++j) {
+                if (!(open_q & (1 << j))) continue;             // wave-uniform
+                const double q = (double)a.q[j];
+                // (w > 0 holds at the crossing by definition; asked for here so that the last bit of a prefix never selects an empty interval)
+                const unsigned long long hit = __ballot(s < S && wv > 0.0f && incl >= q);
+                if (!hit) continue;
+                open_q &= ~(1 << j);
+                if (lane == __builtin_ctzll(hit)) {
+                    float D = t;                                 // k = S - 1 of an open row: no edge behind it
+                    if (s + 1 < E) D = (float)((double)t + ((q - excl) / (double)wv) * ((double)t_up - (double)t));
+                    dq[j] = (D - a.near) / scale;
+                }
+            }
+        }
+        if (lane == 0) {
+            if (a.opacity) a.opacity[n] = (float)carry;
+            if (open_q) {                                        // the ray never accumulates q: the far edge
+                const float zl = zz[E - 1];
+                const float D = a.mul_norm ? zl * nrm : zl;
+                for (int j = 0; j < a.nq; ++j)
+                    if (open_q & (1 << j)) dq[j] = (D - a.near) / scale;
+            }
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------------------- row 11
 template <class T> static inline __host__ __device__ T gb_lds_floats(T C) { return C + 1; }               // per wave: the summed-area row sat[C + 1]
 __global__ __launch_bounds__(256) void get_bounds_kernel(const float* __restrict__ w, const int64_t* __restrict__ below,
@@ -2204,6 +2264,14 @@ int nk::sk_composite(const float* rgbo, const float* z, int z_stride, const floa
     if (N == 0) return 0;
     CompositeArgs a{rgbo, z, z_stride, dirs, dirs_stride, N, S, flags, act, sigma_shift, near, far, normal, cam_dir, rgb, weights, depth, normal_img};
     hipLaunchKernelGGL(composite_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), 0, st, a);
+    return (int)hipGetLastError();
+}
+int nk::sk_ray_depth_stats(const float* w, const float* z, int z_stride, int closed, const float* dirs, int dirs_stride, int64_t N, int S, int mul_norm,
+                           const float* quantiles, int n_quantiles, float near, float far, float* opacity, float* depth_q, hipStream_t st) {
+    if (N == 0 || (!opacity && !(depth_q && n_quantiles))) return 0;
+    DepthStatsArgs a{w, z, z_stride, closed ? 1 : 0, dirs, dirs_stride, N, S, mul_norm ? 1 : 0, {}, depth_q ? n_quantiles : 0, near, far, opacity, depth_q};
+    for (int j = 0; j < a.nq; ++j) a.q[j] = quantiles[j];
+    hipLaunchKernelGGL(ray_depth_stats_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), 0, st, a);
     return (int)hipGetLastError();
 }
 int nk::sk_get_bounds(const float* w, const int64_t* below, int64_t N, int C, int K, float* bounds, hipStream_t st) {

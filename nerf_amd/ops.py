@@ -841,19 +841,107 @@ def _render_buffers(need: int, workspace: Optional[torch.Tensor], dev, N: int, w
     return workspace, rgb, depth, third
 
 
+# ------------------------------------------------------------------------------------------------ depth quantiles and opacity
+def depth_quantiles(quantiles, who: str = "nerf_amd") -> tuple:
+    """None / () -> (); else the quantiles as a tuple of floats, checked on the host: at most DEPTH_QUANTILES_MAX, each in (0, 1)."""
+    if quantiles is None:
+        return ()
+    try:
+        q = tuple(float(v) for v in ([quantiles] if isinstance(quantiles, (int, float)) else quantiles))
+    except (TypeError, ValueError):
+        raise ValueError("%s: quantiles must be numbers in (0, 1) (got %r)" % (who, quantiles)) from None
+    if len(q) > _lib.DEPTH_QUANTILES_MAX:
+        raise ValueError("%s: at most %d quantiles per call (got %d)" % (who, _lib.DEPTH_QUANTILES_MAX, len(q)))
+    for v in q:
+        if not 0.0 < v < 1.0:                                  # (NaN fails both comparisons)
+            raise ValueError("%s: a quantile must lie in (0, 1) (got %r)" % (who, v))
+    return q
+
+
+def ray_depth_stats(weights: torch.Tensor, z: torch.Tensor, dirs: Optional[torch.Tensor] = None, *, quantiles=(0.5,), near: float = 0.0, far: float = 1.0,
+                    mul_norm: bool = True, want_opacity: bool = True):
+    """Quantile (default: median) ray-termination depths and accumulated opacity of composited rays (nerf_amd_ray_depth_stats; the
+    definition is in include/nerf_amd.h and, in fp64, in tests/depth_stats_ref.py).  ``weights`` (N,S) >= 0, ``z`` (N,S+1) -- the row also
+    holds the edge that closes the last interval -- or (N,S) (open); rows of ``z`` may be a strided view.  ``dirs``: (N,3) directions or
+    the (N,6) ray table; t = z |d| when given and ``mul_norm``, else t = z.  The cumulative mass C is summed in fp64 and is ABSOLUTE, not
+    renormalised: with k the first interval at which C reaches q, D_q = t_k + (q - C_k) / w_k (t_{k+1} - t_k) (open row, last interval:
+    t_{S-1}); a ray that never accumulates q reports its far edge t_{E-1}.  -> (depth_q (N,Q) = (D_q - near) / (far - near) | None when no
+    quantile is asked for, opacity (N,) = C_S | None)."""
+    q = depth_quantiles(quantiles, "nerf_amd.ray_depth_stats")
+    if weights.dim() != 2 or z.dim() != 2 or weights.shape[1] < 1 or z.shape[0] != weights.shape[0] or z.shape[1] - weights.shape[1] not in (0, 1):
+        raise ValueError("nerf_amd.ray_depth_stats: weights (N,S) with S >= 1 and z (N,S+1) or (N,S) (got %s and %s)" % (tuple(weights.shape), tuple(z.shape)))
+    N, S = weights.shape
+    if dirs is not None and (dirs.dim() != 2 or dirs.shape[0] != N or dirs.shape[1] not in (3, 6)):
+        raise ValueError("nerf_amd.ray_depth_stats: dirs is (N,3) directions or the (N,6) ray table (got %s)" % (tuple(dirs.shape),))
+    weights = _dev(weights, "weights")
+    if not (z.is_cuda and z.dtype == torch.float32 and z.stride(1) == 1 and z.stride(0) >= z.shape[1]):
+        z = _dev(z, "depths")
+    dirs_ptr, dirs_stride = None, 3
+    if dirs is not None and mul_norm:
+        dirs = _dev(dirs, "dirs")
+        dirs_ptr, dirs_stride = C.c_void_p(dirs.data_ptr() + (12 if dirs.shape[1] == 6 else 0)), dirs.shape[1]
+    dev = weights.device
+    depth_q = torch.empty((N, len(q)), dtype=torch.float32, device=dev) if q else None
+    opacity = torch.empty((N,), dtype=torch.float32, device=dev) if want_opacity else None
+    check(lib.nerf_amd_ray_depth_stats(_ptr(weights), _ptr(z), z.stride(0), int(z.shape[1] == S + 1), dirs_ptr, dirs_stride, N, S, int(dirs_ptr is not None),
+                                       (C.c_float * len(q))(*q) if q else None, len(q), float(near), float(far), _ptr(opacity), _ptr(depth_q), _stream()),
+          "nerf_amd_ray_depth_stats")
+    return depth_q, opacity
+
+
+def _render_request(packed_prop, packed_fine, precision, rays, camera, ray_offset, z_base, u_strat, u_inv, N, n_fine, near, far, white_bkg, dev, *,
+                    q, want_opacity, want_fine_depths, want_depth, want_weights, workspace, prop_pnum=0, spacing=_lib.SPACING_LINEAR, ref=False,
+                    ref_flags=0, cam_dir=None):
+    """One of the four render entry points through nerf_amd_render, with the outputs they have no argument for.
+    -> (rgb, depth | None, weights | None, normal_img | None, workspace, {"depth_q" (N,Q) | None, "opacity" (N,) | None, "fine_depths" (N,E) | None})"""
+    S = n_fine + (64 if ref else 0)
+
+    def out(shape, want=True):
+        return torch.empty(shape, dtype=torch.float32, device=dev) if want else None
+    rgb, depth, w, normal_img = out((N, 3)), out((N,), want_depth), out((N, S), want_weights), out((N,), ref and cam_dir is not None)
+    extras = {"depth_q": out((N, len(q)), bool(q)), "opacity": out((N,), want_opacity), "fine_depths": out((N, S if ref else S + 1), want_fine_depths)}
+    r = _lib.RenderRequest(packed_prop=packed_prop.data_ptr(), packed_fine=packed_fine.data_ptr(), precision=precision, ref=int(ref), ref_flags=int(ref_flags),
+                           white_bkg=int(white_bkg), ray_offset=int(ray_offset), N=N, n_fine=int(n_fine), prop_pnum=int(prop_pnum), spacing=spacing,
+                           near=float(near), far=float(far), n_quantiles=len(q))
+    if camera is not None:
+        r.camera = C.pointer(camera)
+    for name, t in (("rays", rays), ("z_base", z_base), ("u_strat", u_strat), ("u_inv", u_inv), ("cam_dir", cam_dir), ("rgb", rgb), ("depth", depth),
+                    ("weights", w), ("normal_img", normal_img), ("opacity", extras["opacity"]), ("depth_q", extras["depth_q"]), ("fine_depths", extras["fine_depths"])):
+        if t is not None:
+            setattr(r, name, t.data_ptr())
+    for j, v in enumerate(q):
+        r.quantiles[j] = v
+    need = lib.nerf_amd_render_request_workspace_bytes(C.byref(r))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    check(lib.nerf_amd_render(C.byref(r), _ptr(workspace), _stream()), "nerf_amd_render")
+    return rgb, depth, w, normal_img, workspace, extras
+
+
 def render_rays(packed_prop, packed_mip, precision, rays, z_base, u_strat, u_inv, n_fine, near, far, white_bkg,
                 want_depth=True, want_weights=False, workspace: Optional[torch.Tensor] = None, camera: Optional[Samples] = None,
                 ray_offset: int = 0, n_rays: Optional[int] = None, contract: bool = False, ipe_radius: Optional[float] = None,
-                seed: Optional[int] = None, rng_ray_offset: int = 0, ipe_dir_norm: Optional[torch.Tensor] = None):
+                seed: Optional[int] = None, rng_ray_offset: int = 0, ipe_dir_norm: Optional[torch.Tensor] = None, *, quantiles=None,
+                want_opacity: bool = False, want_fine_depths: bool = False):
     """The tile body of render_image (procedures.py:64-85) for all given rays in four launches.  `contract`: Mip-NeRF 360 scene
     contraction of every sample position (proposal and fine) before encoding.  `ipe_radius`: the fine pass encodes the conical frusta
     between consecutive fine depths with the integrated PE (mip_methods.py:15-58; explicit `rays` required).
     u_strat = u_inv = None with `seed`: every uniform is drawn inside the kernels (Philox4x32-10 keyed by `seed`, a pure function of
-    (ray index + rng_ray_offset, sample)); pass `n_rays` (or rays) for the ray count."""
+    (ray index + rng_ray_offset, sample)); pass `n_rays` (or rays) for the ray count.
+    ``quantiles`` (up to 4 values in (0, 1)), ``want_opacity``, ``want_fine_depths`` (keyword-only; here and in render_rays_warped,
+    _rounds_stats and _ref): when any is set the call goes through nerf_amd_render -- the same launches, then ray_depth_stats of the composited
+    weights and depth row -- and a dict {"depth_q" (N,Q), "opacity" (N,), "fine_depths" (N,E)} (None where not asked for; Ref-NeRF also
+    "weights") follows the usual four results.  The mass is absolute: a ray that never accumulates q reports its far edge."""
+    q = depth_quantiles(quantiles, "nerf_amd.render_rays")
     u_strat, u_inv, seed, dev, N = _render_batch(rays, z_base, u_strat, u_inv, seed, n_rays)
     if ipe_radius is not None and rays is None:
         raise ValueError("nerf_amd: integrated PE needs an explicit ray table")
     camera, _keep = _render_descriptor(camera, contract, ipe_radius, ipe_dir_norm, seed, rng_ray_offset)
+    if q or want_opacity or want_fine_depths:
+        rgb, depth, w, _, workspace, extras = _render_request(packed_prop, packed_mip, _prop_prec(packed_prop, precision, packed_mip), rays, camera, ray_offset, z_base,
+                                                              u_strat, u_inv, N, n_fine, near, far, white_bkg, dev, q=q, want_opacity=want_opacity,
+                                                              want_fine_depths=want_fine_depths, want_depth=want_depth, want_weights=want_weights, workspace=workspace)
+        return rgb, depth, w, workspace, extras
     workspace, rgb, depth, w = _render_buffers(lib.nerf_amd_render_workspace_bytes(N, n_fine), workspace, dev, N, want_depth, (N, n_fine) if want_weights else None)
     check(lib.nerf_amd_render_rays(_ptr(packed_prop), _ptr(packed_mip), _prop_prec(packed_prop, precision, packed_mip), _ptr(rays),
                                    C.byref(camera) if camera is not None else None, ray_offset, _ptr(z_base), _ptr(u_strat),
@@ -932,13 +1020,21 @@ def warped_resample(density: torch.Tensor, s_c: torch.Tensor, rays: torch.Tensor
 
 def render_rays_warped(packed_prop, packed_mip, precision, rays, u_strat, u_inv, n_fine, near, far, white_bkg, *, want_depth=True, want_weights=False,
                        workspace: Optional[torch.Tensor] = None, contract: bool = False, ipe_radius: Optional[float] = None, seed: Optional[int] = None,
-                       rng_ray_offset: int = 0, ipe_dir_norm: Optional[torch.Tensor] = None, spacing: str = "disparity"):
+                       rng_ray_offset: int = 0, ipe_dir_norm: Optional[torch.Tensor] = None, spacing: str = "disparity", quantiles=None,
+                       want_opacity: bool = False, want_fine_depths: bool = False):
     """ops.render_rays under disparity spacing (nerf_amd_render_rays_warped): explicit rays (N,6); ``depth`` is W^-1 of the expected
     metric depth, in [0, 1].  u_strat = u_inv = None with ``seed``: in-kernel Philox uniforms, as in render_rays.  n_fine <= 623 (the
-    resampling kernel's LDS rows, include/nerf_amd.h)."""
+    resampling kernel's LDS rows, include/nerf_amd.h).  ``quantiles`` / ``want_opacity`` / ``want_fine_depths``: as in render_rays; the
+    quantile depths are W^-1 of the metric quantile depths, in the same [0, 1] scale as ``depth``."""
+    q = depth_quantiles(quantiles, "nerf_amd.render_rays_warped")
     rays = _dev(rays, "rays")
     u_strat, u_inv, seed, dev, N = _render_batch(rays, None, u_strat, u_inv, seed, rays.shape[0])
     camera, _keep = _render_descriptor(None, contract, ipe_radius, ipe_dir_norm, seed, rng_ray_offset)
+    if q or want_opacity or want_fine_depths:
+        rgb, depth, w, _, workspace, extras = _render_request(packed_prop, packed_mip, _prop_prec(packed_prop, precision, packed_mip), rays, camera, 0, None, u_strat, u_inv,
+                                                              N, int(n_fine), near, far, white_bkg, dev, q=q, want_opacity=want_opacity, want_fine_depths=want_fine_depths,
+                                                              want_depth=want_depth, want_weights=want_weights, workspace=workspace, spacing=_spacing_kind(spacing))
+        return rgb, depth, w, workspace, extras
     workspace, rgb, depth, w = _render_buffers(lib.nerf_amd_render_warped_workspace_bytes(N, n_fine), workspace, dev, N, want_depth,
                                                (N, n_fine) if want_weights else None)
     check(lib.nerf_amd_render_rays_warped(_ptr(packed_prop), _ptr(packed_mip), _prop_prec(packed_prop, precision, packed_mip), _ptr(rays),
@@ -958,13 +1054,38 @@ def render_rays_rounds(packed_prop, packed_mip, precision, rays, z_base, n_fine,
     in-kernel Philox uniforms of ``seed`` only.  ``prop_pnum`` (3..256) sorted depths are resampled from the first histogram with columns
     [0, prop_pnum) of each ray's inverse-CDF stream, the proposal network is evaluated there, and the n_fine + 1 fine depths are drawn from
     that second histogram with columns [prop_pnum, prop_pnum + n_fine + 1).  ``z_base`` (64) is read under spacing="linear" only; under
-    "disparity" ``depth`` is W^-1 of the expected metric depth.  -> (rgb, depth | None, weights | None, workspace)"""
+    "disparity" ``depth`` is W^-1 of the expected metric depth.  -> (rgb, depth | None, weights | None, workspace)
+    (Depth quantiles, opacity, fine depths: render_rays_rounds_stats -- this signature is pinned as it stands.)"""
+    return _render_rays_rounds(packed_prop, packed_mip, precision, rays, z_base, n_fine, near, far, white_bkg, prop_pnum, seed, rng_ray_offset, spacing, contract,
+                               ipe_radius, ipe_dir_norm, want_depth, want_weights, workspace, (), False, False)
+
+
+def render_rays_rounds_stats(packed_prop, packed_mip, precision, rays, z_base, n_fine, near, far, white_bkg, *, prop_pnum, seed, rng_ray_offset: int = 0,
+                             spacing: str = "linear", contract: bool = False, ipe_radius: Optional[float] = None, ipe_dir_norm: Optional[torch.Tensor] = None,
+                             want_depth=True, want_weights=False, workspace: Optional[torch.Tensor] = None, quantiles=None, want_opacity: bool = False,
+                             want_fine_depths: bool = False):
+    """render_rays_rounds with the keyword-only ``quantiles`` / ``want_opacity`` / ``want_fine_depths`` of render_rays: when any is set the
+    call goes through nerf_amd_render and the dict {"depth_q", "opacity", "fine_depths"} follows the four results; else it IS
+    render_rays_rounds.  The mass is absolute: a ray that never accumulates q reports its far edge."""
+    return _render_rays_rounds(packed_prop, packed_mip, precision, rays, z_base, n_fine, near, far, white_bkg, prop_pnum, seed, rng_ray_offset, spacing, contract,
+                               ipe_radius, ipe_dir_norm, want_depth, want_weights, workspace, depth_quantiles(quantiles, "nerf_amd.render_rays_rounds_stats"),
+                               want_opacity, want_fine_depths)
+
+
+def _render_rays_rounds(packed_prop, packed_mip, precision, rays, z_base, n_fine, near, far, white_bkg, prop_pnum, seed, rng_ray_offset, spacing, contract, ipe_radius,
+                        ipe_dir_norm, want_depth, want_weights, workspace, q, want_opacity, want_fine_depths):
     rays = _dev(rays, "rays")
     N = rays.shape[0]
     kind = _spacing_kind(spacing)
     if kind == _lib.SPACING_LINEAR:
         z_base = _dev(z_base, "z_base")
     camera, _keep = _render_descriptor(None, contract, ipe_radius, ipe_dir_norm, seed, rng_ray_offset)
+    if q or want_opacity or want_fine_depths:
+        rgb, depth, w, _, workspace, extras = _render_request(packed_prop, packed_mip, _prop_prec(packed_prop, precision, packed_mip), rays, camera, 0,
+                                                              z_base if kind == _lib.SPACING_LINEAR else None, None, None, N, int(n_fine), near, far, white_bkg,
+                                                              rays.device, q=q, want_opacity=want_opacity, want_fine_depths=want_fine_depths, want_depth=want_depth,
+                                                              want_weights=want_weights, workspace=workspace, prop_pnum=int(prop_pnum), spacing=kind)
+        return rgb, depth, w, workspace, extras
     workspace, rgb, depth, w = _render_buffers(lib.nerf_amd_render_rounds_workspace_bytes(N, int(n_fine), int(prop_pnum), kind), workspace, rays.device, N,
                                                want_depth, (N, n_fine) if want_weights else None)
     check(lib.nerf_amd_render_rays_rounds(_ptr(packed_prop), _ptr(packed_mip), _prop_prec(packed_prop, precision, packed_mip), _ptr(rays), C.byref(camera), 0,
@@ -976,14 +1097,24 @@ def render_rays_rounds(packed_prop, packed_mip, precision, rays, z_base, n_fine,
 def render_rays_ref(packed_prop, packed_ref, precision, rays, z_base, u_strat, u_inv, n_fine, near, far, white_bkg,
                     want_depth=True, cam_dir: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
                     camera: Optional[Samples] = None, ray_offset: int = 0, n_rays: Optional[int] = None, flags: int = 0,
-                    seed: Optional[int] = None, rng_ray_offset: int = 0, contract: bool = False):
+                    seed: Optional[int] = None, rng_ray_offset: int = 0, contract: bool = False, *, quantiles=None, want_opacity: bool = False,
+                    want_fine_depths: bool = False):
     """The tile body of render_image for a Ref-NeRF fine network (procedures.py:64-85, is_ref_model branch) in six launches.
     `cam_dir` (3,) = render_pose[:, -2] asks for the normal image (procedures.py:79-81).  u_strat = u_inv = None with `seed`: in-kernel
-    uniforms as in render_rays."""
+    uniforms as in render_rays.  ``quantiles`` / ``want_opacity`` / ``want_fine_depths``: as in render_rays, on the n_fine + 64 merged
+    depths (an open row); the trailing dict then also holds "weights" (N, n_fine + 64)."""
+    q = depth_quantiles(quantiles, "nerf_amd.render_rays_ref")
     u_strat, u_inv, seed, dev, N = _render_batch(rays, z_base, u_strat, u_inv, seed, n_rays)
     # contract: Mip-NeRF 360 scene contraction of every sample position (the build's own definition); a caller's descriptor keeps its own flag
     camera, _keep = _render_descriptor(camera, True if contract else None, None, None, seed, rng_ray_offset)
     cam_dir = _dev(cam_dir, "cam_dir") if cam_dir is not None else None
+    if q or want_opacity or want_fine_depths:
+        rgb, depth, w, normal_img, workspace, extras = _render_request(packed_prop, packed_ref, _prop_prec(packed_prop, precision), rays, camera, ray_offset, z_base, u_strat,
+                                                                       u_inv, N, n_fine, near, far, white_bkg, dev, q=q, want_opacity=want_opacity,
+                                                                       want_fine_depths=want_fine_depths, want_depth=want_depth, want_weights=True, workspace=workspace,
+                                                                       ref=True, ref_flags=flags, cam_dir=cam_dir)
+        extras["weights"] = w
+        return rgb, depth, normal_img, workspace, extras
     workspace, rgb, depth, normal_img = _render_buffers(lib.nerf_amd_render_ref_workspace_bytes(N, n_fine), workspace, dev, N, want_depth,
                                                         (N,) if cam_dir is not None else None)
     check(lib.nerf_amd_render_rays_ref(_ptr(packed_prop), _ptr(packed_ref), _prop_prec(packed_prop, precision), int(flags), _ptr(rays),

@@ -236,7 +236,8 @@ def broadcast_parameters(modules: Sequence[torch.nn.Module], src: int = 0, group
 
 def render_image_sharded(network, prop_net, render_pose, image_size, focal, near, far, sample_num=128, white_bkg=False,
                          render_depth=False, gather: bool = True, seed: int = 0, group=None, render_normal=False, contract: bool = False,
-                         ipe=False, *, spacing: str = "linear", prop_rounds: int = 1, prop_pnum: Optional[int] = None, ipe_cov: str = "metric") -> dict:
+                         ipe=False, *, spacing: str = "linear", prop_rounds: int = 1, prop_pnum: Optional[int] = None, ipe_cov: str = "metric",
+                         depth_quantiles=None, render_opacity: bool = False) -> dict:
     """Ray-sharded whole-image render: rank r renders a contiguous 256-aligned slice of the image's (tile-ordered) ray list through
     ``procedures.render_image``'s own body -- MipNeRF, Ref-NeRF and layer-by-layer networks alike.  Every uniform is drawn in the kernels
     with Philox keyed by (``seed``, GLOBAL ray index), so the gathered image does not depend on the world size: it is bit-identical to
@@ -245,7 +246,9 @@ def render_image_sharded(network, prop_net, render_pose, image_size, focal, near
     ``{"rgb_rays", "depth_rays", "normal_rays", "range"}`` of this rank's slice).  ``spacing`` is render_image's: under "disparity" too every
     uniform is a function of the global ray index, so the shards reproduce the whole image.  ``prop_rounds`` / ``prop_pnum`` likewise (the
     second proposal round draws further columns of the same per-ray stream), and ``ipe_cov`` (the contracted frustum covariance is a function
-    of the ray, its depths and the whole image's direction norm)."""
+    of the ray, its depths and the whole image's direction norm).  ``depth_quantiles`` / ``render_opacity`` are render_image's too: per-ray
+    functions of the same weights and depths, gathered like the depth into "depth_quantiles" (Q,H,W) and "opacity_img" (H,W)
+    (gather=False: "depth_q_rays", "opacity_rays")."""
     from . import ops
     from .procedures import get_patch_size, render_image
     ops.ipe_contract(contract, ipe, ipe_cov, "nerf_amd.parallel.render_image_sharded")
@@ -256,7 +259,7 @@ def render_image_sharded(network, prop_net, render_pose, image_size, focal, near
     start, end = shard_range(n, rank, world, align=256)
     part = render_image(network, prop_net, render_pose, image_size, focal, near, far, sample_num, white_bkg, render_depth, render_normal,
                         rng="philox", contract=contract, ipe=ipe, seed=int(seed), _shard=(start, end), spacing=spacing,
-                        prop_rounds=prop_rounds, prop_pnum=prop_pnum, ipe_cov=ipe_cov)
+                        prop_rounds=prop_rounds, prop_pnum=prop_pnum, ipe_cov=ipe_cov, depth_quantiles=depth_quantiles, render_opacity=render_opacity)
     if not gather:
         part.pop("to_image")
         return part
@@ -266,4 +269,8 @@ def render_image_sharded(network, prop_net, render_pose, image_size, focal, near
         out["depth_img"] = to_image(gather_shards(part["depth_rays"].unsqueeze(-1), n, 256, group), 1).expand(3, -1, -1).contiguous()
     if part["normal_rays"] is not None:
         out["normal_img"] = to_image(gather_shards(part["normal_rays"].unsqueeze(-1), n, 256, group), 1).expand(3, -1, -1).contiguous()
+    if part.get("depth_q_rays") is not None:
+        out["depth_quantiles"] = to_image(gather_shards(part["depth_q_rays"], n, 256, group), part["depth_q_rays"].shape[1])
+    if part.get("opacity_rays") is not None:
+        out["opacity_img"] = to_image(gather_shards(part["opacity_rays"].unsqueeze(-1), n, 256, group), 1)[0]
     return out

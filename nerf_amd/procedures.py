@@ -50,7 +50,7 @@ GENERIC_CHUNK_RAYS = 4096
 def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, render_depth, chunk: Optional[int] = None,
                           is_ref_model: bool = False, cam_dir=None, seed: Optional[int] = None, ray_offset: int = 0, contract: bool = False,
                           ipe_radius: Optional[float] = None, ipe_dir_norm=None, *, spacing: str = "linear", prop_rounds: int = 1,
-                          prop_pnum: Optional[int] = None, ipe_cov: str = "metric"):
+                          prop_pnum: Optional[int] = None, ipe_cov: str = "metric", depth_quantiles=None, render_opacity: bool = False):
     """The tile body of procedures.py:62-85 as the reference writes it -- stratified depths, ProposalNetwork.forward, get_weights,
     maxBlurFilter, inverseSample, NeRF.length2pts, network.forward, NeRF.render -- on chunks of rays: the route of networks the fused
     render entry (nerf_amd_render_rays) has no packed layout for.  Every call is a HIP kernel of this package; uniforms that were not
@@ -64,15 +64,22 @@ def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sampl
     drawn from that second histogram.  The ray's inverse-CDF stream then has prop_pnum + sample_num + 1 columns: the first prop_pnum feed
     the second round, the rest the fine resampling.
     ``ipe_cov`` (with ``ipe_radius`` and ``contract``): "contracted" = the frustum covariance goes through the contraction with its mean
-    (MipNeRF.forward_rays); the proposal passes contract positions as before."""
+    (MipNeRF.forward_rays); the proposal passes contract positions as before.
+    ``depth_quantiles`` / ``render_opacity`` (render_image's): ops.ray_depth_stats of NeRF.render's weights and the depth row it
+    composited -- the sample_num + 1 sorted depths with their closing edge, Ref-NeRF the merged open row -- normalised like the depth;
+    when either is set a dict {"depth_q" (N,Q) | None, "opacity" (N,) | None} follows the three results."""
     from .mip_methods import maxBlurFilter
     ops.ipe_contract(contract, ipe_radius, ipe_cov, "nerf_amd.render_image")
+    quantiles = ops.depth_quantiles(depth_quantiles, "nerf_amd.render_image")
+    want_stats = bool(quantiles) or bool(render_opacity)
     from .utils import inverseSample
     N = rays.shape[0]
     chunk = GENERIC_CHUNK_RAYS if chunk is None else chunk
     rgb = torch.empty((N, 3), dtype=torch.float32, device=rays.device)
     depth = torch.empty((N,), dtype=torch.float32, device=rays.device) if render_depth else None
     normal_px = torch.empty((N,), dtype=torch.float32, device=rays.device) if cam_dir is not None else None
+    stats = {"depth_q": torch.empty((N, len(quantiles)), dtype=torch.float32, device=rays.device) if quantiles else None,
+             "opacity": torch.empty((N,), dtype=torch.float32, device=rays.device) if render_opacity else None}
     resolution = (far - near) / sample_num                                           # procedures.py:57
     warped = _check_spacing(spacing, near, far)
     for s in range(0, N, chunk):
@@ -105,8 +112,10 @@ def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sampl
         else:
             fine, _ = inverseSample(prop_w, z, sample_num + 1, sort=True, u=u2.contiguous())
         normal = None
+        edges = fine                                                                 # the depth row of the quantiles: the closing edge still on it
         if is_ref_model:                                                             # :71-74
             samples, fine = NeRF.coarseFineMerge(r, z, fine)
+            edges = fine                                                             # (Ref-NeRF: the merged row, open)
             rgbo, normal = network.forward(samples, contract=True) if contract else network.forward(samples)
             rgbo[..., -1] = torch.nn.functional.softplus(rgbo[..., -1] + 0.5)
         elif ipe_radius is not None:                                                  # frusta between the sample_num + 1 sorted depths
@@ -115,15 +124,24 @@ def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sampl
         else:
             fine = fine[..., :-1].contiguous()
             rgbo = network.forward(NeRF.length2pts(r, fine), contract=True) if contract else network.forward(NeRF.length2pts(r, fine))
-        part, _, extras = NeRF.render(rgbo, fine, r[:, 3:], white_bkg=white_bkg, density_act=torch.nn.functional.relu,
-                                      render_depth=((0.0, 1.0) if warped else (near, far)) if render_depth else None,
-                                      normal_info=(normal, cam_dir) if cam_dir is not None else None)
+        part, weights, extras = NeRF.render(rgbo, fine, r[:, 3:], white_bkg=white_bkg, density_act=torch.nn.functional.relu,
+                                            render_depth=((0.0, 1.0) if warped else (near, far)) if render_depth else None,
+                                            normal_info=(normal, cam_dir) if cam_dir is not None else None)
         rgb[s: s + n] = part
+        if want_stats:
+            dq, op = ops.ray_depth_stats(weights, edges.contiguous(), r, quantiles=quantiles, near=0.0 if warped else near, far=1.0 if warped else far,
+                                         want_opacity=bool(render_opacity))
+            if quantiles:
+                stats["depth_q"][s: s + n] = ops.warp_depths(dq, near, far, inverse=True, spacing=spacing)[0] if warped else dq
+            if render_opacity:
+                stats["opacity"][s: s + n] = op
         if render_depth:
             d = extras["depth_img"].reshape(n, 1)
             depth[s: s + n] = (ops.warp_depths(d, near, far, inverse=True, spacing=spacing)[0] if warped else d).reshape(-1)
         if cam_dir is not None:
             normal_px[s: s + n] = extras["normal_img"].reshape(-1)
+    if want_stats:
+        return rgb, depth, normal_px, stats
     return rgb, depth, normal_px
 
 
@@ -165,7 +183,8 @@ def _check_spacing(spacing, near, far) -> bool:
 def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Tensor, image_size, focal,
                  near: float, far: float, sample_num: int = 128, white_bkg: bool = False, render_depth=False,
                  render_normal=False, rng: str = "philox", contract: bool = False, ipe=False, seed: Optional[int] = None,
-                 _shard=None, *, spacing: str = "linear", prop_rounds: int = 1, prop_pnum: Optional[int] = None, ipe_cov: str = "metric") -> dict:
+                 _shard=None, *, spacing: str = "linear", prop_rounds: int = 1, prop_pnum: Optional[int] = None, ipe_cov: str = "metric",
+                 depth_quantiles=None, render_opacity: bool = False) -> dict:
     """Whole-image inference (procedures.py:34-97) -> {"rgb" (3,H,W) [, "depth_img" (3,H,W)]} on
     ``render_pose.device``.  The caller provides ``no_grad``/``eval()`` like for the reference.
     ``rng``, ``contract`` and ``ipe`` are additions.  ``rng``: where the stratified / inverse-CDF uniforms come from --
@@ -203,8 +222,20 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
     leaves the covariance in metric space; "contracted" pushes the whole Gaussian through the linearised contraction like Mip-NeRF 360
     (eq. 11-14: mu' = f(mu), Sigma' = J Sigma J^T), so that the attenuation exp(-0.5 4^l var) is measured in the coordinates the mean
     lives in and the far background keeps its low frequencies.  Every route -- fused, two rounds, disparity,
-    layer by layer, sharded -- computes the same function; frusta inside the unit ball are the same bits under both."""
+    layer by layer, sharded -- computes the same function; frusta inside the unit ball are the same bits under both.
+    ``depth_quantiles`` (keyword-only; an addition): up to 4 values q in (0, 1) -> ``result["depth_quantiles"]`` (Q,H,W), the depth at
+    which a ray's cumulative weight reaches q -- (0.5,) is the median ray-termination depth Mip-NeRF 360 shows, which a little weight far
+    out does not drag through empty space like the expected depth.  Definition (include/nerf_amd.h, tests/depth_stats_ref.py): with the
+    fine pass's weights w_s and sorted depths t_s = z_s |d|, C summed in fp64, k the first interval at which C reaches q,
+    D_q = t_k + (q - C_k) / w_k (t_{k+1} - t_k), normalised like ``depth_img`` ((D - near) / (far - near); W^-1(D) under "disparity").
+    The mass is ABSOLUTE, not renormalised: a ray that never accumulates q (it leaves the scene with opacity < q) reports its far edge.
+    ``render_opacity`` (keyword-only; an addition): ``result["opacity_img"]`` (H,W), the accumulated opacity sum_s w_s -- masks, RGBA
+    export, background replacement.  Both come from one more kernel on what compositing leaves in the workspace, on every route; with
+    neither set the call and the dict are exactly what they were.  A ``_shard`` call adds "depth_q_rays" (n,Q) and "opacity_rays" (n,)."""
     ops.ipe_contract(contract, ipe, ipe_cov, "nerf_amd.render_image")
+    quantiles = ops.depth_quantiles(depth_quantiles, "nerf_amd.render_image")
+    render_opacity = bool(render_opacity)
+    want_stats = bool(quantiles) or render_opacity
     if prop_rounds not in (1, 2):
         raise ValueError("nerf_amd.render_image: prop_rounds must be 1 or 2 (got %r)" % (prop_rounds,))
     if prop_pnum is not None and int(prop_pnum) < 1:
@@ -261,27 +292,36 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
     warped = _check_spacing(spacing, near, far)
     route = _render_route(is_ref_model, generic, warped, prop_rounds, prop_pnum)
     cam_dir = render_pose[:, -2].contiguous() if render_normal else None
+    # depth quantiles / opacity: the fused entry points take them as keywords (and then return their dict last); without them the calls are
+    # exactly what they were
+    stat_kw = dict(quantiles=quantiles, want_opacity=render_opacity) if want_stats else dict()
     if route == "calls":
-        rgb, depth, normal_px = _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, bool(render_depth),
-                                                      is_ref_model=is_ref_model, cam_dir=cam_dir, seed=seed, ray_offset=off, contract=contract,
-                                                      ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, spacing=spacing, prop_rounds=prop_rounds,
-                                                      prop_pnum=prop_pnum, ipe_cov=ipe_cov)
+        out = _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, bool(render_depth),
+                                    is_ref_model=is_ref_model, cam_dir=cam_dir, seed=seed, ray_offset=off, contract=contract,
+                                    ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, spacing=spacing, prop_rounds=prop_rounds,
+                                    prop_pnum=prop_pnum, ipe_cov=ipe_cov, **(dict(depth_quantiles=quantiles, render_opacity=render_opacity) if want_stats else dict()))
+        rgb, depth, normal_px = out[:3]
     elif route == "ref":
         # procedures.py:71-74: coarse and fine depths are merged and sorted (a merge of two ascending sets), the last one dropped,
         # sigma -> softplus(sigma + 0.5) before compositing (nerf_amd_render_rays_ref: six launches)
-        rgb, depth, normal_px, _ = ops.render_rays_ref(prop_net.packed(prec), network.packed(prec), prec, rays, z_base, u_strat, u_inv, sample_num, near, far,
-                                                       white_bkg, want_depth=bool(render_depth), cam_dir=cam_dir, flags=network.kernel_flags, seed=seed,
-                                                       contract=contract, rng_ray_offset=off)
+        out = ops.render_rays_ref(prop_net.packed(prec), network.packed(prec), prec, rays, z_base, u_strat, u_inv, sample_num, near, far,
+                                  white_bkg, want_depth=bool(render_depth), cam_dir=cam_dir, flags=network.kernel_flags, seed=seed,
+                                  contract=contract, rng_ray_offset=off, **stat_kw)
+        rgb, depth, normal_px = out[:3]
     else:
         # (a narrow fine network has no integrated-PE kernel: with ipe its 256-wide -- zero-padded -- blob is used)
         packed = (prop_net.packed(prec), network.packed(prec, wide=bool(ipe)), prec, rays)
-        common = dict(want_depth=bool(render_depth), contract=ops.ipe_contract(contract, ipe, ipe_cov), ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, seed=seed, rng_ray_offset=off)
+        common = dict(want_depth=bool(render_depth), contract=ops.ipe_contract(contract, ipe, ipe_cov), ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, seed=seed, rng_ray_offset=off,
+                      **stat_kw)
         if route == "rounds":
-            rgb, depth, _, _ = ops.render_rays_rounds(*packed, z_base, sample_num, near, far, white_bkg, prop_pnum=prop_pnum, spacing=spacing, **common)
+            out = (ops.render_rays_rounds_stats if want_stats else ops.render_rays_rounds)(*packed, z_base, sample_num, near, far, white_bkg, prop_pnum=prop_pnum,
+                                                                                           spacing=spacing, **common)
         elif route == "warped":
-            rgb, depth, _, _ = ops.render_rays_warped(*packed, u_strat, u_inv, sample_num, near, far, white_bkg, spacing=spacing, **common)
+            out = ops.render_rays_warped(*packed, u_strat, u_inv, sample_num, near, far, white_bkg, spacing=spacing, **common)
         else:
-            rgb, depth, _, _ = ops.render_rays(*packed, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, **common)
+            out = ops.render_rays(*packed, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, **common)
+        rgb, depth = out[:2]
+    stats = out[-1] if want_stats else {"depth_q": None, "opacity": None}
 
     def to_image(t, ch):
         if sz is None:
@@ -292,13 +332,20 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
         return img
 
     if _shard is not None:
-        return {"rgb_rays": rgb, "depth_rays": depth, "normal_rays": normal_px, "range": (off, off + rays.shape[0]), "to_image": to_image}
+        part = {"rgb_rays": rgb, "depth_rays": depth, "normal_rays": normal_px, "range": (off, off + rays.shape[0]), "to_image": to_image}
+        if want_stats:
+            part.update(depth_q_rays=stats["depth_q"], opacity_rays=stats["opacity"])
+        return part
     result = dict()
     result["rgb"] = to_image(rgb, 3)
     if render_depth:
         result["depth_img"] = to_image(depth.unsqueeze(-1), 1).expand(3, -1, -1).contiguous()   # procedures.py:88
     if render_normal:
         result["normal_img"] = to_image(normal_px.unsqueeze(-1), 1).expand(3, -1, -1).contiguous()   # procedures.py:90
+    if quantiles:
+        result["depth_quantiles"] = to_image(stats["depth_q"], len(quantiles))
+    if render_opacity:
+        result["opacity_img"] = to_image(stats["opacity"].unsqueeze(-1), 1)[0]
     return result
 
 

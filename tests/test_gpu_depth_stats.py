@@ -1,0 +1,267 @@
+"""Depth quantiles and opacity on the GPU: the stand-alone kernel against the fp64 specification and its derived bound
+(tests/depth_stats_ref.py), the request entry point against the four entry points it stands for (bit for bit) and against the stand-alone
+kernel on its own outputs (bit for bit: the same kernel on the same inputs), render_image on all five routes, shards, graph capture."""
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import depth_stats_ref as R
+from conftest import gate
+from nerf_amd import synthetic_weights as W
+from oracle import nerf_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+SEED = 0x5EED0DE9
+QS = (0.02, 0.1, 0.5)
+SPACINGS = {"linear": (2.0, 6.0, False), "disparity": (0.2, 100.0, True)}     # near, far, contract
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _gpu():
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import nerf_amd
+    nerf_amd.set_precision("fp32")
+    yield
+    nerf_amd.set_precision("fp32")
+
+
+def _cuda(*arrays):
+    return [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays]
+
+
+# ------------------------------------------------------------------------------------------------ the kernel against the specification
+@pytest.mark.parametrize("closed", [True, False], ids=["closed", "open"])
+@pytest.mark.parametrize("S", R.GPU_S)
+def test_kernel_against_the_specification(S, closed):
+    from nerf_amd import ops
+    worst, worst_ulps, pairs = 0.0, 0.0, 0
+    for N in R.GPU_N:
+        w, z, dirs = R.make_inputs(N, S, closed, S + N)
+        tw, tz, td = _cuda(w, z, dirs)
+        rays = torch.cat((torch.zeros_like(td), td), 1).contiguous()
+        wide = torch.full((N, z.shape[1] + 3), float("nan"), device="cuda")                 # rows of a longer stride: what lies behind a row is never read
+        wide[:, : z.shape[1]] = tz
+        for qs in ((0.5,), (0.1, 0.5, 0.95), (0.1, 0.25, 0.5, 0.95)):
+            for mul in (True, False):
+                for z_in, d_in in ((tz, td), (wide[:, : z.shape[1]], rays)):
+                    dq, op = ops.ray_depth_stats(tw, z_in, d_in, quantiles=qs, near=2.0, far=6.0, mul_norm=mul)
+                    assert dq.shape == (N, len(qs)) and op.shape == (N,)
+                    ratio, ulps, n_excl, n_pairs = R.check(dq.cpu().numpy(), op.cpu().numpy(), w, z, dirs, qs, 2.0, 6.0, mul)
+                    assert n_excl == 0                                                       # (at most 1 % may be excluded: none is)
+                    worst, worst_ulps, pairs = max(worst, ratio), max(worst_ulps, ulps), pairs + n_pairs
+    print("S %d %s: %d pairs, worst err / tol %.3f, opacity within %.1f ulp" % (S, "closed" if closed else "open", pairs, worst, worst_ulps))
+    gate("ray_depth_stats vs fp64 specification, S %d %s: max err / tol" % (S, "closed" if closed else "open"), worst, 1.0)
+    assert worst_ulps <= 1.0
+
+
+def test_crossings_in_the_last_lane_and_in_lane_zero_of_the_next_chunk_and_the_optional_outputs():
+    from nerf_amd import ops
+    w, z, dirs = R.make_inputs(67, 129, True, 0)
+    k = R.spec(w, z, dirs, (0.5,))["k"][:, 0]
+    assert {63, 64} <= set(k.tolist()) and -1 in set(k.tolist())                             # both sides of the chunk boundary, and rays that never reach q
+    tw, tz, td = _cuda(w, z, dirs)
+    dq, op = ops.ray_depth_stats(tw, tz, td, quantiles=(0.5,))
+    only_q, none = ops.ray_depth_stats(tw, tz, td, quantiles=(0.5,), want_opacity=False)
+    none_q, only_op = ops.ray_depth_stats(tw, tz, td, quantiles=None)
+    assert none is None and none_q is None and torch.equal(only_q, dq) and torch.equal(only_op, op)
+    no_dirs, _ = ops.ray_depth_stats(tw, tz, quantiles=(0.5,))                               # no directions: t = z
+    assert torch.equal(no_dirs, ops.ray_depth_stats(tw, tz, td, quantiles=(0.5,), mul_norm=False)[0])
+    assert R.check(no_dirs.cpu().numpy(), None, w, z, None, (0.5,))[0] <= 1.0
+    empty = ops.ray_depth_stats(tw[:0], tz[:0], td[:0])
+    assert empty[0].shape == (0, 1) and empty[1].shape == (0,)
+
+
+def test_graph_capture_and_replay():
+    from nerf_amd import ops
+    w, z, dirs = R.make_inputs(67, 300, True, 1)
+    tw, tz, td = _cuda(w, z, dirs)
+    want = ops.ray_depth_stats(tw, tz, td, quantiles=QS, near=2.0, far=6.0)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        got = ops.ray_depth_stats(tw, tz, td, quantiles=QS, near=2.0, far=6.0)
+    w2, _, _ = R.make_inputs(67, 300, True, 2)
+    tw.copy_(torch.from_numpy(w2).cuda())                                                    # new contents in the captured buffers
+    want2 = ops.ray_depth_stats(tw, tz, td, quantiles=QS, near=2.0, far=6.0)
+    graph.replay()
+    torch.cuda.synchronize()
+    assert torch.equal(got[0], want2[0]) and torch.equal(got[1], want2[1]) and not torch.equal(want2[0], want[0])
+
+
+# ------------------------------------------------------------------------------------------------ the request entry point
+@functools.lru_cache(maxsize=None)
+def _nets():
+    from nerf_amd.addtional import ProposalNetwork
+    from nerf_amd.mip_model import MipNeRF
+    from nerf_amd.ref_model import RefNeRF
+    prop, mip, ref = ProposalNetwork(10, 256), MipNeRF(10, 4, 256), RefNeRF(10, 4)
+    prop.load_state_dict(W.proposal_state("small"))
+    mip.load_state_dict(W.mip_state("small"))
+    ref.load_state_dict(W.ref_state("small"))
+    return prop.cuda().eval(), mip.cuda().eval(), ref.cuda().eval()
+
+
+def _camera(side=40):
+    return O.pose_spherical(30.0, -30.0, 4.0)[:3].contiguous().cuda(), O.fov2focal(0.6911112070083618, (side, side))
+
+
+@functools.lru_cache(maxsize=None)
+def _rays(n=200):
+    from nerf_amd import ops, utils
+    pose, focal = _camera()
+    fx, fy = utils._focal_xy(focal)
+    return ops.generate_rays(pose, 40, 40, fx, fy, pose.device)[700: 700 + n].contiguous()
+
+
+ENTRIES = ("plain", "warped", "rounds", "ref")
+
+
+def _entry(entry, precision, nf, want_weights=True, **kw):
+    """one of the four ops.render_rays* on 200 rays with in-kernel uniforms -> its result tuple"""
+    import nerf_amd
+    from nerf_amd import ops
+    nerf_amd.set_precision(precision)
+    prec = ops.BF16 if precision == "bf16" else ops.F32
+    prop, mip, ref = _nets()
+    rays = _rays()
+    near, far, contract = SPACINGS["disparity" if entry == "warped" else "linear"]
+    z_base = torch.linspace(near, far, 64).cuda()
+    with torch.no_grad():
+        if entry == "plain":
+            return ops.render_rays(prop.packed(prec), mip.packed(prec), prec, rays, z_base, None, None, nf, near, far, True, want_weights=want_weights, seed=SEED, **kw)
+        if entry == "warped":
+            return ops.render_rays_warped(prop.packed(prec), mip.packed(prec), prec, rays, None, None, nf, near, far, True, want_weights=want_weights, seed=SEED,
+                                          contract=contract, **kw)
+        if entry == "rounds":
+            return (ops.render_rays_rounds_stats if kw else ops.render_rays_rounds)(prop.packed(prec), mip.packed(prec), prec, rays, z_base, nf, near, far, True,
+                                                                                    prop_pnum=16, seed=SEED, want_weights=want_weights, **kw)
+        return ops.render_rays_ref(prop.packed(prec), ref.packed(prec), prec, rays, z_base, None, None, nf, near, far, True, flags=ref.kernel_flags, seed=SEED, **kw)
+
+
+def _request_without_new_outputs(entry, precision, nf):
+    """the same call through nerf_amd_render with opacity, depth_q and fine_depths NULL -> (rgb, depth, weights | None)"""
+    from nerf_amd import _lib, ops
+    prec = ops.BF16 if precision == "bf16" else ops.F32
+    prop, mip, ref = _nets()
+    rays = _rays()
+    near, far, contract = SPACINGS["disparity" if entry == "warped" else "linear"]
+    camera, _keep = ops._render_descriptor(None, contract if entry == "warped" else (None if entry == "ref" else False), None, None, SEED, 0)
+    fine = ref.packed(prec) if entry == "ref" else mip.packed(prec)
+    pp = ops._prop_prec(prop.packed(prec), prec) if entry == "ref" else ops._prop_prec(prop.packed(prec), prec, fine)
+    with torch.no_grad():
+        out = ops._render_request(prop.packed(prec), fine, pp, rays, camera, 0, None if entry == "warped" else torch.linspace(near, far, 64).cuda(), None, None,
+                                  rays.shape[0], nf, near, far, True, rays.device, q=(), want_opacity=False, want_fine_depths=False, want_depth=True,
+                                  want_weights=entry != "ref", workspace=None, prop_pnum=16 if entry == "rounds" else 0,
+                                  spacing=_lib.SPACING_DISPARITY if entry == "warped" else _lib.SPACING_LINEAR, ref=entry == "ref",
+                                  ref_flags=ref.kernel_flags if entry == "ref" else 0)
+    assert out[5] == {"depth_q": None, "opacity": None, "fine_depths": None}
+    return out[0], out[1], out[2]
+
+
+@pytest.mark.parametrize("nf", [32, 128])
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_request_without_new_outputs_is_the_old_entry_point_bit_for_bit(entry, nf):
+    old = _entry(entry, "fp32", nf)
+    new = _request_without_new_outputs(entry, "fp32", nf)
+    assert bool(torch.isfinite(old[0]).all()) and float(old[0].std()) > 1e-4
+    assert torch.equal(new[0], old[0]) and torch.equal(new[1], old[1])
+    if entry != "ref":
+        assert torch.equal(new[2], old[2])
+
+
+@pytest.mark.parametrize("precision", ["fp32", "bf16"])
+@pytest.mark.parametrize("nf", [32, 128])
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_new_outputs_are_the_stand_alone_kernel_on_the_returned_weights_and_depths(entry, nf, precision):
+    from nerf_amd import ops
+    old = _entry(entry, precision, nf)
+    new = _entry(entry, precision, nf, quantiles=QS, want_opacity=True, want_fine_depths=True)
+    x = new[4]
+    weights = x["weights"] if entry == "ref" else new[2]
+    E = nf + 64 if entry == "ref" else nf + 1
+    assert x["fine_depths"].shape == (200, E) and weights.shape == (200, E if entry == "ref" else nf) and x["depth_q"].shape == (200, 3)
+    assert torch.equal(new[0], old[0]) and torch.equal(new[1], old[1])                       # rgb, depth: untouched
+    if entry == "ref":
+        assert old[2] is None and new[2] is None                                             # (no cam_dir: no normal image)
+    else:
+        assert torch.equal(new[2], old[2])
+    near, far, _ = SPACINGS["disparity" if entry == "warped" else "linear"]
+    rays = _rays()
+    if entry == "warped":
+        raw, op = ops.ray_depth_stats(weights, x["fine_depths"], rays, quantiles=QS, near=0.0, far=1.0)
+        dq = ops.warp_depths(raw, near, far, inverse=True)[0]
+        check_near, check_far = 0.0, 1.0
+    else:
+        raw, op = ops.ray_depth_stats(weights, x["fine_depths"], rays, quantiles=QS, near=near, far=far)
+        dq, check_near, check_far = raw, near, far
+    assert torch.equal(x["depth_q"], dq) and torch.equal(x["opacity"], op)
+    ratio, ulps, n_excl, n_pairs = R.check(raw.cpu().numpy(), op.cpu().numpy(), weights.cpu().numpy(), x["fine_depths"].cpu().numpy(), rays.cpu().numpy(), QS,
+                                           check_near, check_far)
+    reached = float((torch.from_numpy(R.spec(weights.cpu().numpy(), x["fine_depths"].cpu().numpy(), rays.cpu().numpy(), QS)["k"]) >= 0).float().mean())
+    print("%s %s nf %d: err / tol %.3f, opacity %.1f ulp, %d of %d pairs excluded, %.0f %% of the pairs reach their q, opacity %.3f .. %.3f"
+          % (entry, precision, nf, ratio, ulps, n_excl, n_pairs, 100 * reached, float(op.min()), float(op.max())))
+    assert n_excl <= 0.01 * n_pairs
+    gate("request outputs vs fp64 specification, %s %s nf %d: max err / tol" % (entry, precision, nf), ratio, 1.0)
+    assert ulps <= 1.0 and 0.0 < reached
+    # without a weights output the kernel reads the part appended to the workspace: the same bits
+    if entry != "ref":
+        lean = _entry(entry, precision, nf, want_weights=False, quantiles=QS, want_opacity=True)
+        assert lean[2] is None and lean[4]["fine_depths"] is None
+        assert torch.equal(lean[0], old[0]) and torch.equal(lean[4]["depth_q"], x["depth_q"]) and torch.equal(lean[4]["opacity"], x["opacity"])
+
+
+# ------------------------------------------------------------------------------------------------ render_image
+ROUTES = {"plain": dict(), "warped": dict(spacing="disparity"), "rounds": dict(prop_rounds=2, prop_pnum=16), "ref": dict()}
+
+
+def _image(route, monkeypatch=None, **kw):
+    from nerf_amd import procedures
+    prop, mip, ref = _nets()
+    pose, focal = _camera()
+    near, far, contract = SPACINGS["disparity" if route == "warped" else "linear"]
+    if monkeypatch is not None:
+        monkeypatch.setattr(procedures, "_render_route", lambda *a: "calls")
+    with torch.no_grad():
+        return procedures.render_image(ref if route == "ref" else mip, prop, pose, 40, focal, near, far, 64, white_bkg=True, render_depth=True, seed=SEED,
+                                       contract=contract, **ROUTES[route], **kw)
+
+
+@pytest.mark.parametrize("route", list(ROUTES))
+def test_render_image_routes_agree_and_the_default_call_is_unchanged(route, monkeypatch):
+    """Each fused route against the call-by-call route.  The existing tests establish bit equality of rgb and depth between the fused routes
+    and the call-by-call route (test_gpu_ray_warp, test_gpu_two_round_render: plain, warped, rounds; asserted again here for all four), and
+    the new outputs are one deterministic kernel on the weights and depths behind them: bit equality."""
+    plain = _image(route)
+    assert set(plain) == {"rgb", "depth_img"}                                                # the keywords off: exactly today's keys
+    fused = _image(route, depth_quantiles=QS, render_opacity=True)
+    assert set(fused) == {"rgb", "depth_img", "depth_quantiles", "opacity_img"}
+    assert fused["depth_quantiles"].shape == (3, 40, 40) and fused["opacity_img"].shape == (40, 40)
+    assert torch.equal(fused["rgb"], plain["rgb"]) and torch.equal(fused["depth_img"], plain["depth_img"])
+    calls = _image(route, monkeypatch, depth_quantiles=QS, render_opacity=True)
+    d_rgb, d_depth = (fused["rgb"] - calls["rgb"]).abs().max().item(), (fused["depth_img"] - calls["depth_img"]).abs().max().item()
+    d_q, d_op = (fused["depth_quantiles"] - calls["depth_quantiles"]).abs().max().item(), (fused["opacity_img"] - calls["opacity_img"]).abs().max().item()
+    print("%s vs calls: rgb %.3e depth %.3e depth_quantiles %.3e opacity %.3e; opacity %.3f .. %.3f" % (route, d_rgb, d_depth, d_q, d_op,
+                                                                                                     float(fused["opacity_img"].min()), float(fused["opacity_img"].max())))
+    assert torch.equal(fused["rgb"], calls["rgb"]) and torch.equal(fused["depth_img"], calls["depth_img"])
+    assert torch.equal(fused["depth_quantiles"], calls["depth_quantiles"]) and torch.equal(fused["opacity_img"], calls["opacity_img"])
+    q = fused["depth_quantiles"]
+    assert bool(torch.isfinite(q).all()) and bool((q[0] <= q[1]).all()) and bool((q[1] <= q[2]).all())      # D_q is monotone in q
+    # (NeRF.render closes the last interval with delta = 1e10: a ray whose last sample has any density accumulates all of its mass)
+    assert float(fused["opacity_img"].min()) >= 0.0 and float(fused["opacity_img"].max()) <= 1.0 + 1e-5
+    only_op = _image(route, render_opacity=True)
+    assert set(only_op) == {"rgb", "depth_img", "opacity_img"} and torch.equal(only_op["opacity_img"], fused["opacity_img"])
+
+
+@pytest.mark.parametrize("route", ["plain", "warped", "ref"])
+def test_three_shards_reproduce_the_image_bit_for_bit(route):
+    whole = _image(route, depth_quantiles=QS, render_opacity=True)
+    parts = [_image(route, depth_quantiles=QS, render_opacity=True, _shard=s) for s in ((0, 512), (512, 1100), (1100, 1600))]
+    assert all(set(p) == {"rgb_rays", "depth_rays", "normal_rays", "range", "to_image", "depth_q_rays", "opacity_rays"} for p in parts)
+    to_image = parts[0]["to_image"]
+    assert torch.equal(to_image(torch.cat([p["depth_q_rays"] for p in parts]), 3), whole["depth_quantiles"])
+    assert torch.equal(to_image(torch.cat([p["opacity_rays"] for p in parts]).unsqueeze(-1), 1)[0], whole["opacity_img"])
+    assert set(_image(route, _shard=(0, 512))) == {"rgb_rays", "depth_rays", "normal_rays", "range", "to_image"}
