@@ -327,10 +327,15 @@ struct RowsOutT {                                            // accumulators 8 h
                 // one 16-byte load / store per lane instead of two 8-byte ones -- the chain pays per store INSTRUCTION, not per byte.
                 if (q == 1) continue;
                 f32x4 v1 = {acc[8 * half + 4], acc[8 * half + 5], acc[8 * half + 6], acc[8 * half + 7]};
+                // (As inline assembly with read-write operands: through __builtin_amdgcn_permlane32_swap hipcc emitted TWO swaps per store
+                // instead of four -- the second on the results of the first -- and filled elements 1..3 of either group with copies:
+                // three of every four columns of the bf16 rows were wrong.  tests/test_gpu_ref_backward_layers.py, stage `dallin`.
+                // The two v_nop are the wait states between a VALU write of an operand and the swap.)
+                float lo[4] = {v[0], v[1], v[2], v[3]}, hi[4] = {v1[0], v1[1], v1[2], v1[3]};
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, v[i]), __builtin_bit_cast(uint32_t, v1[i]), false, false);
-                    v[i] = __builtin_bit_cast(float, (uint32_t)r[0]); v1[i] = __builtin_bit_cast(float, (uint32_t)r[1]);
+                    asm volatile("v_nop\n\tv_nop\n\tv_permlane32_swap_b32 %0, %1" : "+v"(lo[i]), "+v"(hi[i]));
+                    v[i] = lo[i]; v1[i] = hi[i];
                 }
                 // after the swap: h = 0 holds [own group 0 | partner's group 0] = columns +0..7, h = 1 [partner's group 1 | own group 1] = +8..15
                 bf16x8* p = reinterpret_cast<bf16x8*>(reinterpret_cast<__bf16*>(rows) + m * ld + 32 * fb + 16 * half + 8 * h);

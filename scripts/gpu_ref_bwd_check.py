@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Diagnostic of the hand-written Ref-NeRF training kernels against torch.autograd of the reference expression (tests/torch_spec.py ref_expr)
-on the device: training forward == inference forward, density gradients (RefNeRF.get_grad) of both networks, every parameter gradient."""
+on the device: training forward == inference forward, density gradients (RefNeRF.get_grad) of both networks, every parameter gradient.
+For correctness it is superseded by tests/test_gpu_ref_backward_layers.py (every stage, element by element, fp32 and bf16); kept as a diagnostic."""
 import sys
 
 import torch

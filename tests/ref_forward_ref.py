@@ -216,10 +216,11 @@ def check_normal(aux, normal):
     return _report(normal, torch.stack([v for v, _ in comp], 1), torch.stack([e for _, e in comp], 1))
 
 
-def dir_inputs_ref(aux, dirs, table):
-    """fp64 (value, error) of the 39 computed directional inputs in the reference's column order [real 19 | imag 19 | n.d], from the
-    kernel's own head values and the directions as fetch_sample hands them over (raw, not normalised).  table = the (9, 19) IDE table."""
-    comp, _ = normal_ref(aux)
+def dir_state(aux, dirs):
+    """(value, error) pairs of everything between the head rows and the IDE terms, as ref_kernel forms it -- and as ref_heads_delta_kernel
+    (bwd_kernels.hip) re-forms it with the same expressions: -> dict comp (3 pairs: the normal), nn (|n0| + 1e-7), dot (n.d), r (3 pairs: the
+    reflection), rough, zp / re / im (9 pairs each: z^k, Re / Im (x + i y)^k), att {l: pair}"""
+    comp, nn = normal_ref(aux)
     d = dirs.double()
     o = _zero(d[:, 0])
     dot = _add(*_add(*_mul(d[:, 0], o, *comp[0]), *_mul(d[:, 1], o, *comp[1])), *_mul(d[:, 2], o, *comp[2]))
@@ -238,9 +239,16 @@ def dir_inputs_ref(aux, dirs, table):
         re.append(_add(a[0], a[1], -b[0], b[1]))
         a, b = _mul(*re[k - 1], y, ey), _mul(*im[k - 1], x, ex)
         im.append(_add(*a, *b))
-    att = {}
-    for l, sg in SIGMA.items():
-        att[l] = _exp(*_mul(torch.full_like(o, -sg), o, *rough))
+    att = {l: _exp(*_mul(torch.full_like(o, -sg), o, *rough)) for l, sg in SIGMA.items()}
+    return {"comp": comp, "nn": nn, "dot": dot, "r": r, "rough": rough, "zp": zp, "re": re, "im": im, "att": att}
+
+
+def dir_inputs_ref(aux, dirs, table):
+    """fp64 (value, error) of the 39 computed directional inputs in the reference's column order [real 19 | imag 19 | n.d], from the
+    kernel's own head values and the directions as fetch_sample hands them over (raw, not normalised).  table = the (9, 19) IDE table."""
+    st = dir_state(aux, dirs)
+    dot, zp, re, im, att = st["dot"], st["zp"], st["re"], st["im"], st["att"]
+    o = _zero(dot[0])
     mat = table.double()
     real, imag = [], []
     for t in range(19):
