@@ -635,7 +635,8 @@ int nerf_amd_ray_depth_stats(const float* weights, const float* z, int z_stride,
  *   Every field means what the argument of that name means there (`normal_img` / `cam_dir` / `ref_flags` are read for Ref-NeRF only;
  *   `weights` is (N, n_fine) for MipNeRF and -- through this entry point alone -- (N, n_fine + 64) for Ref-NeRF; with two rounds u_strat and
  *   u_inv must be NULL).  With opacity, depth_q and fine_depths NULL the call IS that entry point: same checks, same launches, same bits,
- *   and nerf_amd_render_request_workspace_bytes equals its workspace query.
+ *   and nerf_amd_render_request_workspace_bytes equals its workspace query.  (Inside the library the four fill such a request themselves and
+ *   go this way; the Python package calls nerf_amd_render alone, and the four argument-list symbols are kept for C callers.)
  *   opacity (N), depth_q (N, n_quantiles) with quantiles[0 .. n_quantiles): nerf_amd_ray_depth_stats of the weights and depth row the fine
  *   pass composited (mul_norm; closed rows of n_fine + 1 depths on the MipNeRF routes, open rows of n_fine + 64 for Ref-NeRF; near, far of
  *   the request -- under disparity spacing near = 0, far = 1 followed by W^-1 like `depth`, so depth_q lives in the same [0, 1] s-scale).

@@ -930,15 +930,46 @@ const char* rounds_shape_error(int64_t N, int n_fine, int prop_pnum, int spacing
     if (prop_pnum < 3 || prop_pnum > 256) return "bad prop_pnum (3 <= prop_pnum <= 256: the second round's histogram)";
     return nullptr;
 }
+// request -> plan, the one place a plan is filled: which pipeline (ref, prop_pnum, spacing) and what is refused before it starts
+int plan_from_request(const nerf_amd_render_request* r, RenderPlan& p, bool sizing) {     // sizing: the workspace query, which needs no descriptor
+    if (!r) return fail(NERF_AMD_EINVAL, "NULL argument: request");
+    if (r->size < sizeof(nerf_amd_render_request)) return fail(NERF_AMD_EINVAL, "request->size is smaller than nerf_amd_render_request");
+    if (r->spacing != NERF_AMD_SPACING_LINEAR && r->spacing != NERF_AMD_SPACING_DISPARITY)
+        return fail(NERF_AMD_EINVAL, "unknown spacing (NERF_AMD_SPACING_LINEAR or NERF_AMD_SPACING_DISPARITY)");
+    const bool warped = r->spacing == NERF_AMD_SPACING_DISPARITY, rounds = !r->ref && r->prop_pnum != 0;
+    if (r->ref && (warped || r->prop_pnum)) return fail(NERF_AMD_EUNSUPPORTED, "the Ref-NeRF pipeline has neither disparity spacing nor a second proposal round");
+    if (rounds) {
+        if (const char* bad_shape = rounds_shape_error(r->N, r->n_fine, r->prop_pnum, r->spacing)) return fail(NERF_AMD_EINVAL, bad_shape);
+        if (r->u_strat || r->u_inv) return fail(NERF_AMD_EINVAL, "two proposal rounds draw their uniforms in the kernels: u_strat and u_inv must be NULL");
+    }
+    p = RenderPlan{r->packed_prop, r->packed_fine, r->precision, 0, r->rays, r->camera, r->ray_offset, warped ? nullptr : r->z_base, r->u_strat, r->u_inv, r->N, r->n_fine,
+                   rounds ? r->prop_pnum : 0, warped, r->ref != 0, r->near, r->far, 0.0f, 0.0f, r->white_bkg, r->rgb, r->depth, r->weights};
+    if (warped)
+        if (int e = check_spacing(r->spacing, r->near, r->far, &p.gn, &p.gf)) return e;
+    if (rounds && !sizing && r->N && !r->camera) return fail(NERF_AMD_EINVAL, "NULL argument: in-kernel uniforms need the descriptor (rng_seed, rng_ray_offset)");
+    if (p.ref) { p.ref_flags = r->ref_flags; p.cam_dir = r->cam_dir; p.normal_img = r->normal_img; }
+    if (int e = check_quantiles(r->quantiles, r->n_quantiles)) return e;
+    p.opacity = r->opacity; p.depth_q = r->depth_q; p.fine_depths = r->fine_depths; p.n_quantiles = r->n_quantiles;
+    for (int j = 0; j < r->n_quantiles; ++j) p.quantiles[j] = r->quantiles[j];
+    return NERF_AMD_OK;
+}
+// every render entry point ends here: nerf_amd_render directly, the four argument-list entry points with a request they fill themselves
+int render_request(const nerf_amd_render_request* r, void* workspace, void* stream) {
+    RenderPlan p{};
+    if (int e = plan_from_request(r, p, false)) return e;
+    return p.ref ? render_ref(p, workspace, S(stream)) : render_mip(p, workspace, S(stream));
+}
 }  // namespace
 
 size_t nerf_amd_render_workspace_bytes(int64_t N, int n_fine) { return render_ws_bytes(false, false, N, n_fine); }
 int nerf_amd_render_rays(const void* packed_prop, const void* packed_mip, int precision, const float* rays, const nerf_amd_samples* camera,
                          int64_t ray_offset, const float* z_base, const float* u_strat, const float* u_inv, int64_t N, int n_fine, float near, float far,
                          int white_bkg, float* rgb, float* depth, float* weights, void* workspace, void* stream) {
-    RenderPlan p{packed_prop, packed_mip, precision, 0, rays, camera, ray_offset, z_base, u_strat, u_inv, N, n_fine, 0, false, false, near, far, 0.0f, 0.0f,
-                 white_bkg, rgb, depth, weights};
-    return render_mip(p, workspace, S(stream));
+    nerf_amd_render_request r{};
+    r.size = sizeof r; r.packed_prop = packed_prop; r.packed_fine = packed_mip; r.precision = precision; r.rays = rays; r.camera = camera;
+    r.ray_offset = ray_offset; r.z_base = z_base; r.u_strat = u_strat; r.u_inv = u_inv; r.N = N; r.n_fine = n_fine; r.spacing = NERF_AMD_SPACING_LINEAR;
+    r.near = near; r.far = far; r.white_bkg = white_bkg; r.rgb = rgb; r.depth = depth; r.weights = weights;
+    return render_request(&r, workspace, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ disparity ray spacing
@@ -979,10 +1010,13 @@ size_t nerf_amd_render_warped_workspace_bytes(int64_t N, int n_fine) { return re
 int nerf_amd_render_rays_warped(const void* packed_prop, const void* packed_mip, int precision, const float* rays, const nerf_amd_samples* camera,
                                 int64_t ray_offset, const float* u_strat, const float* u_inv, int64_t N, int n_fine, int spacing, float near, float far,
                                 int white_bkg, float* rgb, float* depth, float* weights, void* workspace, void* stream) {
-    RenderPlan p{packed_prop, packed_mip, precision, 0, rays, camera, ray_offset, nullptr, u_strat, u_inv, N, n_fine, 0, true, false, near, far, 0.0f, 0.0f,
-                 white_bkg, rgb, depth, weights};
-    if (int e = check_spacing(spacing, near, far, &p.gn, &p.gf)) return e;
-    return render_mip(p, workspace, S(stream));
+    // (the request takes NERF_AMD_SPACING_LINEAR as the linear pipeline and words an unknown value differently: refused here, with check_spacing's text)
+    if (spacing != NERF_AMD_SPACING_DISPARITY) return fail(NERF_AMD_EINVAL, "unknown spacing (the warped entry points take NERF_AMD_SPACING_DISPARITY only)");
+    nerf_amd_render_request r{};
+    r.size = sizeof r; r.packed_prop = packed_prop; r.packed_fine = packed_mip; r.precision = precision; r.rays = rays; r.camera = camera;
+    r.ray_offset = ray_offset; r.u_strat = u_strat; r.u_inv = u_inv; r.N = N; r.n_fine = n_fine; r.spacing = spacing;
+    r.near = near; r.far = far; r.white_bkg = white_bkg; r.rgb = rgb; r.depth = depth; r.weights = weights;
+    return render_request(&r, workspace, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ two proposal rounds
@@ -992,60 +1026,35 @@ size_t nerf_amd_render_rounds_workspace_bytes(int64_t N, int n_fine, int prop_pn
 int nerf_amd_render_rays_rounds(const void* packed_prop, const void* packed_mip, int precision, const float* rays, const nerf_amd_samples* camera,
                                 int64_t ray_offset, const float* z_base, int64_t N, int n_fine, int prop_pnum, int spacing, float near, float far, int white_bkg,
                                 float* rgb, float* depth, float* weights, void* workspace, void* stream) {
+    // (first and here: to the request prop_pnum == 0 means one round)
     if (const char* bad_shape = rounds_shape_error(N, n_fine, prop_pnum, spacing)) return fail(NERF_AMD_EINVAL, bad_shape);
-    RenderPlan p{packed_prop, packed_mip, precision, 0, rays, camera, ray_offset, z_base, nullptr, nullptr, N, n_fine, prop_pnum,
-                 spacing == NERF_AMD_SPACING_DISPARITY, false, near, far, 0.0f, 0.0f, white_bkg, rgb, depth, weights};
-    if (p.warped)
-        if (int e = check_spacing(spacing, near, far, &p.gn, &p.gf)) return e;
-    if (N && !camera) return fail(NERF_AMD_EINVAL, "NULL argument: in-kernel uniforms need the descriptor (rng_seed, rng_ray_offset)");
-    return render_mip(p, workspace, S(stream));
+    nerf_amd_render_request r{};
+    r.size = sizeof r; r.packed_prop = packed_prop; r.packed_fine = packed_mip; r.precision = precision; r.rays = rays; r.camera = camera;
+    r.ray_offset = ray_offset; r.z_base = z_base; r.N = N; r.n_fine = n_fine; r.prop_pnum = prop_pnum; r.spacing = spacing;
+    r.near = near; r.far = far; r.white_bkg = white_bkg; r.rgb = rgb; r.depth = depth; r.weights = weights;
+    return render_request(&r, workspace, stream);
 }
 
 size_t nerf_amd_render_ref_workspace_bytes(int64_t N, int n_fine) { return render_ws_bytes(false, true, N, n_fine); }
 int nerf_amd_render_rays_ref(const void* packed_prop, const void* packed_ref, int precision, int ref_flags, const float* rays, const nerf_amd_samples* camera,
                              int64_t ray_offset, const float* z_base, const float* u_strat, const float* u_inv, int64_t N, int n_fine, float near, float far,
                              int white_bkg, const float* cam_dir, float* rgb, float* depth, float* normal_img, void* workspace, void* stream) {
-    RenderPlan p{packed_prop, packed_ref, precision, 0, rays, camera, ray_offset, z_base, u_strat, u_inv, N, n_fine, 0, false, true, near, far, 0.0f, 0.0f,
-                 white_bkg, rgb, depth, nullptr};
-    p.ref_flags = ref_flags; p.cam_dir = cam_dir; p.normal_img = normal_img;
-    return render_ref(p, workspace, S(stream));
+    nerf_amd_render_request r{};
+    r.size = sizeof r; r.packed_prop = packed_prop; r.packed_fine = packed_ref; r.precision = precision; r.ref = 1; r.ref_flags = ref_flags; r.rays = rays;
+    r.camera = camera; r.ray_offset = ray_offset; r.z_base = z_base; r.u_strat = u_strat; r.u_inv = u_inv; r.N = N; r.n_fine = n_fine;
+    r.spacing = NERF_AMD_SPACING_LINEAR; r.near = near; r.far = far; r.white_bkg = white_bkg; r.cam_dir = cam_dir; r.rgb = rgb; r.depth = depth;
+    r.normal_img = normal_img;
+    return render_request(&r, workspace, stream);
 }
 
 // ------------------------------------------------------------------------------------------------ one request for all four, with the optional outputs
-namespace {
-// request -> plan; what the four entry points refuse before they fill their plan is refused here in the same order
-int plan_from_request(const nerf_amd_render_request* r, RenderPlan& p, bool sizing) {     // sizing: the workspace query, which needs no descriptor
-    if (!r) return fail(NERF_AMD_EINVAL, "NULL argument: request");
-    if (r->size < sizeof(nerf_amd_render_request)) return fail(NERF_AMD_EINVAL, "request->size is smaller than nerf_amd_render_request");
-    if (r->spacing != NERF_AMD_SPACING_LINEAR && r->spacing != NERF_AMD_SPACING_DISPARITY)
-        return fail(NERF_AMD_EINVAL, "unknown spacing (NERF_AMD_SPACING_LINEAR or NERF_AMD_SPACING_DISPARITY)");
-    const bool warped = r->spacing == NERF_AMD_SPACING_DISPARITY, rounds = !r->ref && r->prop_pnum != 0;
-    if (r->ref && (warped || r->prop_pnum)) return fail(NERF_AMD_EUNSUPPORTED, "the Ref-NeRF pipeline has neither disparity spacing nor a second proposal round");
-    if (rounds) {
-        if (const char* bad_shape = rounds_shape_error(r->N, r->n_fine, r->prop_pnum, r->spacing)) return fail(NERF_AMD_EINVAL, bad_shape);
-        if (r->u_strat || r->u_inv) return fail(NERF_AMD_EINVAL, "two proposal rounds draw their uniforms in the kernels: u_strat and u_inv must be NULL");
-    }
-    p = RenderPlan{r->packed_prop, r->packed_fine, r->precision, 0, r->rays, r->camera, r->ray_offset, warped ? nullptr : r->z_base, r->u_strat, r->u_inv, r->N, r->n_fine,
-                   rounds ? r->prop_pnum : 0, warped, r->ref != 0, r->near, r->far, 0.0f, 0.0f, r->white_bkg, r->rgb, r->depth, r->weights};
-    if (warped)
-        if (int e = check_spacing(r->spacing, r->near, r->far, &p.gn, &p.gf)) return e;
-    if (rounds && !sizing && r->N && !r->camera) return fail(NERF_AMD_EINVAL, "NULL argument: in-kernel uniforms need the descriptor (rng_seed, rng_ray_offset)");
-    if (p.ref) { p.ref_flags = r->ref_flags; p.cam_dir = r->cam_dir; p.normal_img = r->normal_img; }
-    if (int e = check_quantiles(r->quantiles, r->n_quantiles)) return e;
-    p.opacity = r->opacity; p.depth_q = r->depth_q; p.fine_depths = r->fine_depths; p.n_quantiles = r->n_quantiles;
-    for (int j = 0; j < r->n_quantiles; ++j) p.quantiles[j] = r->quantiles[j];
-    return NERF_AMD_OK;
-}
-}  // namespace
 size_t nerf_amd_render_request_workspace_bytes(const nerf_amd_render_request* request) {
     RenderPlan p{};
     if (plan_from_request(request, p, true) || p.N < 0 || p.n_fine < 1) return 0;
     return RenderExtrasWs(p, nullptr).bytes;
 }
 int nerf_amd_render(const nerf_amd_render_request* request, void* workspace, void* stream) {
-    RenderPlan p{};
-    if (int e = plan_from_request(request, p, false)) return e;
-    return p.ref ? render_ref(p, workspace, S(stream)) : render_mip(p, workspace, S(stream));
+    return render_request(request, workspace, stream);
 }
 
 int nerf_amd_ray_depth_stats(const float* weights, const float* z, int z_stride, int closed, const float* dirs, int dirs_stride, int64_t N, int Sn, int mul_norm,

@@ -831,16 +831,6 @@ def _render_descriptor(camera: Optional[Samples], contract, ipe_radius, ipe_dir_
     return camera, keepalive
 
 
-def _render_buffers(need: int, workspace: Optional[torch.Tensor], dev, N: int, want_depth, third_shape):
-    """-> (workspace: the caller's if it holds `need` bytes, else a new one; rgb (N,3); depth (N,) | None; a third output of third_shape | None)"""
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    rgb = torch.empty((N, 3), dtype=torch.float32, device=dev)
-    depth = torch.empty((N,), dtype=torch.float32, device=dev) if want_depth else None
-    third = torch.empty(third_shape, dtype=torch.float32, device=dev) if third_shape is not None else None
-    return workspace, rgb, depth, third
-
-
 # ------------------------------------------------------------------------------------------------ depth quantiles and opacity
 def depth_quantiles(quantiles, who: str = "nerf_amd") -> tuple:
     """None / () -> (); else the quantiles as a tuple of floats, checked on the host: at most DEPTH_QUANTILES_MAX, each in (0, 1)."""
@@ -890,23 +880,28 @@ def ray_depth_stats(weights: torch.Tensor, z: torch.Tensor, dirs: Optional[torch
 
 
 def _render_request(packed_prop, packed_fine, precision, rays, camera, ray_offset, z_base, u_strat, u_inv, N, n_fine, near, far, white_bkg, dev, *,
-                    q, want_opacity, want_fine_depths, want_depth, want_weights, workspace, prop_pnum=0, spacing=_lib.SPACING_LINEAR, ref=False,
+                    q, want_opacity, want_fine_depths, want_depth, workspace, want_weights=False, prop_pnum=0, spacing=_lib.SPACING_LINEAR, ref=False,
                     ref_flags=0, cam_dir=None):
-    """One of the four render entry points through nerf_amd_render, with the outputs they have no argument for.
-    -> (rgb, depth | None, weights | None, normal_img | None, workspace, {"depth_q" (N,Q) | None, "opacity" (N,) | None, "fine_depths" (N,E) | None})"""
+    """The package's one whole-ray render call: nerf_amd_render, which picks the pipeline by `ref`, `prop_pnum` and `spacing`.
+    -> (rgb, depth | None, weights | None -- Ref-NeRF: normal_img | None --, workspace: the caller's if it holds the call's bytes, else a new
+    one), followed, when a quantile, the opacity or the fine depths are asked for, by {"depth_q" (N,Q) | None, "opacity" (N,) | None,
+    "fine_depths" (N,E) | None}; Ref-NeRF takes its weights output only then, as "weights" of that dict."""
     S = n_fine + (64 if ref else 0)
+    asked = bool(q) or want_opacity or want_fine_depths
+    if ref:
+        want_weights = asked
 
     def out(shape, want=True):
         return torch.empty(shape, dtype=torch.float32, device=dev) if want else None
     rgb, depth, w, normal_img = out((N, 3)), out((N,), want_depth), out((N, S), want_weights), out((N,), ref and cam_dir is not None)
     extras = {"depth_q": out((N, len(q)), bool(q)), "opacity": out((N,), want_opacity), "fine_depths": out((N, S if ref else S + 1), want_fine_depths)}
-    r = _lib.RenderRequest(packed_prop=packed_prop.data_ptr(), packed_fine=packed_fine.data_ptr(), precision=precision, ref=int(ref), ref_flags=int(ref_flags),
-                           white_bkg=int(white_bkg), ray_offset=int(ray_offset), N=N, n_fine=int(n_fine), prop_pnum=int(prop_pnum), spacing=spacing,
-                           near=float(near), far=float(far), n_quantiles=len(q))
+    r = _lib.RenderRequest(precision=precision, ref=int(ref), ref_flags=int(ref_flags), white_bkg=int(white_bkg), ray_offset=int(ray_offset), N=N, n_fine=int(n_fine),
+                           prop_pnum=int(prop_pnum), spacing=spacing, near=float(near), far=float(far), n_quantiles=len(q))
     if camera is not None:
         r.camera = C.pointer(camera)
-    for name, t in (("rays", rays), ("z_base", z_base), ("u_strat", u_strat), ("u_inv", u_inv), ("cam_dir", cam_dir), ("rgb", rgb), ("depth", depth),
-                    ("weights", w), ("normal_img", normal_img), ("opacity", extras["opacity"]), ("depth_q", extras["depth_q"]), ("fine_depths", extras["fine_depths"])):
+    for name, t in (("packed_prop", packed_prop), ("packed_fine", packed_fine), ("rays", rays), ("z_base", z_base), ("u_strat", u_strat), ("u_inv", u_inv),
+                    ("cam_dir", cam_dir), ("rgb", rgb), ("depth", depth), ("weights", w), ("normal_img", normal_img), ("opacity", extras["opacity"]),
+                    ("depth_q", extras["depth_q"]), ("fine_depths", extras["fine_depths"])):
         if t is not None:
             setattr(r, name, t.data_ptr())
     for j, v in enumerate(q):
@@ -915,7 +910,11 @@ def _render_request(packed_prop, packed_fine, precision, rays, camera, ray_offse
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(need, dtype=torch.uint8, device=dev)
     check(lib.nerf_amd_render(C.byref(r), _ptr(workspace), _stream()), "nerf_amd_render")
-    return rgb, depth, w, normal_img, workspace, extras
+    if not asked:
+        return rgb, depth, normal_img if ref else w, workspace
+    if ref:
+        extras["weights"] = w
+    return rgb, depth, normal_img if ref else w, workspace, extras
 
 
 def render_rays(packed_prop, packed_mip, precision, rays, z_base, u_strat, u_inv, n_fine, near, far, white_bkg,
@@ -929,25 +928,17 @@ def render_rays(packed_prop, packed_mip, precision, rays, z_base, u_strat, u_inv
     u_strat = u_inv = None with `seed`: every uniform is drawn inside the kernels (Philox4x32-10 keyed by `seed`, a pure function of
     (ray index + rng_ray_offset, sample)); pass `n_rays` (or rays) for the ray count.
     ``quantiles`` (up to 4 values in (0, 1)), ``want_opacity``, ``want_fine_depths`` (keyword-only; here and in render_rays_warped,
-    _rounds_stats and _ref): when any is set the call goes through nerf_amd_render -- the same launches, then ray_depth_stats of the composited
-    weights and depth row -- and a dict {"depth_q" (N,Q), "opacity" (N,), "fine_depths" (N,E)} (None where not asked for; Ref-NeRF also
-    "weights") follows the usual four results.  The mass is absolute: a ray that never accumulates q reports its far edge."""
+    _rounds and _ref): when any is set the same launches are followed by ray_depth_stats of the composited weights and depth row, and a
+    dict {"depth_q" (N,Q), "opacity" (N,), "fine_depths" (N,E)} (None where not asked for; Ref-NeRF also "weights") follows the usual four
+    results.  The mass is absolute: a ray that never accumulates q reports its far edge.  (All four render through nerf_amd_render.)"""
     q = depth_quantiles(quantiles, "nerf_amd.render_rays")
     u_strat, u_inv, seed, dev, N = _render_batch(rays, z_base, u_strat, u_inv, seed, n_rays)
     if ipe_radius is not None and rays is None:
         raise ValueError("nerf_amd: integrated PE needs an explicit ray table")
     camera, _keep = _render_descriptor(camera, contract, ipe_radius, ipe_dir_norm, seed, rng_ray_offset)
-    if q or want_opacity or want_fine_depths:
-        rgb, depth, w, _, workspace, extras = _render_request(packed_prop, packed_mip, _prop_prec(packed_prop, precision, packed_mip), rays, camera, ray_offset, z_base,
-                                                              u_strat, u_inv, N, n_fine, near, far, white_bkg, dev, q=q, want_opacity=want_opacity,
-                                                              want_fine_depths=want_fine_depths, want_depth=want_depth, want_weights=want_weights, workspace=workspace)
-        return rgb, depth, w, workspace, extras
-    workspace, rgb, depth, w = _render_buffers(lib.nerf_amd_render_workspace_bytes(N, n_fine), workspace, dev, N, want_depth, (N, n_fine) if want_weights else None)
-    check(lib.nerf_amd_render_rays(_ptr(packed_prop), _ptr(packed_mip), _prop_prec(packed_prop, precision, packed_mip), _ptr(rays),
-                                   C.byref(camera) if camera is not None else None, ray_offset, _ptr(z_base), _ptr(u_strat),
-                                   _ptr(u_inv), N, n_fine, float(near), float(far), int(white_bkg), _ptr(rgb), _ptr(depth),
-                                   _ptr(w), _ptr(workspace), _stream()), "nerf_amd_render_rays")
-    return rgb, depth, w, workspace
+    return _render_request(packed_prop, packed_mip, _prop_prec(packed_prop, precision, packed_mip), rays, camera, ray_offset, z_base, u_strat, u_inv, N, n_fine,
+                           near, far, white_bkg, dev, q=q, want_opacity=want_opacity, want_fine_depths=want_fine_depths, want_depth=want_depth,
+                           want_weights=want_weights, workspace=workspace)
 
 
 # ------------------------------------------------------------------------------------------------ disparity ray spacing (Mip-NeRF 360 s-space)
@@ -1027,21 +1018,14 @@ def render_rays_warped(packed_prop, packed_mip, precision, rays, u_strat, u_inv,
     resampling kernel's LDS rows, include/nerf_amd.h).  ``quantiles`` / ``want_opacity`` / ``want_fine_depths``: as in render_rays; the
     quantile depths are W^-1 of the metric quantile depths, in the same [0, 1] scale as ``depth``."""
     q = depth_quantiles(quantiles, "nerf_amd.render_rays_warped")
+    if _spacing_kind(spacing) != _lib.SPACING_DISPARITY:       # (to nerf_amd_render, linear spacing is the plain pipeline)
+        raise ValueError("nerf_amd.render_rays_warped: spacing must be 'disparity' (got %r): linear spacing is render_rays" % (spacing,))
     rays = _dev(rays, "rays")
     u_strat, u_inv, seed, dev, N = _render_batch(rays, None, u_strat, u_inv, seed, rays.shape[0])
     camera, _keep = _render_descriptor(None, contract, ipe_radius, ipe_dir_norm, seed, rng_ray_offset)
-    if q or want_opacity or want_fine_depths:
-        rgb, depth, w, _, workspace, extras = _render_request(packed_prop, packed_mip, _prop_prec(packed_prop, precision, packed_mip), rays, camera, 0, None, u_strat, u_inv,
-                                                              N, int(n_fine), near, far, white_bkg, dev, q=q, want_opacity=want_opacity, want_fine_depths=want_fine_depths,
-                                                              want_depth=want_depth, want_weights=want_weights, workspace=workspace, spacing=_spacing_kind(spacing))
-        return rgb, depth, w, workspace, extras
-    workspace, rgb, depth, w = _render_buffers(lib.nerf_amd_render_warped_workspace_bytes(N, n_fine), workspace, dev, N, want_depth,
-                                               (N, n_fine) if want_weights else None)
-    check(lib.nerf_amd_render_rays_warped(_ptr(packed_prop), _ptr(packed_mip), _prop_prec(packed_prop, precision, packed_mip), _ptr(rays),
-                                          C.byref(camera) if camera is not None else None, 0, _ptr(u_strat), _ptr(u_inv), N, int(n_fine), _spacing_kind(spacing),
-                                          float(near), float(far), int(white_bkg), _ptr(rgb), _ptr(depth), _ptr(w), _ptr(workspace), _stream()),
-          "nerf_amd_render_rays_warped")
-    return rgb, depth, w, workspace
+    return _render_request(packed_prop, packed_mip, _prop_prec(packed_prop, precision, packed_mip), rays, camera, 0, None, u_strat, u_inv, N, int(n_fine), near, far,
+                           white_bkg, dev, q=q, want_opacity=want_opacity, want_fine_depths=want_fine_depths, want_depth=want_depth, want_weights=want_weights,
+                           workspace=workspace, spacing=_lib.SPACING_DISPARITY)
 
 
 ROUNDS_PNUM_MIN, ROUNDS_PNUM_MAX = 3, 256      # prop_pnum of nerf_amd_render_rays_rounds (include/nerf_amd.h)
@@ -1049,49 +1033,24 @@ ROUNDS_PNUM_MIN, ROUNDS_PNUM_MAX = 3, 256      # prop_pnum of nerf_amd_render_ra
 
 def render_rays_rounds(packed_prop, packed_mip, precision, rays, z_base, n_fine, near, far, white_bkg, *, prop_pnum, seed, rng_ray_offset: int = 0,
                        spacing: str = "linear", contract: bool = False, ipe_radius: Optional[float] = None, ipe_dir_norm: Optional[torch.Tensor] = None,
-                       want_depth=True, want_weights=False, workspace: Optional[torch.Tensor] = None):
+                       want_depth=True, want_weights=False, workspace: Optional[torch.Tensor] = None, quantiles=None, want_opacity: bool = False,
+                       want_fine_depths: bool = False):
     """ops.render_rays / ops.render_rays_warped with Mip-NeRF 360's two proposal rounds (nerf_amd_render_rays_rounds): explicit rays (N,6),
     in-kernel Philox uniforms of ``seed`` only.  ``prop_pnum`` (3..256) sorted depths are resampled from the first histogram with columns
     [0, prop_pnum) of each ray's inverse-CDF stream, the proposal network is evaluated there, and the n_fine + 1 fine depths are drawn from
     that second histogram with columns [prop_pnum, prop_pnum + n_fine + 1).  ``z_base`` (64) is read under spacing="linear" only; under
     "disparity" ``depth`` is W^-1 of the expected metric depth.  -> (rgb, depth | None, weights | None, workspace)
-    (Depth quantiles, opacity, fine depths: render_rays_rounds_stats -- this signature is pinned as it stands.)"""
-    return _render_rays_rounds(packed_prop, packed_mip, precision, rays, z_base, n_fine, near, far, white_bkg, prop_pnum, seed, rng_ray_offset, spacing, contract,
-                               ipe_radius, ipe_dir_norm, want_depth, want_weights, workspace, (), False, False)
-
-
-def render_rays_rounds_stats(packed_prop, packed_mip, precision, rays, z_base, n_fine, near, far, white_bkg, *, prop_pnum, seed, rng_ray_offset: int = 0,
-                             spacing: str = "linear", contract: bool = False, ipe_radius: Optional[float] = None, ipe_dir_norm: Optional[torch.Tensor] = None,
-                             want_depth=True, want_weights=False, workspace: Optional[torch.Tensor] = None, quantiles=None, want_opacity: bool = False,
-                             want_fine_depths: bool = False):
-    """render_rays_rounds with the keyword-only ``quantiles`` / ``want_opacity`` / ``want_fine_depths`` of render_rays: when any is set the
-    call goes through nerf_amd_render and the dict {"depth_q", "opacity", "fine_depths"} follows the four results; else it IS
-    render_rays_rounds.  The mass is absolute: a ray that never accumulates q reports its far edge."""
-    return _render_rays_rounds(packed_prop, packed_mip, precision, rays, z_base, n_fine, near, far, white_bkg, prop_pnum, seed, rng_ray_offset, spacing, contract,
-                               ipe_radius, ipe_dir_norm, want_depth, want_weights, workspace, depth_quantiles(quantiles, "nerf_amd.render_rays_rounds_stats"),
-                               want_opacity, want_fine_depths)
-
-
-def _render_rays_rounds(packed_prop, packed_mip, precision, rays, z_base, n_fine, near, far, white_bkg, prop_pnum, seed, rng_ray_offset, spacing, contract, ipe_radius,
-                        ipe_dir_norm, want_depth, want_weights, workspace, q, want_opacity, want_fine_depths):
-    rays = _dev(rays, "rays")
-    N = rays.shape[0]
+    ``quantiles`` / ``want_opacity`` / ``want_fine_depths``: as in render_rays (the dict then follows the four results)."""
+    q = depth_quantiles(quantiles, "nerf_amd.render_rays_rounds")
     kind = _spacing_kind(spacing)
-    if kind == _lib.SPACING_LINEAR:
-        z_base = _dev(z_base, "z_base")
+    if not ROUNDS_PNUM_MIN <= int(prop_pnum) <= ROUNDS_PNUM_MAX:       # (to nerf_amd_render, prop_pnum = 0 is the one-round pipeline)
+        raise ValueError("nerf_amd.render_rays_rounds: prop_pnum must be %d..%d (got %r)" % (ROUNDS_PNUM_MIN, ROUNDS_PNUM_MAX, prop_pnum))
+    rays = _dev(rays, "rays")
+    z_base = _dev(z_base, "z_base") if kind == _lib.SPACING_LINEAR else None
     camera, _keep = _render_descriptor(None, contract, ipe_radius, ipe_dir_norm, seed, rng_ray_offset)
-    if q or want_opacity or want_fine_depths:
-        rgb, depth, w, _, workspace, extras = _render_request(packed_prop, packed_mip, _prop_prec(packed_prop, precision, packed_mip), rays, camera, 0,
-                                                              z_base if kind == _lib.SPACING_LINEAR else None, None, None, N, int(n_fine), near, far, white_bkg,
-                                                              rays.device, q=q, want_opacity=want_opacity, want_fine_depths=want_fine_depths, want_depth=want_depth,
-                                                              want_weights=want_weights, workspace=workspace, prop_pnum=int(prop_pnum), spacing=kind)
-        return rgb, depth, w, workspace, extras
-    workspace, rgb, depth, w = _render_buffers(lib.nerf_amd_render_rounds_workspace_bytes(N, int(n_fine), int(prop_pnum), kind), workspace, rays.device, N,
-                                               want_depth, (N, n_fine) if want_weights else None)
-    check(lib.nerf_amd_render_rays_rounds(_ptr(packed_prop), _ptr(packed_mip), _prop_prec(packed_prop, precision, packed_mip), _ptr(rays), C.byref(camera), 0,
-                                          _ptr(z_base) if kind == _lib.SPACING_LINEAR else None, N, int(n_fine), int(prop_pnum), kind, float(near), float(far),
-                                          int(white_bkg), _ptr(rgb), _ptr(depth), _ptr(w), _ptr(workspace), _stream()), "nerf_amd_render_rays_rounds")
-    return rgb, depth, w, workspace
+    return _render_request(packed_prop, packed_mip, _prop_prec(packed_prop, precision, packed_mip), rays, camera, 0, z_base, None, None, rays.shape[0], int(n_fine),
+                           near, far, white_bkg, rays.device, q=q, want_opacity=want_opacity, want_fine_depths=want_fine_depths, want_depth=want_depth,
+                           want_weights=want_weights, workspace=workspace, prop_pnum=int(prop_pnum), spacing=kind)
 
 
 def render_rays_ref(packed_prop, packed_ref, precision, rays, z_base, u_strat, u_inv, n_fine, near, far, white_bkg,
@@ -1108,20 +1067,9 @@ def render_rays_ref(packed_prop, packed_ref, precision, rays, z_base, u_strat, u
     # contract: Mip-NeRF 360 scene contraction of every sample position (the build's own definition); a caller's descriptor keeps its own flag
     camera, _keep = _render_descriptor(camera, True if contract else None, None, None, seed, rng_ray_offset)
     cam_dir = _dev(cam_dir, "cam_dir") if cam_dir is not None else None
-    if q or want_opacity or want_fine_depths:
-        rgb, depth, w, normal_img, workspace, extras = _render_request(packed_prop, packed_ref, _prop_prec(packed_prop, precision), rays, camera, ray_offset, z_base, u_strat,
-                                                                       u_inv, N, n_fine, near, far, white_bkg, dev, q=q, want_opacity=want_opacity,
-                                                                       want_fine_depths=want_fine_depths, want_depth=want_depth, want_weights=True, workspace=workspace,
-                                                                       ref=True, ref_flags=flags, cam_dir=cam_dir)
-        extras["weights"] = w
-        return rgb, depth, normal_img, workspace, extras
-    workspace, rgb, depth, normal_img = _render_buffers(lib.nerf_amd_render_ref_workspace_bytes(N, n_fine), workspace, dev, N, want_depth,
-                                                        (N,) if cam_dir is not None else None)
-    check(lib.nerf_amd_render_rays_ref(_ptr(packed_prop), _ptr(packed_ref), _prop_prec(packed_prop, precision), int(flags), _ptr(rays),
-                                       C.byref(camera) if camera is not None else None, ray_offset, _ptr(z_base), _ptr(u_strat),
-                                       _ptr(u_inv), N, n_fine, float(near), float(far), int(white_bkg), _ptr(cam_dir), _ptr(rgb),
-                                       _ptr(depth), _ptr(normal_img), _ptr(workspace), _stream()), "nerf_amd_render_rays_ref")
-    return rgb, depth, normal_img, workspace
+    return _render_request(packed_prop, packed_ref, _prop_prec(packed_prop, precision), rays, camera, ray_offset, z_base, u_strat, u_inv, N, n_fine, near, far,
+                           white_bkg, dev, q=q, want_opacity=want_opacity, want_fine_depths=want_fine_depths, want_depth=want_depth, workspace=workspace, ref=True,
+                           ref_flags=flags, cam_dir=cam_dir)
 
 
 # ------------------------------------------------------------------------------------------------ backward

@@ -292,14 +292,13 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
     warped = _check_spacing(spacing, near, far)
     route = _render_route(is_ref_model, generic, warped, prop_rounds, prop_pnum)
     cam_dir = render_pose[:, -2].contiguous() if render_normal else None
-    # depth quantiles / opacity: the fused entry points take them as keywords (and then return their dict last); without them the calls are
-    # exactly what they were
-    stat_kw = dict(quantiles=quantiles, want_opacity=render_opacity) if want_stats else dict()
+    # depth quantiles / opacity: every route takes them as keywords and returns its dict last when either is set
+    stat_kw = dict(quantiles=quantiles, want_opacity=render_opacity)
     if route == "calls":
         out = _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, bool(render_depth),
                                     is_ref_model=is_ref_model, cam_dir=cam_dir, seed=seed, ray_offset=off, contract=contract,
                                     ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, spacing=spacing, prop_rounds=prop_rounds,
-                                    prop_pnum=prop_pnum, ipe_cov=ipe_cov, **(dict(depth_quantiles=quantiles, render_opacity=render_opacity) if want_stats else dict()))
+                                    prop_pnum=prop_pnum, ipe_cov=ipe_cov, depth_quantiles=quantiles, render_opacity=render_opacity)
         rgb, depth, normal_px = out[:3]
     elif route == "ref":
         # procedures.py:71-74: coarse and fine depths are merged and sorted (a merge of two ascending sets), the last one dropped,
@@ -314,8 +313,7 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
         common = dict(want_depth=bool(render_depth), contract=ops.ipe_contract(contract, ipe, ipe_cov), ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, seed=seed, rng_ray_offset=off,
                       **stat_kw)
         if route == "rounds":
-            out = (ops.render_rays_rounds_stats if want_stats else ops.render_rays_rounds)(*packed, z_base, sample_num, near, far, white_bkg, prop_pnum=prop_pnum,
-                                                                                           spacing=spacing, **common)
+            out = ops.render_rays_rounds(*packed, z_base, sample_num, near, far, white_bkg, prop_pnum=prop_pnum, spacing=spacing, **common)
         elif route == "warped":
             out = ops.render_rays_warped(*packed, u_strat, u_inv, sample_num, near, far, white_bkg, spacing=spacing, **common)
         else:

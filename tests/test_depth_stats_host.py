@@ -187,7 +187,15 @@ def test_python_argument_errors_are_value_errors_on_the_host():
         with pytest.raises(ValueError):
             ops.render_rays_warped(None, None, 0, None, None, None, 8, 2.0, 6.0, True, quantiles=bad)
         with pytest.raises(ValueError):
-            ops.render_rays_rounds_stats(None, None, 0, None, None, 8, 2.0, 6.0, True, prop_pnum=16, seed=0, quantiles=bad)
+            ops.render_rays_rounds(None, None, 0, None, None, 8, 2.0, 6.0, True, prop_pnum=16, seed=0, quantiles=bad)
+    # what the argument-list C entry points refused by being the one called: the request reads prop_pnum = 0 as one round and linear spacing
+    # as the plain pipeline, so the package refuses both itself, before any tensor is touched, with and without the optional outputs
+    for kw in (dict(), dict(quantiles=(0.5,))):
+        for p in (0, 2, 257):
+            with pytest.raises(ValueError, match="prop_pnum"):
+                ops.render_rays_rounds(None, None, 0, None, None, 8, 2.0, 6.0, True, prop_pnum=p, seed=0, **kw)
+        with pytest.raises(ValueError, match="spacing"):
+            ops.render_rays_warped(None, None, 0, None, None, None, 8, 2.0, 6.0, True, spacing="linear", **kw)
     for bad_w, bad_z in ((torch.zeros(3, 8), torch.zeros(3, 10)), (torch.zeros(3, 8), torch.zeros(4, 9)), (torch.zeros(3, 0), torch.zeros(3, 1)),
                          (torch.zeros(8), torch.zeros(9))):
         with pytest.raises(ValueError):
@@ -196,9 +204,8 @@ def test_python_argument_errors_are_value_errors_on_the_host():
         ops.ray_depth_stats(w, z, torch.zeros(3, 4))
     assert ops.depth_quantiles(None) == () and ops.depth_quantiles(0.5) == (0.5,) and ops.depth_quantiles([0.25, 0.5]) == (0.25, 0.5)
     # appended, keyword-only, off by default
-    # (render_rays_rounds keeps the signature test_two_round_render_host pins; its twin render_rays_rounds_stats adds the three keywords)
-    assert list(inspect.signature(ops.render_rays_rounds_stats).parameters)[:-3] == list(inspect.signature(ops.render_rays_rounds).parameters)
-    for fn in (ops.render_rays, ops.render_rays_warped, ops.render_rays_rounds_stats, ops.render_rays_ref):
+    assert not hasattr(ops, "render_rays_rounds_stats")                  # (one function per pipeline: the twin is gone)
+    for fn in (ops.render_rays, ops.render_rays_warped, ops.render_rays_rounds, ops.render_rays_ref):
         p = inspect.signature(fn).parameters
         assert [(n, p[n].default, p[n].kind) for n in list(p)[-3:]] == [("quantiles", None, inspect.Parameter.KEYWORD_ONLY),
                                                                         ("want_opacity", False, inspect.Parameter.KEYWORD_ONLY),

@@ -120,10 +120,11 @@ def _rays(n=200):
 ENTRIES = ("plain", "warped", "rounds", "ref")
 
 
-def _entry(entry, precision, nf, want_weights=True, **kw):
-    """one of the four ops.render_rays* on 200 rays with in-kernel uniforms -> its result tuple"""
+def _entry(entry, precision, nf, want_weights=True, ops=None, **kw):
+    """one of the four ops.render_rays* (or of another module's: abi_render) on 200 rays with in-kernel uniforms -> its result tuple"""
     import nerf_amd
-    from nerf_amd import ops
+    if ops is None:
+        from nerf_amd import ops
     nerf_amd.set_precision(precision)
     prec = ops.BF16 if precision == "bf16" else ops.F32
     prop, mip, ref = _nets()
@@ -137,36 +138,20 @@ def _entry(entry, precision, nf, want_weights=True, **kw):
             return ops.render_rays_warped(prop.packed(prec), mip.packed(prec), prec, rays, None, None, nf, near, far, True, want_weights=want_weights, seed=SEED,
                                           contract=contract, **kw)
         if entry == "rounds":
-            return (ops.render_rays_rounds_stats if kw else ops.render_rays_rounds)(prop.packed(prec), mip.packed(prec), prec, rays, z_base, nf, near, far, True,
-                                                                                    prop_pnum=16, seed=SEED, want_weights=want_weights, **kw)
+            return ops.render_rays_rounds(prop.packed(prec), mip.packed(prec), prec, rays, z_base, nf, near, far, True, prop_pnum=16, seed=SEED,
+                                          want_weights=want_weights, **kw)
         return ops.render_rays_ref(prop.packed(prec), ref.packed(prec), prec, rays, z_base, None, None, nf, near, far, True, flags=ref.kernel_flags, seed=SEED, **kw)
-
-
-def _request_without_new_outputs(entry, precision, nf):
-    """the same call through nerf_amd_render with opacity, depth_q and fine_depths NULL -> (rgb, depth, weights | None)"""
-    from nerf_amd import _lib, ops
-    prec = ops.BF16 if precision == "bf16" else ops.F32
-    prop, mip, ref = _nets()
-    rays = _rays()
-    near, far, contract = SPACINGS["disparity" if entry == "warped" else "linear"]
-    camera, _keep = ops._render_descriptor(None, contract if entry == "warped" else (None if entry == "ref" else False), None, None, SEED, 0)
-    fine = ref.packed(prec) if entry == "ref" else mip.packed(prec)
-    pp = ops._prop_prec(prop.packed(prec), prec) if entry == "ref" else ops._prop_prec(prop.packed(prec), prec, fine)
-    with torch.no_grad():
-        out = ops._render_request(prop.packed(prec), fine, pp, rays, camera, 0, None if entry == "warped" else torch.linspace(near, far, 64).cuda(), None, None,
-                                  rays.shape[0], nf, near, far, True, rays.device, q=(), want_opacity=False, want_fine_depths=False, want_depth=True,
-                                  want_weights=entry != "ref", workspace=None, prop_pnum=16 if entry == "rounds" else 0,
-                                  spacing=_lib.SPACING_DISPARITY if entry == "warped" else _lib.SPACING_LINEAR, ref=entry == "ref",
-                                  ref_flags=ref.kernel_flags if entry == "ref" else 0)
-    assert out[5] == {"depth_q": None, "opacity": None, "fine_depths": None}
-    return out[0], out[1], out[2]
 
 
 @pytest.mark.parametrize("nf", [32, 128])
 @pytest.mark.parametrize("entry", ENTRIES)
 def test_request_without_new_outputs_is_the_old_entry_point_bit_for_bit(entry, nf):
-    old = _entry(entry, "fp32", nf)
-    new = _request_without_new_outputs(entry, "fp32", nf)
+    """the argument-list C entry point, called directly (abi_render), against ops.*, which goes through nerf_amd_render with opacity, depth_q and
+    fine_depths NULL"""
+    import abi_render
+    old = _entry(entry, "fp32", nf, ops=abi_render)
+    new = _entry(entry, "fp32", nf)
+    assert len(old) == 4 and len(new) == 4
     assert bool(torch.isfinite(old[0]).all()) and float(old[0].std()) > 1e-4
     assert torch.equal(new[0], old[0]) and torch.equal(new[1], old[1])
     if entry != "ref":

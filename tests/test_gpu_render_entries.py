@@ -51,9 +51,13 @@ def test_the_fixture_holds_exactly_the_cases(parent):
     assert sum(c["weights"] for c in G29.CASES) == 4 and {c["entry"] for c in G29.CASES} == {"plain", "warped", "rounds", "ref"}
 
 
-@pytest.mark.parametrize("c", G29.CASES, ids=G29.key)
-def test_entry_points_reproduce_the_parent_bit_for_bit(ops, parent, nets, c):
-    got = G29.outputs(ops, nets, c)
+@pytest.mark.parametrize("via,c", [(via, c) for via in ("request", "abi") for c in G29.CASES],
+                         ids=[G29.key(c) + suffix for suffix in ("", "-abi") for c in G29.CASES])
+def test_entry_points_reproduce_the_parent_bit_for_bit(ops, parent, nets, c, via):
+    """via "request": the package, which renders through nerf_amd_render (ids as before: the case alone); "abi": the argument-list C entry
+    points, called directly (abi_render)."""
+    import abi_render
+    got = G29.outputs(ops if via == "request" else abi_render, nets, c)
     name = G29.key(c)
     for what, a in got.items():
         if a is None:

@@ -115,7 +115,8 @@ def test_op_signature():
     assert all(p[n].kind is inspect.Parameter.POSITIONAL_OR_KEYWORD for n in list(p)[:9])
     keyword_only = dict(prop_pnum=inspect.Parameter.empty, seed=inspect.Parameter.empty, rng_ray_offset=0, spacing="linear", contract=False, ipe_radius=None,
                         ipe_dir_norm=None, want_depth=True, want_weights=False, workspace=None)
-    assert list(p)[9:] == list(keyword_only)
+    assert list(p)[9:] == list(keyword_only) + ["quantiles", "want_opacity", "want_fine_depths"]       # the optional outputs, as in its three siblings
+    keyword_only.update(quantiles=None, want_opacity=False, want_fine_depths=False)
     for name, default in keyword_only.items():
         assert p[name].kind is inspect.Parameter.KEYWORD_ONLY and p[name].default == default, name
     assert (ops.ROUNDS_PNUM_MIN, ops.ROUNDS_PNUM_MAX) == (3, 256)
