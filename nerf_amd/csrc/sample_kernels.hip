@@ -165,6 +165,18 @@ __global__ __launch_bounds__(256) void dirs_norm_final_kernel(const double* __re
 // ---------------------------------------------------------------------------------------- row 1
 struct Cam { int H, W; float fx, fy; float pose[12]; };
 
+// The ray (o, d) through camera-plane coordinates (cx, cy) of a (3,4) pose, and the point o + z d on a ray: the one definition of each for
+// every kernel of this file that forms them (same expression grouping, so the kernels agree bit for bit where they overlap).
+DEVINL void camera_ray(const float* pose, float cx, float cy, float* r) {
+    r[0] = pose[3]; r[1] = pose[7]; r[2] = pose[11];
+    r[3] = (cx * pose[0] + cy * pose[1]) + (-1.0f) * pose[2];
+    r[4] = (cx * pose[4] + cy * pose[5]) + (-1.0f) * pose[6];
+    r[5] = (cx * pose[8] + cy * pose[9]) + (-1.0f) * pose[10];
+}
+DEVINL void point_on_ray(const float* r, float z, float* p) {
+    p[0] = r[0] + r[3] * z; p[1] = r[1] + r[4] * z; p[2] = r[2] + r[5] * z;
+}
+
 __global__ void raygen_kernel(Cam cam, int64_t first, int64_t count, float* __restrict__ out) {
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
         const int64_t n = first + i;
@@ -172,11 +184,7 @@ __global__ void raygen_kernel(Cam cam, int64_t first, int64_t count, float* __re
         const int row = (int)(n / cam.W), col = (int)(n - (int64_t)row * cam.W);
         const float cx = (((float)col - (float)cam.W * 0.5f) + 0.5f) / cam.fx;
         const float cy = (((float)cam.H * 0.5f - (float)row) + 0.5f) / cam.fy;
-        float* r = rays + n * 6;
-        r[0] = cam.pose[3]; r[1] = cam.pose[7]; r[2] = cam.pose[11];
-        r[3] = (cx * cam.pose[0] + cy * cam.pose[1]) + (-1.0f) * cam.pose[2];
-        r[4] = (cx * cam.pose[4] + cy * cam.pose[5]) + (-1.0f) * cam.pose[6];
-        r[5] = (cx * cam.pose[8] + cy * cam.pose[9]) + (-1.0f) * cam.pose[10];
+        camera_ray(cam.pose, cx, cy, rays + n * 6);
     }
 }
 
@@ -185,11 +193,7 @@ __global__ void pixel_rays_kernel(Cam cam, const int64_t* __restrict__ coords, i
     for (int64_t n = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; n < N; n += (int64_t)gridDim.x * blockDim.x) {
         const float cx = ((float)coords[n * 2] + 0.5f) / cam.fx;
         const float cy = ((float)coords[n * 2 + 1] + 0.5f) / cam.fy;
-        float* r = rays + n * 6;
-        r[0] = cam.pose[3]; r[1] = cam.pose[7]; r[2] = cam.pose[11];
-        r[3] = (cx * cam.pose[0] + cy * cam.pose[1]) + (-1.0f) * cam.pose[2];
-        r[4] = (cx * cam.pose[4] + cy * cam.pose[5]) + (-1.0f) * cam.pose[6];
-        r[5] = (cx * cam.pose[8] + cy * cam.pose[9]) + (-1.0f) * cam.pose[10];
+        camera_ray(cam.pose, cx, cy, rays + n * 6);
     }
 }
 
@@ -203,10 +207,7 @@ __global__ void stratified_points_kernel(const float* __restrict__ rays, const f
         const int s = (int)(i - n * S);
         const float zv = z_base[s] + u[i] * jitter;
         z_out[i] = zv;
-        if (pts) {
-            const float* r = rays + n * 6;
-            pts[i * 3] = r[0] + r[3] * zv; pts[i * 3 + 1] = r[1] + r[4] * zv; pts[i * 3 + 2] = r[2] + r[5] * zv;
-        }
+        if (pts) point_on_ray(rays + n * 6, zv, pts + i * 3);
     }
 }
 
@@ -227,10 +228,7 @@ DEVINL uint64_t sampler_index_word(int64_t n, uint64_t seed) {
 DEVINL void sampler_ray(const float* pose, float fx, float fy, float ix, float iy, float* q, float* __restrict__ ray_out) {
     const float cx = (ix + 0.5f) / fx;                                                   // utils.py:78-81
     const float cy = (iy + 0.5f) / fy;
-    q[0] = pose[3]; q[1] = pose[7]; q[2] = pose[11];
-    q[3] = (cx * pose[0] + cy * pose[1]) + (-1.0f) * pose[2];
-    q[4] = (cx * pose[4] + cy * pose[5]) + (-1.0f) * pose[6];
-    q[5] = (cx * pose[8] + cy * pose[9]) + (-1.0f) * pose[10];
+    camera_ray(pose, cx, cy, q);
 #pragma unroll
     for (int k = 0; k < 6; ++k) ray_out[k] = q[k];
 }
@@ -247,9 +245,7 @@ DEVINL void sampler_samples(int64_t n0, int64_t N, int C, uint64_t seed, float n
         const float u = u01_from_bits(w == 0 ? r.w[0] : (w == 1 ? r.w[1] : (w == 2 ? r.w[2] : r.w[3])));
         const float z = (near + (float)sidx * res) + u * res;                        // linspace(near, far - res, C)[s] + u res
         lengths[n * C + sidx] = z;
-        const float* q = ray_s[rl];
-        float* o = pts + (n * C + sidx) * 3;
-        o[0] = q[0] + q[3] * z; o[1] = q[1] + q[4] * z; o[2] = q[2] + q[5] * z;
+        point_on_ray(ray_s[rl], z, pts + (n * C + sidx) * 3);
     }
 }
 // `pose_dev` / `seed_dev` (both optional): the camera pose and the seed read from DEVICE memory instead of the launch arguments, so that
@@ -354,14 +350,18 @@ __global__ __launch_bounds__(256) void sigma_to_weights_kernel(const float* __re
 }
 
 // ---------------------------------------------------------------------------------------- row 6
+// element s of maxBlurFilter (mip_methods.py:61-66) over the row w[0 .. S-1]; the row's ends see themselves
+DEVINL float max_blur_at(const float* w, int s, int S, float alpha) {
+    const float c = w[s];
+    const float front = (s == 0) ? c : fmaxf(w[s - 1], c);
+    const float rear = (s == S - 1) ? c : fmaxf(c, w[s + 1]);
+    return 0.5f * (front + rear) + alpha;
+}
 __global__ void max_blur_kernel(const float* __restrict__ w, int64_t N, int S, float alpha, float* __restrict__ out) {
     const int64_t total = N * S;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const int s = (int)(i % S);
-        const float c = w[i];
-        const float front = (s == 0) ? c : fmaxf(w[i - 1], c);
-        const float rear = (s == S - 1) ? c : fmaxf(c, w[i + 1]);
-        out[i] = 0.5f * (front + rear) + alpha;
+        out[i] = max_blur_at(w + (i - s), s, S, alpha);
     }
 }
 
@@ -555,9 +555,48 @@ DEVINL void wave_inverse_sample(const float* pw, const float* bins, int nw, floa
     }
 }
 
-// LDS floats per wave: pw[C] bins[C] cdf[C] samp[K] bel[K] sortbuf; resample_kernel appends zl[C] wraw[C]
-static inline __host__ __device__ size_t inv_lds_floats(int C, int K) { return (size_t)3 * C + 2 * K + SORT_LDS_FLOATS; }
-static inline __host__ __device__ size_t rs_lds_floats(int C, int K) { return inv_lds_floats(C, K) + 2 * C; }
+// The per-wave LDS rows of the five inverse-sampling kernels, described ONCE (all rows are 4-byte words; bel and sortbuf hold ints):
+//   pw[C] bins[C] cdf[C] samp[K] bel[K] sortbuf[SORT_LDS_FLOATS] | zl[C] wraw[C] | tail
+// inverse_sample_kernel ends at zl; the fused kernels add zl (metric depths) and wraw (unblurred weights) and put their own rows at `tail`.
+// P = float*: the kernels' pointers from a wave's base; P = size_t: the same walk from 0 counts the floats, so the launch sizes
+// (nk::sk_*_lds_bytes) cannot disagree with the carve.
+template <class P> struct ResampleRowsAt { P pw, bins, cdf, samp, bel, sortbuf, zl, wraw, tail; };
+typedef ResampleRowsAt<float*> ResampleRows;
+template <class P> static inline __host__ __device__ ResampleRowsAt<P> resample_rows(P base, int C, int K) {
+    ResampleRowsAt<P> r;
+    r.pw = base; r.bins = r.pw + C; r.cdf = r.bins + C; r.samp = r.cdf + C; r.bel = r.samp + K; r.sortbuf = r.bel + K;
+    r.zl = r.sortbuf + SORT_LDS_FLOATS; r.wraw = r.zl + C; r.tail = r.wraw + C;
+    return r;
+}
+static inline __host__ __device__ size_t inv_lds_floats(int C, int K) { return resample_rows<size_t>(0, C, K).zl; }
+static inline __host__ __device__ size_t rs_lds_floats(int C, int K) { return resample_rows<size_t>(0, C, K).tail; }
+// tails: warped_resample_kernel sf[K] uu[K]; resample_window_kernel uu[K] | sf[K] (WARPED)
+static inline __host__ __device__ size_t warped_lds_floats(int C, int K) { return rs_lds_floats(C, K) + (size_t)2 * K; }
+static inline __host__ __device__ size_t rsw_lds_floats(int C, int K, bool warped) { return rs_lds_floats(C, K) + (size_t)(warped ? 2 : 1) * K; }
+// the rows of this wave in a workgroup whose waves hold `wave_floats` each
+DEVINL ResampleRows wave_resample_rows(size_t wave_floats, int C, int K) {
+    return resample_rows(reinterpret_cast<float*>(smem) + wave_in_block() * wave_floats, C, K);
+}
+template <class UF>
+DEVINL void wave_inverse_sample(const ResampleRows& r, int nw, UF&& uf, int K, int sort, float* __restrict__ z_out, int64_t* __restrict__ below_out,
+                                int64_t* __restrict__ above_out) {
+    wave_inverse_sample(r.pw, r.bins, nw, r.cdf, r.samp, reinterpret_cast<int*>(r.bel), reinterpret_cast<int*>(r.sortbuf), uf, K, sort, z_out, below_out,
+                        above_out);
+}
+
+// The stages the fused resampling kernels share (one wavefront, rows in LDS; the callers put lds_wave_sync around them).
+// max-blur of the raw weights (max_blur_kernel's element) -> w_prop (optional, global) and its slice [1, C-2] = the pdf row pw
+DEVINL void wave_blur_pdf(const float* wraw, int C, float alpha, float* pw, float* w_prop) {
+    for (int j = lane_id(); j < C; j += 64) {
+        const float wb = max_blur_at(wraw, j, C, alpha);
+        if (j >= 1 && j <= C - 2) pw[j - 1] = wb;                              // pdf over weights[1:-1]
+        if (w_prop) w_prop[j] = wb;
+    }
+}
+// bins[j] = the mid-point of x[j] and x[j + 1], j < C - 1
+DEVINL void wave_midpoints(const float* x, int C, float* bins) {
+    for (int j = lane_id(); j < C - 1; j += 64) bins[j] = 0.5f * (x[j + 1] + x[j]);
+}
 
 // mode 0: inverseSample(weights (N,C), depths (N,C)) -> bins = mid-points, pdf = weights[1:-1]   (utils.py:34-44)
 // mode 1: sample_pdf(bins (N,C), weights (N,C-1))                                               (utils.py:108-133)
@@ -565,10 +604,8 @@ __global__ __launch_bounds__(256) void inverse_sample_kernel(const float* __rest
                                                             const float* __restrict__ u, int64_t N, int C, int K, int sort,
                                                             int mode, float* __restrict__ z_out, int64_t* __restrict__ below,
                                                             int64_t* __restrict__ above) {
-    float* base = reinterpret_cast<float*>(smem) + wave_in_block() * inv_lds_floats(C, K);
-    float* pw = base; float* bins = pw + C; float* cdf = bins + C; float* samp = cdf + C;
-    int* bel = reinterpret_cast<int*>(samp + K);
-    int* sortbuf = bel + K;
+    const ResampleRows r = wave_resample_rows(inv_lds_floats(C, K), C, K);
+    float* const pw = r.pw; float* const bins = r.bins;
     const int lane = lane_id();
     const int nw = mode == 0 ? C - 2 : C - 1;
     const int wstride = mode == 0 ? C : C - 1;
@@ -576,20 +613,22 @@ __global__ __launch_bounds__(256) void inverse_sample_kernel(const float* __rest
         lds_wave_sync();
         if (mode == 0) {
             for (int j = lane; j < nw; j += 64) pw[j] = w[n * wstride + 1 + j];
-            for (int j = lane; j < nw + 1; j += 64) bins[j] = 0.5f * (z[n * C + j + 1] + z[n * C + j]);
+            wave_midpoints(z + n * C, C, bins);
         } else {
             for (int j = lane; j < nw; j += 64) pw[j] = w[n * wstride + j];
             for (int j = lane; j < nw + 1; j += 64) bins[j] = z[n * C + j];
         }
         lds_wave_sync();
         const float* un = u + n * K;
-        wave_inverse_sample(pw, bins, nw, cdf, samp, bel, sortbuf, [&](int, int k) { return un[k]; }, K, sort, z_out + n * K,
-                            below ? below + n * K : nullptr, above ? above + n * K : nullptr);
+        wave_inverse_sample(r, nw, [&](int, int k) { return un[k]; }, K, sort, z_out + n * K, below ? below + n * K : nullptr,
+                            above ? above + n * K : nullptr);
     }
 }
 
 // ------------------------------------------------------------------------------------------------
-// Fused proposal resampling: density -> weights -> max-blur -> inverse sampling (procedures.py:68-70).
+// Fused proposal resampling: density -> weights -> max-blur -> inverse sampling (procedures.py:68-70), i.e. wave_sigma_to_weights,
+// wave_blur_pdf, wave_midpoints, wave_inverse_sample on the rows of resample_rows -- the stage functions of all four fused kernels
+// (this one, warped_resample_kernel, resample_window_kernel<false / true>), which differ in where a ray's inputs and uniforms come from.
 // ------------------------------------------------------------------------------------------------
 struct ResampleArgs {
     const float* density; const float* z; const float* z_base; const float* u_strat; float z_jitter;
@@ -603,12 +642,8 @@ struct ResampleArgs {
 #endif
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RS_BLOCKS_PER_CU, RS_BLOCKS_PER_CU))) void resample_kernel(ResampleArgs a) {
     const int C = a.C, K = a.K;
-    float* base = reinterpret_cast<float*>(smem) + wave_in_block() * rs_lds_floats(C, K);
-    float* pw = base; float* bins = pw + C; float* cdf = bins + C; float* samp = cdf + C;
-    int* bel = reinterpret_cast<int*>(samp + K);
-    int* sortbuf = bel + K;
-    float* zl = reinterpret_cast<float*>(sortbuf + SORT_LDS_FLOATS);
-    float* wraw = zl + C;
+    const ResampleRows rows = wave_resample_rows(rs_lds_floats(C, K), C, K);
+    float* const zl = rows.zl; float* const wraw = rows.wraw;
     const int lane = lane_id();
     // All global inputs of a ray (direction, depths or their uniforms, densities, the K inverse-CDF uniforms) are loaded ONE RAY
     // AHEAD into registers: the ray's own phases then never wait for HBM (three exposed round trips per ray before).
@@ -673,19 +708,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(RS_BLOCKS_P
                               [=](int s) { return zl[s] * nrm; },
                               [=](int s, float wv, float) { wraw[s] = wv; });
         lds_wave_sync();
-        for (int j = lane; j < C; j += 64) {                                   // max-blur (mip_methods.py:61-66)
-            const float c = wraw[j];
-            const float front = (j == 0) ? c : fmaxf(wraw[j - 1], c);
-            const float rear = (j == C - 1) ? c : fmaxf(c, wraw[j + 1]);
-            const float wb = 0.5f * (front + rear) + a.alpha;
-            if (j >= 1 && j <= C - 2) pw[j - 1] = wb;                          // pdf over weights[1:-1]
-            if (a.w_prop) a.w_prop[n * C + j] = wb;
-        }
-        for (int j = lane; j < C - 1; j += 64) bins[j] = 0.5f * (zl[j + 1] + zl[j]);   // mid-points of the RAW depths
+        wave_blur_pdf(wraw, C, a.alpha, rows.pw, a.w_prop ? a.w_prop + n * C : nullptr);
+        wave_midpoints(zl, C, rows.bins);                                      // mid-points of the RAW depths
         lds_wave_sync();
         const float* un = a.u_inv ? a.u_inv + n * K : nullptr;
         const uint64_t seed = a.rng_seed; const int64_t nn = n + a.rng_ray_offset;
-        wave_inverse_sample(pw, bins, C - 2, cdf, samp, bel, sortbuf,
+        wave_inverse_sample(rows, C - 2,
                             [=](int i, int k) {
                                 if (fits) return i == 0 ? cu0 : (i == 1 ? cu1 : cu2);
                                 if (un) return un[k];
@@ -714,22 +742,19 @@ DEVINL float warp_z_to_s(float z, const WarpConsts& c) {
     return (1.0f / zb - c.gn) / (c.gf - c.gn);
 }
 
-// elementwise s -> z = W(s) (inverse: z -> s) over (N,S), optionally pts (N,S,3) = o + z d with the arithmetic of stratified_points_kernel
+// elementwise s -> z = W(s) (inverse: z -> s) over (N,S), optionally pts (N,S,3) = o + z d (point_on_ray, as in stratified_points_kernel)
 __global__ void warp_depths_kernel(const float* __restrict__ in, const float* __restrict__ rays, int64_t N, int S, int inverse, WarpConsts c,
                                    float* __restrict__ out, float* __restrict__ pts) {
     const int64_t total = N * S;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
         const float zv = inverse ? warp_z_to_s(in[i], c) : warp_s_to_z(in[i], c);
         out[i] = zv;
-        if (pts) {
-            const float* r = rays + (i / S) * 6;
-            pts[i * 3] = r[0] + r[3] * zv; pts[i * 3 + 1] = r[1] + r[4] * zv; pts[i * 3 + 2] = r[2] + r[5] * zv;
-        }
+        if (pts) point_on_ray(rays + (i / S) * 6, zv, pts + i * 3);
     }
 }
 
 // the coarse draw in s: s_j = (float)j r + u r with r = fp32(1/C) -- sampler_samples' expression at near = 0, res = 1/C -- then
-// z = W(s) and pts = o + z d.  u: explicit (N,C), or word 0 of the 'RS' Philox block of global ray n + ray_offset (philox_u_strat).
+// z = W(s) and pts = o + z d (point_on_ray).  u: explicit (N,C), or word 0 of the 'RS' Philox block of global ray n + ray_offset (philox_u_strat).
 __global__ void warped_stratified_kernel(const float* __restrict__ rays, const float* __restrict__ u, int64_t N, int C, float res, uint64_t seed,
                                          int64_t ray_offset, WarpConsts c, float* __restrict__ s_out, float* __restrict__ z_out,
                                          float* __restrict__ pts) {
@@ -742,34 +767,34 @@ __global__ void warped_stratified_kernel(const float* __restrict__ rays, const f
         const float zv = warp_s_to_z(sv, c);
         s_out[i] = sv;
         z_out[i] = zv;
-        if (pts) {
-            const float* r = rays + n * 6;
-            pts[i * 3] = r[0] + r[3] * zv; pts[i * 3 + 1] = r[1] + r[4] * zv; pts[i * 3 + 2] = r[2] + r[5] * zv;
-        }
+        if (pts) point_on_ray(rays + n * 6, zv, pts + i * 3);
+    }
+}
+
+// the tail of the two warped fused kernels: the sorted s_fine row sf[K] (LDS) -> s_fine (optional) and z_fine = W(s_fine)
+DEVINL void wave_unwarp_samples(const float* sf, int K, const WarpConsts& c, float* s_fine, float* z_fine) {
+    for (int k = lane_id(); k < K; k += 64) {
+        const float sv = sf[k];
+        if (s_fine) s_fine[k] = sv;
+        z_fine[k] = warp_s_to_z(sv, c);
     }
 }
 
 // The fused per-ray step between the two MLP kernels under disparity spacing: weights from the METRIC depths W(s_c) |d|, max-blur,
-// inverse sampling over the mid-points of s_c (wave_inverse_sample fed other bin coordinates: its arithmetic is shared with
-// resample_kernel and inverse_sample_kernel), then z_fine = W(s_fine).  One wavefront per ray; a kernel of its own so that
-// resample_kernel's code, register budget and occupancy stay exactly as they are.
+// inverse sampling over the mid-points of s_c, then z_fine = W(s_fine).  One wavefront per ray.  Its stages are resample_kernel's:
+// wave_sigma_to_weights, wave_blur_pdf, wave_midpoints (of s_c instead of z) and wave_inverse_sample on the rows of resample_rows; its
+// tail, wave_unwarp_samples, is the windowed warped kernel's.  A kernel of its own so that resample_kernel's register budget and occupancy
+// stay as they are.
 struct WarpedResampleArgs {
     const float* density; const float* s_c; const float* dirs; int dirs_stride; const float* u_inv; int64_t N; int C; int K; int softplus;
     float alpha; WarpConsts c; float* z_fine; float* s_fine; int64_t* below; float* w_prop; uint64_t rng_seed; int64_t rng_ray_offset;
 };
-// LDS floats per wave: the rows of inverse_sample_kernel | zl[C] wraw[C] | sf[K] uu[K]
-static inline __host__ __device__ size_t warped_lds_floats(int C, int K) { return inv_lds_floats(C, K) + (size_t)2 * C + (size_t)2 * K; }
 
 __global__ __launch_bounds__(256) void warped_resample_kernel(WarpedResampleArgs a) {
     const int C = a.C, K = a.K;
-    float* base = reinterpret_cast<float*>(smem) + wave_in_block() * warped_lds_floats(C, K);
-    float* pw = base; float* bins = pw + C; float* cdf = bins + C; float* samp = cdf + C;
-    int* bel = reinterpret_cast<int*>(samp + K);
-    int* sortbuf = bel + K;
-    float* zl = reinterpret_cast<float*>(sortbuf + SORT_LDS_FLOATS);
-    float* wraw = zl + C;
-    float* sf = wraw + C;
-    float* uu = sf + K;
+    const ResampleRows rows = wave_resample_rows(warped_lds_floats(C, K), C, K);
+    float* const zl = rows.zl; float* const wraw = rows.wraw;
+    float* const sf = rows.tail; float* const uu = sf + K;
     const int lane = lane_id();
     const WarpConsts c = a.c;
     for (int64_t n = blockIdx.x * (int64_t)WAVES_PER_BLOCK + wave_in_block(); n < a.N; n += (int64_t)gridDim.x * WAVES_PER_BLOCK) {
@@ -788,24 +813,12 @@ __global__ __launch_bounds__(256) void warped_resample_kernel(WarpedResampleArgs
                               [=](int s) { return zl[s] * nrm; },
                               [=](int s, float wv, float) { wraw[s] = wv; });
         lds_wave_sync();
-        for (int j = lane; j < C; j += 64) {                                   // max-blur (mip_methods.py:61-66)
-            const float cw = wraw[j];
-            const float front = (j == 0) ? cw : fmaxf(wraw[j - 1], cw);
-            const float rear = (j == C - 1) ? cw : fmaxf(cw, wraw[j + 1]);
-            const float wb = 0.5f * (front + rear) + a.alpha;
-            if (j >= 1 && j <= C - 2) pw[j - 1] = wb;                          // pdf over weights[1:-1]
-            if (a.w_prop) a.w_prop[n * C + j] = wb;
-        }
-        for (int j = lane; j < C - 1; j += 64) bins[j] = 0.5f * (sc[j + 1] + sc[j]);   // mid-points of s_c
+        wave_blur_pdf(wraw, C, a.alpha, rows.pw, a.w_prop ? a.w_prop + n * C : nullptr);
+        wave_midpoints(sc, C, rows.bins);                                      // mid-points of s_c
         lds_wave_sync();
-        wave_inverse_sample(pw, bins, C - 2, cdf, samp, bel, sortbuf, [=](int, int k) { return uu[k]; }, K, 1, sf,
-                            a.below ? a.below + n * K : nullptr, nullptr);
+        wave_inverse_sample(rows, C - 2, [=](int, int k) { return uu[k]; }, K, 1, sf, a.below ? a.below + n * K : nullptr, nullptr);
         lds_wave_sync();
-        for (int k = lane; k < K; k += 64) {
-            const float sv = sf[k];
-            if (a.s_fine) a.s_fine[n * K + k] = sv;
-            a.z_fine[n * K + k] = warp_s_to_z(sv, c);
-        }
+        wave_unwarp_samples(sf, K, c, a.s_fine ? a.s_fine + n * K : nullptr, a.z_fine + n * K);
     }
 }
 
@@ -831,30 +844,24 @@ DEVINL void wave_window_uniforms(float* uu, uint64_t seed, int64_t nn, int u_col
 }
 
 // resample_kernel (WARPED = false: x = metric depths z) and warped_resample_kernel (WARPED = true: x = s, weights from W(s) |d|, bins in s,
-// z_fine = W(s_fine)) behind the window: the same device functions for weights, max-blur and inverse sampling in the same order, so a
-// round-two call equals the single-stage call given the same columns as a tensor.  resample_kernel binds lane j to ONE Philox block, which
-// holds only at u_col0 = 0; here a lane's samples come from other blocks, so the uniforms go through an LDS row and only the ray's global
-// loads -- direction, coordinates, densities -- stay one ray ahead in registers (C <= 128).  Kernels of their own: the one-round kernels'
-// code, register budget and occupancy stay exactly as they are.
+// z_fine = W(s_fine)) behind the window: wave_sigma_to_weights, wave_blur_pdf's loop (a copy, for the measured reason given at it),
+// wave_midpoints and wave_inverse_sample (and, WARPED, wave_unwarp_samples) in the one-round kernels' order, so a round-two call equals
+// the single-stage call given the same columns as a tensor.  resample_kernel binds lane j to ONE Philox block, which holds only at
+// u_col0 = 0; here a lane's samples come from other blocks, so the uniforms go through an LDS row and only the ray's global loads --
+// direction, coordinates, densities -- stay one ray ahead in registers (C <= 128).  Kernels of their own: the one-round kernels'
+// register budget and occupancy stay as they are.
 struct ResampleWindowArgs {
     const float* density; const float* x; const float* dirs; int dirs_stride; int64_t N; int C; int K; int u_col0; float alpha; WarpConsts c;
     float* z_fine; float* s_fine; uint64_t rng_seed; int64_t rng_ray_offset;
 };
-// LDS floats per wave: the rows of resample_kernel | uu[K] | sf[K] (WARPED)
-static inline __host__ __device__ size_t rsw_lds_floats(int C, int K, bool warped) { return rs_lds_floats(C, K) + (size_t)(warped ? 2 : 1) * K; }
 
 template <bool WARPED>
 __global__ __launch_bounds__(256) void resample_window_kernel(ResampleWindowArgs a) {
     const int C = a.C, K = a.K;
-    float* base = reinterpret_cast<float*>(smem) + wave_in_block() * rsw_lds_floats(C, K, WARPED);
-    float* pw = base; float* bins = pw + C; float* cdf = bins + C; float* samp = cdf + C;
-    int* bel = reinterpret_cast<int*>(samp + K);
-    int* sortbuf = bel + K;
-    float* zl = reinterpret_cast<float*>(sortbuf + SORT_LDS_FLOATS);
-    float* wraw = zl + C;
-    float* uu = wraw + C;
-    float* sf = uu + K;                                                          // (WARPED only)
-    float* xl = WARPED ? cdf : zl;                                               // the bin coordinates: s parks in the cdf row, free until the inverse sampling writes it
+    const ResampleRows rows = wave_resample_rows(rsw_lds_floats(C, K, WARPED), C, K);
+    float* const zl = rows.zl; float* const wraw = rows.wraw;
+    float* const uu = rows.tail; float* const sf = uu + K;                       // (sf: WARPED only)
+    float* const xl = WARPED ? rows.cdf : zl;                                    // the bin coordinates: s parks in the cdf row, free until the inverse sampling writes it
     const int lane = lane_id();
     const WarpConsts c = a.c;
     struct RayIn { float dx, dy, dz, x0, x1, dens0, dens1; };                    // scalars only: indexed members end up in scratch
@@ -900,23 +907,21 @@ __global__ __launch_bounds__(256) void resample_window_kernel(ResampleWindowArgs
                               [=](int s) { return zl[s] * nrm; },
                               [=](int s, float wv, float) { wraw[s] = wv; });
         lds_wave_sync();
-        for (int j = lane; j < C; j += 64) {                                     // max-blur (mip_methods.py:61-66)
+        // wave_blur_pdf's loop without w_prop, kept as a copy: through the call this kernel takes 2 more VGPRs and, per 640 000 rays,
+        // 1194.5 us against 1177.0 us (<false>) and 1334.9 us against 1314.1 us (<true>), outside the spread of 12.0 / 7.0 us
+        for (int j = lane; j < C; j += 64) {
             const float cw = wraw[j];
             const float front = (j == 0) ? cw : fmaxf(wraw[j - 1], cw);
             const float rear = (j == C - 1) ? cw : fmaxf(cw, wraw[j + 1]);
-            if (j >= 1 && j <= C - 2) pw[j - 1] = 0.5f * (front + rear) + a.alpha;   // pdf over weights[1:-1]
+            if (j >= 1 && j <= C - 2) rows.pw[j - 1] = 0.5f * (front + rear) + a.alpha;   // pdf over weights[1:-1]
         }
-        for (int j = lane; j < C - 1; j += 64) bins[j] = 0.5f * (xl[j + 1] + xl[j]);   // mid-points of the coordinates
+        wave_midpoints(xl, C, rows.bins);                                        // mid-points of the coordinates
         lds_wave_sync();
         float* out = a.z_fine + n * K;
-        wave_inverse_sample(pw, bins, C - 2, cdf, samp, bel, sortbuf, [=](int, int k) { return uu[k]; }, K, 1, WARPED ? sf : out, nullptr, nullptr);
+        wave_inverse_sample(rows, C - 2, [=](int, int k) { return uu[k]; }, K, 1, WARPED ? sf : out, nullptr, nullptr);
         if (WARPED) {
             lds_wave_sync();
-            for (int k = lane; k < K; k += 64) {
-                const float sv = sf[k];
-                if (a.s_fine) a.s_fine[n * K + k] = sv;
-                out[k] = warp_s_to_z(sv, c);
-            }
+            wave_unwarp_samples(sf, K, c, a.s_fine ? a.s_fine + n * K : nullptr, out);
         }
         cur = nxt;
     }
@@ -1503,7 +1508,8 @@ __global__ __launch_bounds__(256) void relu_mask_bias_kernel(uint32_t* __restric
 // how ties are ordered, so z_out equals torch.sort(cat(a, b))[0][:, :-1] bit for bit.  The stratified depths are only ascending
 // while the jitter (far - near) / n_fine does not exceed the spacing of the 64 bins, i.e. for n_fine >= 63: a wave that finds one
 // of its inputs out of order first sorts it in LDS (stable rank sort, O(n^2 / 64) per lane -- the rare path).
-DEVINL void wave_sort_if_needed(float* v, float* tmp, int n, int lane) {
+// (idx / itmp, both or neither: a row of source indices that moves with the values -- merge_sorted_order_kernel's)
+DEVINL void wave_sort_if_needed(float* v, float* tmp, int n, int lane, int* idx = nullptr, int* itmp = nullptr) {
     int bad = 0;
     for (int i = lane; i + 1 < n; i += 64) bad |= (v[i] > v[i + 1]) ? 1 : 0;
     if (!__any(bad)) return;
@@ -1512,10 +1518,28 @@ DEVINL void wave_sort_if_needed(float* v, float* tmp, int n, int lane) {
         int r = 0;
         for (int k = 0; k < n; ++k) { const float y = v[k]; r += (y < x || (y == x && k < i)) ? 1 : 0; }
         tmp[r] = x;
+        if (idx) itmp[r] = idx[i];
     }
     lds_wave_sync();
-    for (int i = lane; i < n; i += 64) v[i] = tmp[i];
+    for (int i = lane; i < n; i += 64) { v[i] = tmp[i]; if (idx) idx[i] = itmp[i]; }
     lds_wave_sync();
+}
+// The rank searches of the merge (and of the interlevel loss): binary searches over an ascending row of n floats.
+DEVINL int count_le(const float* a, int n, float v) {                                        // #{k < n : a_k <= v}
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] <= v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+DEVINL int count_lt(const float* a, int n, float v) {                                        // #{k < n : a_k < v}
+    int lo = 0, hi = n;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (a[mid] < v) lo = mid + 1; else hi = mid;
+    }
+    return lo;
 }
 template <class T> static inline __host__ __device__ T merge_lds_floats(T K, T C, bool order) { return (order ? 4 : 2) * (K + C); }   // per wave: la[K] lb[C] tmp[K + C] (order: + indices)
 __global__ __launch_bounds__(256) void merge_sorted_kernel(const float* __restrict__ a, const float* __restrict__ b, int64_t N, int K, int C,
@@ -1535,15 +1559,13 @@ __global__ __launch_bounds__(256) void merge_sorted_kernel(const float* __restri
         float* o = out + n * T;
         for (int i = lane; i < K; i += 64) {
             const float v = la[i];
-            int lo = 0, hi = C;                                 // #(b < v)
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (lb[mid] < v) lo = mid + 1; else hi = mid; }
-            if (i + lo < T) o[i + lo] = v;
+            const int p = i + count_lt(lb, C, v);               // #(b < v)
+            if (p < T) o[p] = v;
         }
         for (int j = lane; j < C; j += 64) {
             const float v = lb[j];
-            int lo = 0, hi = K;                                 // #(a <= v)
-            while (lo < hi) { const int mid = (lo + hi) >> 1; if (la[mid] <= v) lo = mid + 1; else hi = mid; }
-            if (j + lo < T) o[j + lo] = v;
+            const int p = j + count_le(la, K, v);               // #(a <= v)
+            if (p < T) o[p] = v;
         }
     }
 }
@@ -1551,20 +1573,8 @@ __global__ __launch_bounds__(256) void merge_sorted_kernel(const float* __restri
 // The same merge with its sort order, for the training path (train.py:176: coarseFineMerge(..., below_idxs) -> all_inds for getBounds,
 // sort_inds for RefNeRF.coarse_grad_select).  order (N, K + C) = the STABLE argsort of cat(a, b) -- fine index i before coarse index
 // K + j among equal depths, which is what the device radix sort behind torch.sort produces --, all_inds = gather(cat(f_inds, 0..C-1), order).
-DEVINL void wave_sort_idx_if_needed(float* v, int* idx, float* tmp, int* itmp, int n, int lane) {
-    int bad = 0;
-    for (int i = lane; i + 1 < n; i += 64) bad |= (v[i] > v[i + 1]) ? 1 : 0;
-    if (!__any(bad)) return;
-    for (int i = lane; i < n; i += 64) {
-        const float x = v[i];
-        int r = 0;
-        for (int k = 0; k < n; ++k) { const float y = v[k]; r += (y < x || (y == x && k < i)) ? 1 : 0; }
-        tmp[r] = x; itmp[r] = idx[i];
-    }
-    lds_wave_sync();
-    for (int i = lane; i < n; i += 64) { v[i] = tmp[i]; idx[i] = itmp[i]; }
-    lds_wave_sync();
-}
+// The two rank searches are count_lt / count_le written out: through the calls this kernel measured 1346.6 us against 1339.2 us per
+// 640 000 rays (K = 129, C = 64), outside the spread of 4.7 us, and 0.5 to 0.9 % slower in every run; the sort is the shared one.
 __global__ __launch_bounds__(256) void merge_sorted_order_kernel(const float* __restrict__ a, const float* __restrict__ b, const int64_t* __restrict__ f_inds,
                                                                  int64_t N, int K, int C, float* __restrict__ out, int64_t* __restrict__ order,
                                                                  int64_t* __restrict__ all_inds) {
@@ -1581,8 +1591,8 @@ __global__ __launch_bounds__(256) void merge_sorted_order_kernel(const float* __
         for (int i = lane; i < K; i += 64) { la[i] = a[n * K + i]; ia[i] = i; }
         for (int j = lane; j < C; j += 64) { lb[j] = b[n * C + j]; ib[j] = K + j; }
         lds_wave_sync();
-        wave_sort_idx_if_needed(la, ia, tmp, itmp, K, lane);
-        wave_sort_idx_if_needed(lb, ib, tmp, itmp, C, lane);
+        wave_sort_if_needed(la, tmp, K, lane, ia, itmp);
+        wave_sort_if_needed(lb, tmp, C, lane, ib, itmp);
         float* o = out + n * T;
         int64_t* ord = order + n * (K + C);
         int64_t* ai = all_inds ? all_inds + n * (K + C) : nullptr;
@@ -1639,6 +1649,30 @@ __global__ __launch_bounds__(256) void coarse_grad_select_kernel(const float* __
 // One streaming pass + a fixed-order two-stage sum (block partials, then one block) -- deterministic -- instead of the reference's
 // five element-wise torch launches per loss; the backward is one pass too (a product rule per element).
 constexpr int LOSS_BLOCKS = 256;
+// The losses' fixed-order fp64 block sum: every wave's wave_sum_d into `red` (LDS, one slot per wave and value), then THREAD 0 adds the
+// slots in wave order, ((0 + 1) + 2) + 3 -- its result is the sum, every other thread's is left as it was.  A caller whose `red` aliases
+// rows that are still being read puts a __syncthreads() in front.
+DEVINL double block_sum_d(double acc, double* red, int waves = WAVES_PER_BLOCK) {
+    acc = wave_sum_d(acc);
+    if (lane_id() == 0) red[wave_in_block()] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        acc = red[0];
+        for (int k = 1; k < waves; ++k) acc += red[k];
+    }
+    return acc;
+}
+// the same for two values at once (slots interleaved), four waves
+DEVINL void block_sum2_d(double& p, double& q, double* red) {
+    p = wave_sum_d(p);
+    q = wave_sum_d(q);
+    if (lane_id() == 0) { red[2 * wave_in_block()] = p; red[2 * wave_in_block() + 1] = q; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        p = ((red[0] + red[2]) + red[4]) + red[6];
+        q = ((red[1] + red[3]) + red[5]) + red[7];
+    }
+}
 DEVINL float dot_loss_term(float x, int mode) { return mode == 0 ? 1.0f - x : (x > 0.0f ? x : 0.0f); }
 __global__ __launch_bounds__(256) void weighted_dot_loss_kernel(const float* __restrict__ w, const float* __restrict__ a, const float* __restrict__ b, int64_t M,
                                                                 int mode, float* __restrict__ partial) {
@@ -1647,20 +1681,14 @@ __global__ __launch_bounds__(256) void weighted_dot_loss_kernel(const float* __r
         const float x = (a[3 * i] * b[3 * i] + a[3 * i + 1] * b[3 * i + 1]) + a[3 * i + 2] * b[3 * i + 2];
         acc += (double)(w[i] * dot_loss_term(x, mode));
     }
-    acc = wave_sum_d(acc);
-    double* red = reinterpret_cast<double*>(smem);
-    if (lane_id() == 0) red[wave_in_block()] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) reinterpret_cast<double*>(partial)[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    acc = block_sum_d(acc, reinterpret_cast<double*>(smem));
+    if (threadIdx.x == 0) reinterpret_cast<double*>(partial)[blockIdx.x] = acc;
 }
 __global__ __launch_bounds__(256) void weighted_dot_loss_final_kernel(const float* __restrict__ partial, int n, float scale, float* __restrict__ out) {
     double acc = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) acc += reinterpret_cast<const double*>(partial)[i];
-    acc = wave_sum_d(acc);
-    double* red = reinterpret_cast<double*>(smem);
-    if (lane_id() == 0) red[wave_in_block()] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) out[0] = (float)((((red[0] + red[1]) + red[2]) + red[3]) * (double)scale);
+    acc = block_sum_d(acc, reinterpret_cast<double*>(smem));
+    if (threadIdx.x == 0) out[0] = (float)(acc * (double)scale);
 }
 __global__ void weighted_dot_loss_backward_kernel(const float* __restrict__ g, const float* __restrict__ w, const float* __restrict__ a, const float* __restrict__ b,
                                                   int64_t M, int mode, float scale, float* __restrict__ d_w, float* __restrict__ d_a, float* __restrict__ d_b) {
@@ -1749,31 +1777,19 @@ __global__ __launch_bounds__(256) void distortion_loss_kernel(const float* __res
             }
         }
     }
-    accP = wave_sum_d(accP);
-    accQ = wave_sum_d(accQ);
     __syncthreads();                                                                         // (the rows' LDS becomes the block's reduction slots)
-    double* red = reinterpret_cast<double*>(smem);
-    if (lane == 0) { red[2 * wave_in_block()] = accP; red[2 * wave_in_block() + 1] = accQ; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        partial[2 * blockIdx.x] = ((red[0] + red[2]) + red[4]) + red[6];
-        partial[2 * blockIdx.x + 1] = ((red[1] + red[3]) + red[5]) + red[7];
-    }
+    block_sum2_d(accP, accQ, reinterpret_cast<double*>(smem));
+    if (threadIdx.x == 0) { partial[2 * blockIdx.x] = accP; partial[2 * blockIdx.x + 1] = accQ; }
 }
 __global__ __launch_bounds__(256) void distortion_loss_final_kernel(const double* __restrict__ partial, int n, int64_t N, int M, int mode, float scale,
                                                                     float* __restrict__ out) {
     double p = 0.0, q = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) { p += partial[2 * i]; q += partial[2 * i + 1]; }
-    p = wave_sum_d(p);
-    q = wave_sum_d(q);
-    double* red = reinterpret_cast<double*>(smem);
-    if (lane_id() == 0) { red[2 * wave_in_block()] = p; red[2 * wave_in_block() + 1] = q; }
-    __syncthreads();
+    block_sum2_d(p, q, reinterpret_cast<double*>(smem));
     if (threadIdx.x == 0) {
         double cP, cQ;
         dist_coeffs(mode, N, M, cP, cQ);
-        const double P = ((red[0] + red[2]) + red[4]) + red[6], Q = ((red[1] + red[3]) + red[5]) + red[7];
-        out[0] = (float)((P * cP + Q * cQ) * (double)scale);
+        out[0] = (float)((p * cP + q * cQ) * (double)scale);
     }
 }
 
@@ -1932,22 +1948,6 @@ DEVINL IlRows il_rows(int M, int K, bool bwd) {
     r.te = r.tf + (M + 1);
     return r;
 }
-DEVINL int il_count_le(const float* a, int n, float v) {                                     // #{k < n : a_k <= v}, a ascending
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] <= v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
-DEVINL int il_count_lt(const float* a, int n, float v) {                                     // #{k < n : a_k < v}
-    int lo = 0, hi = n;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (a[mid] < v) lo = mid + 1; else hi = mid;
-    }
-    return lo;
-}
 // the wave's rows of ray n: edges as they are, c by a wave scan per 64 columns with the running total carried over (a fixed order)
 DEVINL void il_stage(const float* __restrict__ t, const float* __restrict__ w_prop, const float* __restrict__ t_prop, int64_t n, int M, int K, int Kp,
                      const IlRows& r) {
@@ -1967,7 +1967,7 @@ DEVINL void il_stage(const float* __restrict__ t, const float* __restrict__ w_pr
     }
 }
 DEVINL double il_bound(const IlRows& r, int K, int i) {
-    const int cl = il_count_le(r.te, K + 1, r.tf[i]), ch = il_count_le(r.te, K + 1, r.tf[i + 1]);
+    const int cl = count_le(r.te, K + 1, r.tf[i]), ch = count_le(r.te, K + 1, r.tf[i + 1]);
     return r.c[ch < K ? ch : K] - r.c[cl > 0 ? cl - 1 : 0];                                  // c[hi(t_i+1)] - c[lo(t_i)]
 }
 
@@ -1989,25 +1989,15 @@ __global__ __launch_bounds__(256) void interlevel_loss_kernel(const float* __res
             if (bounds_out) bounds_out[n * M + i] = (float)b;
         }
     }
-    acc = wave_sum_d(acc);
     __syncthreads();                                                                         // (the rows' LDS becomes the block's reduction slots)
-    double* red = reinterpret_cast<double*>(smem);
-    if (lane == 0) red[wave_in_block()] = acc;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = red[0];
-        for (int k = 1; k < waves; ++k) s += red[k];
-        partial[blockIdx.x] = s;
-    }
+    acc = block_sum_d(acc, reinterpret_cast<double*>(smem), waves);
+    if (threadIdx.x == 0) partial[blockIdx.x] = acc;
 }
 __global__ __launch_bounds__(256) void interlevel_loss_final_kernel(const double* __restrict__ partial, int n, float scale, float* __restrict__ out) {
     double p = 0.0;
     for (int i = threadIdx.x; i < n; i += 256) p += partial[i];
-    p = wave_sum_d(p);
-    double* red = reinterpret_cast<double*>(smem);
-    if (lane_id() == 0) red[wave_in_block()] = p;
-    __syncthreads();
-    if (threadIdx.x == 0) out[0] = (float)((((red[0] + red[1]) + red[2]) + red[3]) * (double)scale);
+    p = block_sum_d(p, reinterpret_cast<double*>(smem));
+    if (threadIdx.x == 0) out[0] = (float)(p * (double)scale);
 }
 __global__ __launch_bounds__(256) void interlevel_loss_backward_kernel(const float* __restrict__ w, const float* __restrict__ t,
                                                                        const float* __restrict__ w_prop, const float* __restrict__ t_prop, int64_t N,
@@ -2036,8 +2026,8 @@ __global__ __launch_bounds__(256) void interlevel_loss_backward_kernel(const flo
         }
         lds_wave_sync();
         for (int j = lane; j < K; j += 64) {                                                 // the fine intervals over proposal interval j: [i0, i1)
-            const int i1 = il_count_lt(r.tf, M, r.te[j + 1]);                                //   t_i < e_j+1
-            const int i0 = il_count_lt(r.tf + 1, M, r.te[j]);                                //   t_i+1 >= e_j
+            const int i1 = count_lt(r.tf, M, r.te[j + 1]);                                   //   t_i < e_j+1
+            const int i0 = count_lt(r.tf + 1, M, r.te[j]);                                   //   t_i+1 >= e_j
             d_w_prop[n * K + j] = (float)(i1 > i0 ? gs * (r.F[i1] - r.F[i0]) : 0.0);
         }
     }
