@@ -1378,10 +1378,21 @@ int bwd_grid(int64_t n_tiles) {
     const int n_cu = nerf_host::cu_count();
     return (int)(n_tiles < n_cu ? n_tiles : n_cu);
 }
+// One launch of a persistent tile kernel over M samples: the tile of policy P, one workgroup per tile up to the CU count, the dynamic
+// LDS opted in.  Every dgrad chain of the three translation units below goes through here.
+template <class P, class K, class... Args>
+int launch_tiles(K kernel, size_t lds, int64_t M, hipStream_t st, Args... args) {
+    constexpr int TS = P::NW * P::NT * 32;
+    const int64_t n_tiles = (M + TS - 1) / TS;
+    if (n_tiles == 0) return 0;
+    if (int e = nerf_host::allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds)) return e;
+    hipLaunchKernelGGL(kernel, dim3(bwd_grid(n_tiles)), dim3(P::NW * 64), lds, st, args...);
+    return (int)hipGetLastError();
+}
 
-// The file is compiled as two translation units (Makefile: -DBWD_TU=1 / 2; 0 = everything in one): 2 holds the fused chains of
+// The file is compiled as three translation units (Makefile: -DBWD_TU=1 / 2 / 3; 0 = everything in one): 2 holds the fused chains of
 // Ref-NeRF's backward and of the density gradient -- whose straight-line ten-layer bodies do not go through hipcc's
-// -amdgpu-mfma-vgpr-form pass -- behind bwd_launch_chain, 1 everything else.
+// -amdgpu-mfma-vgpr-form pass -- behind bwd_launch_chain, 3 the directional chain of Ref-NeRF alone, 1 everything else.
 #ifndef BWD_TU
 #define BWD_TU 0
 #endif
@@ -1390,22 +1401,9 @@ int bwd_grid(int64_t n_tiles) {
 // compiles with 65 spilled registers (91 in round 3's activation-mask form with the flag).
 }  // namespace
 #if BWD_TU == 3 || BWD_TU == 0
-namespace {
-template <class P>
-int launch_dir_chain_t(const char* stream, int64_t M, const char* masks, size_t ms, char* dlt, size_t ls, float* rows, hipStream_t st) {
-    constexpr int TS = P::NW * P::NT * 32;
-    const int64_t n_tiles = (M + TS - 1) / TS;
-    if (n_tiles == 0) return 0;
-    const size_t lds = bwd_lds_total<P>();
-    if (int e = nerf_host::allow_dynamic_lds(reinterpret_cast<const void*>(ref_chain9_kernel<P, false>), lds)) return e;
-    hipLaunchKernelGGL((ref_chain9_kernel<P, false>), dim3(bwd_grid(n_tiles)), dim3(P::NW * 64), lds, st, stream, M, masks, (unsigned long long)ms, dlt,
-                       (unsigned long long)ls, rows);
-    return (int)hipGetLastError();
-}
-}  // namespace
 int nk::bwd_launch_dir_chain(int precision, const char* stream, int64_t M, const char* masks, size_t ms, char* dlt, size_t ls, float* rows, hipStream_t st) {
-    if (precision == NERF_AMD_BF16) return launch_dir_chain_t<PB16>(stream, M, masks, ms, dlt, ls, rows, st);
-    return launch_dir_chain_t<PF32>(stream, M, masks, ms, dlt, ls, rows, st);
+    if (precision == NERF_AMD_BF16) return launch_tiles<PB16>(ref_chain9_kernel<PB16, false>, bwd_lds_total<PB16>(), M, st, stream, M, masks, ms, dlt, ls, rows);
+    return launch_tiles<PF32>(ref_chain9_kernel<PF32, false>, bwd_lds_total<PF32>(), M, st, stream, M, masks, ms, dlt, ls, rows);
 }
 #endif
 #if BWD_TU != 1 && BWD_TU != 3
@@ -1414,27 +1412,13 @@ template <class P>
 int launch_chain_t(int which, const char* stream, int64_t M, const char* act, char* dlt, size_t ls, size_t ms, float* rows, hipStream_t st) {
     // the forward's ReLU bit-mask records sit behind the activation slots of its dump (17 slots for Ref-NeRF, 5 for the proposal network)
     const char* masks = act + (size_t)(which == 3 ? PROP_DUMP_SLOTS : REF_DUMP_SLOTS) * ls;
-    constexpr int TS = P::NW * P::NT * 32;
-    const int64_t n_tiles = (M + TS - 1) / TS;
-    if (n_tiles == 0) return 0;
     const size_t lds = bwd_lds_total<P>();
-    const dim3 grid(bwd_grid(n_tiles)), block(P::NW * 64);
     switch (which) {
-        case 0:                                                // (its own translation unit: see bwd_launch_dir_chain)
-            return nk::bwd_launch_dir_chain(P::PREC, stream, M, masks, ms, dlt, ls, rows, st);
-        case 1:
-            if (int e = nerf_host::allow_dynamic_lds(reinterpret_cast<const void*>(ref_spa_bwd_kernel<P>), lds)) return e;
-            hipLaunchKernelGGL((ref_spa_bwd_kernel<P>), grid, block, lds, st, stream, M, masks, (unsigned long long)ms, dlt, (unsigned long long)ls);
-            break;
-        case 2:
-            if (int e = nerf_host::allow_dynamic_lds(reinterpret_cast<const void*>(ref_chain9_kernel<P, true>), lds)) return e;
-            hipLaunchKernelGGL((ref_chain9_kernel<P, true>), grid, block, lds, st, stream, M, masks, (unsigned long long)ms, (char*)nullptr, (unsigned long long)ls, rows);
-            break;
-        default:
-            if (int e = nerf_host::allow_dynamic_lds(reinterpret_cast<const void*>(prop_density_chain_kernel<P>), lds)) return e;
-            hipLaunchKernelGGL((prop_density_chain_kernel<P>), grid, block, lds, st, stream, M, masks, (unsigned long long)ms, rows);
+        case 0: return nk::bwd_launch_dir_chain(P::PREC, stream, M, masks, ms, dlt, ls, rows, st);      // (its own translation unit)
+        case 1: return launch_tiles<P>(ref_spa_bwd_kernel<P>, lds, M, st, stream, M, masks, ms, dlt, ls);
+        case 2: return launch_tiles<P>(ref_chain9_kernel<P, true>, lds, M, st, stream, M, masks, ms, (char*)nullptr, ls, rows);
+        default: return launch_tiles<P>(prop_density_chain_kernel<P>, lds, M, st, stream, M, masks, ms, rows);
     }
-    return (int)hipGetLastError();
 }
 // which: 0 Ref-NeRF directional, 1 Ref-NeRF spatial, 2 Ref-NeRF density gradient, 3 proposal density gradient; `start_frag`: where the
 // chain's stream begins in the blob
@@ -1452,28 +1436,65 @@ int nk::bwd_launch_chain(int which, int precision, const void* blob, int start_f
 }
 #endif  // BWD_TU != 1 && != 3
 #if BWD_TU != 2 && BWD_TU != 3
+// ------------------------------------------------------------------------------------------------ host-visible launchers (capi.hip)
 namespace {
+struct ChainCtx {                     // addressing of fragment dumps: slot l, K group kg
+    int precision; int64_t M; size_t breg, ls, sub;
+    ChainCtx(int prec, int64_t m) : precision(prec), M(m), breg(prec == NERF_AMD_BF16 ? 1024 : 2048), ls(nk::mlp_train_layer_stride(prec, m)), sub(16 * breg) {}
+    const char* at(const void* dump, int slot, int kg = 0) const { return reinterpret_cast<const char*>(dump) + (size_t)slot * ls + (size_t)kg * breg; }
+    char* at(void* dump, int slot, int kg = 0) const { return reinterpret_cast<char*>(dump) + (size_t)slot * ls + (size_t)kg * breg; }
+    // the two dumps of a dgrad chain: the forward's (its ReLU bit masks sit behind its `slots` activation slots) and the delta dump it writes
+    Dump act_dump(const void* act, int slots) const {
+        return Dump{const_cast<char*>(at(act, 0)), ls, at(act, slots), nk::mlp_train_mask_stride(precision, M)};
+    }
+    Dump delta_dump(void* dlt) const { return Dump{at(dlt, 0), ls, nullptr, 0ull}; }
+};
+}  // namespace
 
-template <class P, bool F8 = false>
-int launch_prop_bwd(const void* packed, const float* g, int64_t M, Dump act, Dump dlt, hipStream_t st) {
-    constexpr int TS = P::NW * P::NT * 32;
-    const int64_t n_tiles = (M + TS - 1) / TS;
-    if (n_tiles == 0) return 0;
-    const size_t lds = F8 ? bwd_lds_total_f8<P>() : bwd_lds_total<P>();
-    if (int e = nerf_host::allow_dynamic_lds(reinterpret_cast<const void*>(prop_bwd_kernel<P, F8>), lds)) return e;
-    hipLaunchKernelGGL((prop_bwd_kernel<P, F8>), dim3(bwd_grid(n_tiles)), dim3(P::NW * 64), lds, st, packed, g, M, act, dlt);
-    return (int)hipGetLastError();
+int nk::bwd_launch_prop_chain(const void* packed_bwd, int precision, const float* g_density, int64_t M, const void* act_dump, void* delta_dump,
+                          hipStream_t st) {
+    const ChainCtx c(precision == NERF_AMD_BF16_F8 ? NERF_AMD_BF16 : precision, M);
+    const Dump act = c.act_dump(act_dump, PROP_DUMP_SLOTS), dlt = c.delta_dump(delta_dump);
+    if (precision == NERF_AMD_BF16_F8)                       // (the chain reads only the mask bits of `act`)
+        return launch_tiles<PB16>(prop_bwd_kernel<PB16, true>, bwd_lds_total_f8<PB16>(), M, st, packed_bwd, g_density, M, act, dlt);
+    if (precision == NERF_AMD_BF16) return launch_tiles<PB16>(prop_bwd_kernel<PB16>, bwd_lds_total<PB16>(), M, st, packed_bwd, g_density, M, act, dlt);
+    return launch_tiles<PF32>(prop_bwd_kernel<PF32>, bwd_lds_total<PF32>(), M, st, packed_bwd, g_density, M, act, dlt);
 }
-template <class P, bool F8 = false>
-int launch_mip_bwd(const void* packed, const float* g, const float* rgbo, int64_t M, Dump act, Dump dlt, hipStream_t st) {
-    constexpr int TS = P::NW * P::NT * 32;
-    const int64_t n_tiles = (M + TS - 1) / TS;
-    if (n_tiles == 0) return 0;
-    const size_t lds = F8 ? bwd_lds_total_f8<P>() : bwd_lds_total<P>();
-    if (int e = nerf_host::allow_dynamic_lds(reinterpret_cast<const void*>(mip_bwd_kernel<P, F8>), lds)) return e;
-    hipLaunchKernelGGL((mip_bwd_kernel<P, F8>), dim3(bwd_grid(n_tiles)), dim3(P::NW * 64), lds, st, packed, g, rgbo, M, act, dlt);
-    return (int)hipGetLastError();
+int nk::bwd_launch_mip_chain(const void* packed_bwd, int precision, const float* g_rgbo, const float* rgbo, int64_t M, const void* act_dump,
+                         void* delta_dump, hipStream_t st) {
+    const ChainCtx c(precision == NERF_AMD_BF16_F8 ? NERF_AMD_BF16 : precision, M);
+    const Dump act = c.act_dump(act_dump, MIP_DUMP_SLOTS), dlt = c.delta_dump(delta_dump);
+    if (precision == NERF_AMD_BF16_F8) return launch_tiles<PB16>(mip_bwd_kernel<PB16, true>, bwd_lds_total_f8<PB16>(), M, st, packed_bwd, g_rgbo, rgbo, M, act, dlt);
+    if (precision == NERF_AMD_BF16) return launch_tiles<PB16>(mip_bwd_kernel<PB16>, bwd_lds_total<PB16>(), M, st, packed_bwd, g_rgbo, rgbo, M, act, dlt);
+    return launch_tiles<PF32>(mip_bwd_kernel<PF32>, bwd_lds_total<PF32>(), M, st, packed_bwd, g_rgbo, rgbo, M, act, dlt);
 }
+
+// ------------------------------------------------------------------------------------------------ weight gradients: the product shapes
+namespace {
+// One row per shape of a product dW = X^T Y (X: K groups of delta slots, Y: K groups of an activation / encoding slot): the instantiation
+// wgrad_kernel_{bf16,f32}<KGX, KGY, WO, YKIND> that computes it and everything that follows from the shape.  A workgroup's partial is
+// (32 NOB) x (32 NIB) floats of that instantiation: prow() / pcol() are the kernels' own two expressions.
+enum Shape { HIDDEN, ENC_PE10, HEADS, HEAD_128, DIR_PE4, HEAD_256, BOTTLE, IDE, N_SHAPES };
+struct ShapeRow {
+    int kgx, kgy, wo, ykind;
+    bool heavy;         // 512 accumulator registers, one workgroup per CU: one round of the chip per launch (light shapes: two)
+    bool f8;            // the shape exists under fp8 dumps (NERF_AMD_BF16_F8: the proposal / MipNeRF products) ...
+    bool xf8, yf8;      // ... where X / Y is a hidden slot kept in scaled e4m3 (subtiles F8_SUB_BYTES apart)
+    constexpr int prow() const { return 32 * ((kgx + 1) / 2); }
+    constexpr int pcol() const { return 32 * ((ykind == Y_DMAP) ? (kgy + 1) / 2 : ((ykind == Y_PE10 || ykind == Y_IDE) ? 2 : 1)); }
+};
+constexpr ShapeRow SHAPES[N_SHAPES] = {
+    //           KGX KGY WO  YKIND    heavy  f8     xf8    yf8
+    /* HIDDEN   */ {16, 16, 2, Y_DMAP, true,  true,  true,  true},      // 256 x 256: delta_L^T y_{L-1} (bf16: wgrad256_kernel)
+    /* ENC_PE10 */ {16, 4,  4, Y_PE10, false, true,  true,  false},     // 256 x [x | PE10(x)]
+    /* HEADS    */ {9,  16, 1, Y_DMAP, true,  true,  true,  true},      // (128 + head rows) x 256
+    /* HEAD_128 */ {1,  8,  1, Y_DMAP, false, true,  false, true},      // head rows x 128
+    /* DIR_PE4  */ {8,  2,  4, Y_PE4,  false, true,  true,  false},     // 128 x [d | PE4(d)]
+    /* HEAD_256 */ {1,  16, 1, Y_DMAP, false, true,  false, true},      // head rows x 256
+    /* BOTTLE   */ {16, 8,  2, Y_DMAP, false, false, false, false},     // 256 x 128 (Ref-NeRF: delta x bottle-neck)
+    /* IDE      */ {16, 3,  4, Y_IDE,  false, false, false, false},     // 256 x [IDE 38 | n.d] (Ref-NeRF)
+};
+static_assert(SHAPES[HIDDEN].prow() == 256 && SHAPES[HIDDEN].pcol() == 256, "wgrad256_kernel's partial");
 
 template <bool F8>
 int launch_wgrad256(const WgradJobs& jobs, int n_jobs, int n_wg, int64_t n_sub, hipStream_t st) {
@@ -1481,96 +1502,27 @@ int launch_wgrad256(const WgradJobs& jobs, int n_jobs, int n_wg, int64_t n_sub, 
     hipLaunchKernelGGL((wgrad256_kernel<F8>), dim3(n_wg, n_jobs), dim3(512), 65536, st, jobs, n_sub);
     return (int)hipGetLastError();
 }
-template <int KGX, int KGY, int WO, int YKIND>
-int launch_wgrad(int precision, const WgradJobs& jobs, int n_jobs, int n_wg, int64_t n_sub, hipStream_t st) {
-    if (precision == NERF_AMD_BF16) hipLaunchKernelGGL((wgrad_kernel_bf16<KGX, KGY, WO, YKIND>), dim3(n_wg, n_jobs), dim3(256), 0, st, jobs, n_sub);
-    else hipLaunchKernelGGL((wgrad_kernel_f32<KGX, KGY, WO, YKIND>), dim3(n_wg, n_jobs), dim3(256), 0, st, jobs, n_sub);
+// the one launch of shape S, on plain (fp32 / bf16) or fp8 dumps: n_wg workgroups for each of n products
+template <int S, bool F8>
+int launch_shape(int precision, const WgradJobs& jobs, int n, int n_wg, int64_t n_sub, hipStream_t st) {
+    constexpr ShapeRow R = SHAPES[S];
+    const dim3 grid(n_wg, n), block(256);
+    if constexpr (F8 && !R.f8) return (int)hipErrorInvalidValue;
+    else if constexpr (S == HIDDEN && F8) return launch_wgrad256<true>(jobs, n, n_wg, n_sub, st);
+    else if constexpr (F8) hipLaunchKernelGGL((wgrad_kernel_bf16<R.kgx, R.kgy, R.wo, R.ykind, R.xf8, R.yf8>), grid, block, 0, st, jobs, n_sub);
+    else if (precision == NERF_AMD_BF16) {
+        if constexpr (S == HIDDEN) return launch_wgrad256<false>(jobs, n, n_wg, n_sub, st);
+        else hipLaunchKernelGGL((wgrad_kernel_bf16<R.kgx, R.kgy, R.wo, R.ykind>), grid, block, 0, st, jobs, n_sub);
+    } else hipLaunchKernelGGL((wgrad_kernel_f32<R.kgx, R.kgy, R.wo, R.ykind>), grid, block, 0, st, jobs, n_sub);
     return (int)hipGetLastError();
 }
-// fp8 dump operands (NERF_AMD_BF16_F8): XF8 / YF8 say which operand comes from an fp8 slot
-template <int KGX, int KGY, int WO, int YKIND, bool XF8, bool YF8>
-int launch_wgrad_f8(const WgradJobs& jobs, int n_jobs, int n_wg, int64_t n_sub, hipStream_t st) {
-    hipLaunchKernelGGL((wgrad_kernel_bf16<KGX, KGY, WO, YKIND, XF8, YF8>), dim3(n_wg, n_jobs), dim3(256), 0, st, jobs, n_sub);
-    return (int)hipGetLastError();
-}
+using LaunchShape = int (*)(int, const WgradJobs&, int, int, int64_t, hipStream_t);
+#define SHAPE_LAUNCHERS(F8) {launch_shape<HIDDEN, F8>,  launch_shape<ENC_PE10, F8>, launch_shape<HEADS, F8>,  launch_shape<HEAD_128, F8>, \
+                             launch_shape<DIR_PE4, F8>, launch_shape<HEAD_256, F8>, launch_shape<BOTTLE, F8>, launch_shape<IDE, F8>}
+constexpr LaunchShape LAUNCH_SHAPE_F8[N_SHAPES] = SHAPE_LAUNCHERS(true), LAUNCH_SHAPE[N_SHAPES] = SHAPE_LAUNCHERS(false);
+#undef SHAPE_LAUNCHERS
 
-}  // namespace
-
-// ------------------------------------------------------------------------------------------------ host-visible launchers (capi.hip)
-int nk::bwd_launch_prop_chain(const void* packed_bwd, int precision, const float* g_density, int64_t M, const void* act_dump, void* delta_dump,
-                          hipStream_t st) {
-    const unsigned long long ls = mlp_train_layer_stride(precision, M), ms = mlp_train_mask_stride(precision, M);
-    const Dump act{const_cast<char*>(reinterpret_cast<const char*>(act_dump)), ls, reinterpret_cast<const char*>(act_dump) + (size_t)PROP_DUMP_SLOTS * ls, ms},
-               dlt{reinterpret_cast<char*>(delta_dump), ls, nullptr, 0ull};
-    if (precision == NERF_AMD_BF16_F8) return launch_prop_bwd<PB16, true>(packed_bwd, g_density, M, act, dlt, st);   // (the chain reads only the mask bits of `act`)
-    if (precision == NERF_AMD_BF16) return launch_prop_bwd<PB16>(packed_bwd, g_density, M, act, dlt, st);
-    return launch_prop_bwd<PF32>(packed_bwd, g_density, M, act, dlt, st);
-}
-int nk::bwd_launch_mip_chain(const void* packed_bwd, int precision, const float* g_rgbo, const float* rgbo, int64_t M, const void* act_dump,
-                         void* delta_dump, hipStream_t st) {
-    const unsigned long long ls = mlp_train_layer_stride(precision, M), ms = mlp_train_mask_stride(precision, M);
-    const Dump act{const_cast<char*>(reinterpret_cast<const char*>(act_dump)), ls, reinterpret_cast<const char*>(act_dump) + (size_t)MIP_DUMP_SLOTS * ls, ms},
-               dlt{reinterpret_cast<char*>(delta_dump), ls, nullptr, 0ull};
-    if (precision == NERF_AMD_BF16_F8) return launch_mip_bwd<PB16, true>(packed_bwd, g_rgbo, rgbo, M, act, dlt, st);
-    if (precision == NERF_AMD_BF16) return launch_mip_bwd<PB16>(packed_bwd, g_rgbo, rgbo, M, act, dlt, st);
-    return launch_mip_bwd<PF32>(packed_bwd, g_rgbo, rgbo, M, act, dlt, st);
-}
-
-// ------------------------------------------------------------------------------------------------ weight gradients: orchestration
-namespace {
-struct Product { const char* x0; int kgx0; const char* x1; const char* y; float* partial; float* bias_partial; };
-
-// shape codes: 0 = 256 x 256 (D map), 1 = 256 x PE10, 2 = (128 + head) x 256, 3 = head x 128, 4 = 128 x PE4, 5 = head x 256
-// f8 (NERF_AMD_BF16_F8 dumps of the proposal / MipNeRF networks): the hidden delta / activation slots among the operands are fp8 slots
-// (subtiles F8_SUB_BYTES apart); which operand of a shape is one follows from what the shape multiplies (see the callers)
-int run_wgrad(int shape, int precision, const Product* prods, int n, int n_wg, int64_t n_sub, hipStream_t st, bool f8 = false) {
-    if (n < 1 || n > WG_MAX_JOBS) return (int)hipErrorInvalidValue;
-    const size_t breg = precision == NERF_AMD_BF16 ? 1024 : 2048;
-    const bool xf8 = f8 && shape != 3 && shape != 5, yf8 = f8 && (shape == 0 || shape == 2 || shape == 3 || shape == 5);
-    WgradJobs jobs = {};
-    for (int i = 0; i < n; ++i) {
-        WgradJob& J = jobs.j[i];
-        J.x0 = FragMat{prods[i].x0, xf8 ? (size_t)F8_SUB_BYTES : 16 * breg};
-        J.kgx0 = prods[i].kgx0;
-        J.x1 = FragMat{prods[i].x1, 16 * breg};
-        J.y = FragMat{prods[i].y, yf8 ? (size_t)F8_SUB_BYTES : 16 * breg};
-        J.partial = prods[i].partial; J.bias_partial = prods[i].bias_partial;
-    }
-    if (f8) {
-        if (precision != NERF_AMD_BF16) return (int)hipErrorInvalidValue;
-        switch (shape) {
-            case 0: return launch_wgrad256<true>(jobs, n, n_wg, n_sub, st);
-            case 1: return launch_wgrad_f8<16, 4, 4, Y_PE10, true, false>(jobs, n, n_wg, n_sub, st);
-            case 2: return launch_wgrad_f8<9, 16, 1, Y_DMAP, true, true>(jobs, n, n_wg, n_sub, st);
-            case 3: return launch_wgrad_f8<1, 8, 1, Y_DMAP, false, true>(jobs, n, n_wg, n_sub, st);
-            case 4: return launch_wgrad_f8<8, 2, 4, Y_PE4, true, false>(jobs, n, n_wg, n_sub, st);
-            case 5: return launch_wgrad_f8<1, 16, 1, Y_DMAP, false, true>(jobs, n, n_wg, n_sub, st);
-        }
-        return (int)hipErrorInvalidValue;
-    }
-    switch (shape) {
-        case 0: if (precision == NERF_AMD_BF16) return launch_wgrad256<false>(jobs, n, n_wg, n_sub, st);      // 4 x 2 waves of 2 x 4 blocks
-                hipLaunchKernelGGL((wgrad_kernel_f32<16, 16, 2, Y_DMAP>), dim3(n_wg, n), dim3(256), 0, st, jobs, n_sub);   // fp32: 2 x 2 waves of 4 x 4 blocks
-                return (int)hipGetLastError();
-        case 1: return launch_wgrad<16, 4, 4, Y_PE10>(precision, jobs, n, n_wg, n_sub, st);      // 4 x 1 waves of 2 x 2 blocks
-        case 2: return launch_wgrad<9, 16, 1, Y_DMAP>(precision, jobs, n, n_wg, n_sub, st);      // NOB 5 x NIB 8: 1 x 4 waves of 5 x 2 blocks
-        case 3: return launch_wgrad<1, 8, 1, Y_DMAP>(precision, jobs, n, n_wg, n_sub, st);       // NOB 1 x NIB 4
-        case 4: return launch_wgrad<8, 2, 4, Y_PE4>(precision, jobs, n, n_wg, n_sub, st);        // NOB 4 x NIB 1
-        case 5: return launch_wgrad<1, 16, 1, Y_DMAP>(precision, jobs, n, n_wg, n_sub, st);      // NOB 1 x NIB 8
-        case 6: return launch_wgrad<16, 8, 2, Y_DMAP>(precision, jobs, n, n_wg, n_sub, st);      // 256 x 128 (Ref-NeRF: delta x bottle-neck)
-        case 7: return launch_wgrad<16, 3, 4, Y_IDE>(precision, jobs, n, n_wg, n_sub, st);       // 256 x [IDE 38 | n.d]
-    }
-    return (int)hipErrorInvalidValue;
-}
-int run_finalize(const FinalizeJob* f, int n, hipStream_t st) {
-    if (n < 1 || n > FIN_MAX_JOBS) return (int)hipErrorInvalidValue;
-    FinalizeJobs jobs = {};
-    for (int i = 0; i < n; ++i) jobs.j[i] = f[i];
-    hipLaunchKernelGGL(wgrad_finalize_kernel, dim3(128, n), dim3(256), 0, st, jobs);
-    return (int)hipGetLastError();
-}
-// workgroups per product of a launch that batches `n_jobs` products: the big-accumulator shapes (512 registers: one workgroup per CU)
-// get one round of the chip, the light shapes two
+// workgroups per product of a launch that batches `n_jobs` products: the heavy shapes get one round of the chip, the light shapes two
 int wgrad_workgroups(int64_t n_sub, int n_jobs, bool heavy) {
     const int64_t total = (int64_t)nerf_host::cu_count() * (heavy ? 1 : 2);
     int64_t n = total / n_jobs;
@@ -1582,115 +1534,209 @@ struct Carver {
     char* p;
     float* take(size_t floats) { float* r = reinterpret_cast<float*>(p); p += align256(floats * 4); return r; }
 };
-}  // namespace
 
-int64_t bwd_n_sub(int precision, int64_t M) {
-    const int64_t ts = (precision != NERF_AMD_F32) ? (int64_t)PB16::NW * PB16::NT * 32 : (int64_t)PF32::NW * PF32::NT * 32;
-    return ((M + ts - 1) / ts) * (ts / 32);
+// ------------------------------------------------------------------------------------------------ weight gradients: one plan per network
+// One product of a batch.  X = K groups [dkg, dkg + kgx0) of delta slot `dslot`, followed by the K groups of delta slot `x1slot` up to the
+// shape's KGX; Y = activation slot `aslot` from K group `akg`; `bias`: the row sums of X are wanted too.
+struct Prod {
+    int dslot, aslot;
+    int kgx0 = 16, dkg = 0, x1slot = -1, akg = 0;
+    bool bias = true;
+    float *partial = nullptr, *bias_partial = nullptr;      // [n_wg][prow][pcol], [n_wg][prow]: set by the plan's walk
+    Prod(int delta_slot = 0, int act_slot = 0) : dslot(delta_slot), aslot(act_slot) {}
+    Prod& x_groups(int n, int first = 0) { kgx0 = n; dkg = first; return *this; }
+    Prod& then_slot(int slot) { x1slot = slot; return *this; }
+    Prod& y_from(int kg) { akg = kg; return *this; }
+    Prod& no_bias() { bias = false; return *this; }
+};
+// The products of one launch, and what the finalize launch takes out of them: the FinalizeJob of the kernel, filled by name.
+struct Batch {
+    Shape shape = HIDDEN;
+    bool biases_last = false;       // the bias partials lie behind all matrix partials of the batch (default: behind their own product's)
+    int n = 0, n_wg = 0;
+    Prod p[WG_MAX_JOBS];
+    Batch& add(const Prod& prod) { p[n++] = prod; return *this; }
+    // rows [row0, row0 + rows) x columns [0, cols) of product i -> dst (leading dimension ld) from column col0; their bias sums -> bias_dst
+    FinalizeJob window(int i, int row0, int rows, int cols, float* dst, int ld, int col0, float* bias_dst) const {
+        const ShapeRow& R = SHAPES[shape];
+        FinalizeJob J = {};
+        J.partial = p[i].partial; J.prow = R.prow(); J.pcol = R.pcol();
+        J.dst = dst; J.ld = ld; J.col0 = col0; J.row0 = row0; J.rows = rows; J.cols = cols;
+        if (bias_dst != nullptr) { J.bias_partial = p[i].bias_partial; J.bias_dst = bias_dst; J.bias_prow = R.prow(); J.brow0 = row0; J.brows = rows; }
+        J.n_wg = n_wg;
+        return J;
+    }
+    // all rows of product i, its first `cols` columns -> dst at column col0; bias_dst (or nullptr) gets the bias of all rows
+    FinalizeJob matrix(int i, int cols, float* dst, int ld, int col0, float* bias_dst) const {
+        return window(i, 0, SHAPES[shape].prow(), cols, dst, ld, col0, bias_dst);
+    }
+    // rows [row0, row0 + rows) of product i, whole rows -> dst; bias_dst (or nullptr) gets the bias of the same rows
+    FinalizeJob rows(int i, int row0, int rows, float* dst, int ld, float* bias_dst) const {
+        return window(i, row0, rows, SHAPES[shape].pcol(), dst, ld, 0, bias_dst);
+    }
+    // the bias sums of rows [row0, row0 + rows) of product i alone
+    FinalizeJob bias_rows(int i, int row0, int rows, float* bias_dst) const {
+        FinalizeJob J = window(i, row0, 0, SHAPES[shape].pcol(), nullptr, 0, 0, bias_dst);
+        J.brows = rows;
+        return J;
+    }
+};
+
+// The workspace of one backward and the product batches that run in it, described ONCE (like RenderWs in capi.hip): the constructor
+// walks the parts in their order -- from NULL for the size (the *_workspace_bytes functions), from the caller's pointer for the parts.
+// Every part is rounded up to 256 bytes; the base is aligned up to 256, which the trailing slack pays for.
+//   density gradient:  d_enc (M, 64)
+//   proposal:          the partials of 3 batches
+//   MipNeRF:           the partials of 5 batches | G (128, 256) for the un-fold
+//   Ref-NeRF:          delta dump (REF_DUMP_SLOTS slots) | d_allin (M, 192) | the partials of 7 batches
+// A batch's partials: per product [n_wg][prow][pcol] and, where wanted, the bias sums [n_wg][prow];
+// n_wg = wgrad_workgroups(subtiles, products in the batch, heavy shape).  The batches are launched in the order they stand in.
+enum PlanKind { PLAN_PROPOSAL, PLAN_MIP, PLAN_REF, PLAN_DENSITY };
+constexpr int PLAN_MAX_BATCHES = 7;
+struct BwdPlan {
+    bool f8;                        // hidden slots of both dumps in scaled e4m3 (arithmetic: bf16)
+    ChainCtx c;
+    int64_t n_sub;
+    float* d_enc = nullptr;         // density gradient
+    char* dlt = nullptr;            // Ref-NeRF: delta dump ...
+    float* d_allin = nullptr;       // ... and the 6 feature blocks of the 167-wide input vector
+    float* G = nullptr;             // MipNeRF: dc^T g6
+    int n_batches = 0;
+    Batch b[PLAN_MAX_BATCHES];
+    size_t bytes;
+
+    Batch& batch(Shape shape, bool biases_last = false) {
+        Batch& B = b[n_batches++];
+        B.shape = shape; B.biases_last = biases_last;
+        return B;
+    }
+    BwdPlan(PlanKind kind, int precision, int64_t M, void* base)
+        : f8(precision == NERF_AMD_BF16_F8), c(f8 ? NERF_AMD_BF16 : precision, M), n_sub(nk::mlp_train_n_sub(c.precision, M)) {
+        char* const p0 = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255);
+        Carver ws{p0};
+        switch (kind) {
+            case PLAN_DENSITY:
+                d_enc = ws.take((size_t)M * 64);
+                break;
+            case PLAN_PROPOSAL: {                              // layers.{0,2,4,6,8}: delta slots 0..4, activation slots 0..3, encoding slot 4
+                Batch& hid = batch(HIDDEN);
+                for (int l = 1; l <= 3; ++l) hid.add(Prod(l, l - 1));                           // layers.{2,4,6}: delta_L^T y_{L-1}
+                batch(ENC_PE10).add(Prod(0, 4));                                                // layers.0: delta_0^T [x | PE10(x)]
+                batch(HEAD_256).add(Prod(4, 3).x_groups(1));                                    // layers.8: g^T y_3 (feature 0 of the head K group)
+                break;
+            }
+            case PLAN_MIP: {                                   // delta slots 0..6 hidden, 7 dc, 8 [dpre dsigma]; activation slot 7 c, 8 the encodings
+                Batch& hid = batch(HIDDEN);
+                for (int l = 1; l <= 6; ++l) hid.add(Prod(l, l - 1));                           // layers 1..6 (the skip layer 4: its hidden columns)
+                batch(ENC_PE10, true).add(Prod(0, 8)).add(Prod(4, 8).no_bias());                // lin_block1.0, the encoding columns of lin_block2.0
+                batch(HEADS).add(Prod(7, 6).x_groups(8).then_slot(8));                          // [dc | dpre dsigma]^T g6: rows 0..127 G, 128..130 unused, 131 opacity_head.0
+                batch(HEAD_128).add(Prod(8, 7).x_groups(1).no_bias());                          // rgb_layer.2: dpre^T c
+                batch(DIR_PE4).add(Prod(7, 8).x_groups(8).y_from(4).no_bias());                 // rgb_layer.0's direction columns: dc^T [d | PE4(d)]
+                break;
+            }
+            case PLAN_REF: {                                   // slots 0..7 spatial, 8 [bottle-neck | heads | spec head], 9..16 directional
+                dlt = reinterpret_cast<char*>(ws.take((size_t)REF_DUMP_SLOTS * c.ls / 4));
+                d_allin = ws.take((size_t)M * 192);
+                Batch &spa = batch(HIDDEN), &dir = batch(HIDDEN);
+                for (int l = 1; l <= 7; ++l) spa.add(Prod(l, l - 1));                           // spatial layers 1..7 (layer 4: its hidden columns)
+                for (int l = 1; l <= 7; ++l) dir.add(Prod(9 + l, 9 + l - 1));                   // directional layers 1..7
+                batch(ENC_PE10, true).add(Prod(0, 8).y_from(11)).add(Prod(4, 8).y_from(11).no_bias());   // spatial layers 0 and 4 x [x | PE10(x)]
+                batch(BOTTLE).add(Prod(9, 8)).add(Prod(13, 8));                                 // directional layers 0 and 4 x bottle-neck
+                batch(IDE).add(Prod(9, 8).y_from(8).no_bias()).add(Prod(13, 8).y_from(8).no_bias());     // ... x [IDE | n.d]
+                batch(HEADS).add(Prod(8, 7).x_groups(9));                                       // [bottle-neck | heads]^T S7
+                batch(HEAD_256).add(Prod(8, 16).x_groups(1, 9));                                // spec head
+                break;
+            }
+        }
+        for (int k = 0; k < n_batches; ++k) {
+            Batch& B = b[k];
+            const ShapeRow& R = SHAPES[B.shape];
+            B.n_wg = wgrad_workgroups(n_sub, B.n, R.heavy);
+            const size_t rows = (size_t)B.n_wg * R.prow();
+            for (int i = 0; i < B.n; ++i) {
+                B.p[i].partial = ws.take(rows * R.pcol());
+                if (B.p[i].bias && !B.biases_last) B.p[i].bias_partial = ws.take(rows);
+            }
+            for (int i = 0; i < B.n && B.biases_last; ++i)
+                if (B.p[i].bias) B.p[i].bias_partial = ws.take(rows);
+        }
+        if (kind == PLAN_MIP) G = ws.take((size_t)128 * 256);
+        bytes = (size_t)(ws.p - p0) + (kind == PLAN_REF ? 512 : 256);
+    }
+
+    // every batch's launch, in order, on the two dumps
+    int run_products(const void* act, const void* delta, hipStream_t st) const {
+        for (int k = 0; k < n_batches; ++k) {
+            const Batch& B = b[k];
+            const ShapeRow& R = SHAPES[B.shape];
+            WgradJobs jobs = {};
+            for (int i = 0; i < B.n; ++i) {
+                const Prod& P = B.p[i];
+                WgradJob& J = jobs.j[i];
+                J.x0 = FragMat{c.at(delta, P.dslot, P.dkg), f8 && R.xf8 ? (size_t)F8_SUB_BYTES : c.sub};
+                J.kgx0 = P.kgx0;
+                J.x1 = FragMat{P.x1slot < 0 ? nullptr : c.at(delta, P.x1slot), c.sub};
+                J.y = FragMat{c.at(act, P.aslot, P.akg), f8 && R.yf8 ? (size_t)F8_SUB_BYTES : c.sub};
+                J.partial = P.partial; J.bias_partial = P.bias_partial;
+            }
+            if (int e = (f8 ? LAUNCH_SHAPE_F8 : LAUNCH_SHAPE)[B.shape](c.precision, jobs, B.n, B.n_wg, n_sub, st)) return e;
+        }
+        return 0;
+    }
+};
+int run_finalize(const FinalizeJob* f, int n, hipStream_t st) {
+    if (n < 1 || n > FIN_MAX_JOBS) return (int)hipErrorInvalidValue;
+    FinalizeJobs jobs = {};
+    for (int i = 0; i < n; ++i) jobs.j[i] = f[i];
+    hipLaunchKernelGGL(wgrad_finalize_kernel, dim3(128, n), dim3(256), 0, st, jobs);
+    return (int)hipGetLastError();
 }
+int blocks_1d(int64_t work) { int64_t b = (work + 255) / 256; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
+}  // namespace
 
 // workspace: per-product workgroup partials (+ G for the un-fold)
 size_t nk::bwd_wgrad_workspace_bytes(int net, int precision, int64_t M) {
-    const int64_t n_sub = bwd_n_sub(precision, M);
-    if (net == NERF_AMD_NET_PROPOSAL) {
-        const size_t w0 = wgrad_workgroups(n_sub, 3, true), w1 = wgrad_workgroups(n_sub, 1, false);
-        return 3 * (align256(w0 * 256 * 256 * 4) + align256(w0 * 256 * 4)) + align256(w1 * 256 * 64 * 4) + align256(w1 * 256 * 4) +
-               align256(w1 * 32 * 256 * 4) + align256(w1 * 32 * 4) + 256;
-    }
-    if (net == NERF_AMD_NET_MIP) {
-        const size_t w0 = wgrad_workgroups(n_sub, 6, true), w1 = wgrad_workgroups(n_sub, 2, false), w2 = wgrad_workgroups(n_sub, 1, true),
-                     w3 = wgrad_workgroups(n_sub, 1, false);
-        return 6 * (align256(w0 * 256 * 256 * 4) + align256(w0 * 256 * 4)) + 2 * align256(w1 * 256 * 64 * 4) + align256(w1 * 256 * 4) +
-               align256(w2 * 160 * 256 * 4) + align256(w2 * 160 * 4) + align256(w3 * 32 * 128 * 4) + align256(w3 * 128 * 32 * 4) +
-               align256((size_t)128 * 256 * 4) + 256;
-    }
+    if (net == NERF_AMD_NET_PROPOSAL) return BwdPlan(PLAN_PROPOSAL, precision, M, nullptr).bytes;
+    if (net == NERF_AMD_NET_MIP) return BwdPlan(PLAN_MIP, precision, M, nullptr).bytes;
     return 0;
 }
 
 // ProposalNetwork: d_w / d_b = gradients of layers.{0,2,4,6,8} (addtional.py:67-71), written in the reference's (out, in) layout
 int nk::bwd_prop_weight_grads(int precision, int64_t M, const void* act_dump, const void* delta_dump, float* const* d_w, float* const* d_b,
                           void* workspace, hipStream_t st) {
-    const bool f8 = precision == NERF_AMD_BF16_F8;          // hidden slots of both dumps in scaled e4m3 (arithmetic: bf16)
-    if (f8) precision = NERF_AMD_BF16;
-    const int64_t n_sub = bwd_n_sub(precision, M);
-    if (n_sub == 0) return 0;
-    const size_t breg = precision == NERF_AMD_BF16 ? 1024 : 2048, ls = mlp_train_layer_stride(precision, M);
-    const char* act = reinterpret_cast<const char*>(act_dump);
-    const char* dlt = reinterpret_cast<const char*>(delta_dump);
-    auto A = [&](int slot, int kg0 = 0) { return act + (size_t)slot * ls + (size_t)kg0 * breg; };
-    auto D = [&](int slot, int kg0 = 0) { return dlt + (size_t)slot * ls + (size_t)kg0 * breg; };
-    const int w0 = wgrad_workgroups(n_sub, 3, true), w1 = wgrad_workgroups(n_sub, 1, false);
-    Carver ws{reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255)};
-    float *pw[3], *pb[3];
-    for (int i = 0; i < 3; ++i) { pw[i] = ws.take((size_t)w0 * 256 * 256); pb[i] = ws.take((size_t)w0 * 256); }
-    float* pe = ws.take((size_t)w1 * 256 * 64); float* pe_b = ws.take((size_t)w1 * 256);
-    float* ph = ws.take((size_t)w1 * 32 * 256); float* ph_b = ws.take((size_t)w1 * 32);
-    // layers.{2,4,6}: delta_L^T y_{L-1}
-    Product p0[3];
-    for (int i = 0; i < 3; ++i) p0[i] = Product{D(i + 1), 16, nullptr, A(i), pw[i], pb[i]};
-    if (int e = run_wgrad(0, precision, p0, 3, w0, n_sub, st, f8)) return e;
-    const Product p1{D(0), 16, nullptr, A(4), pe, pe_b};                   // layers.0: delta_0^T [x | PE10(x)]
-    if (int e = run_wgrad(1, precision, &p1, 1, w1, n_sub, st, f8)) return e;
-    const Product p5{D(4), 1, nullptr, A(3), ph, ph_b};                    // layers.8: g^T y_3 (slot feature 0 of the head K group)
-    if (int e = run_wgrad(5, precision, &p5, 1, w1, n_sub, st, f8)) return e;
+    const BwdPlan plan(PLAN_PROPOSAL, precision, M, workspace);
+    if (plan.n_sub == 0) return 0;
+    if (int e = plan.run_products(act_dump, delta_dump, st)) return e;
+    const Batch &hid = plan.b[0], &enc = plan.b[1], &head = plan.b[2];
     FinalizeJob f[5];
-    for (int i = 0; i < 3; ++i) f[i] = FinalizeJob{pw[i], 256, 256, d_w[i + 1], 256, 0, 0, 256, 256, pb[i], d_b[i + 1], 256, 0, 256, w0};
-    f[3] = FinalizeJob{pe, 256, 64, d_w[0], 63, 0, 0, 256, 63, pe_b, d_b[0], 256, 0, 256, w1};
-    f[4] = FinalizeJob{ph, 32, 256, d_w[4], 256, 0, 0, 1, 256, ph_b, d_b[4], 32, 0, 1, w1};
-    return run_finalize(f, 5, st);
+    int n = 0;
+    for (int i = 0; i < 3; ++i) f[n++] = hid.matrix(i, 256, d_w[i + 1], 256, 0, d_b[i + 1]);      // layers.{2,4,6}
+    f[n++] = enc.matrix(0, 63, d_w[0], 63, 0, d_b[0]);                                            // layers.0: the 63 real encoding columns
+    f[n++] = head.rows(0, 0, 1, d_w[4], 256, d_b[4]);                                             // layers.8: row 0 of the head product
+    return run_finalize(f, n, st);
 }
 
 // MipNeRF: tensors in _linear_layers() order (0..3 lin_block1, 4..6 lin_block2, 7 bottle_neck.0, 8 opacity_head.0, 9, 10 rgb_layer.{0,2})
 int nk::bwd_mip_weight_grads(int precision, int64_t M, const void* act_dump, const void* delta_dump, const float* const* w, const float* const* b,
                          float* const* d_w, float* const* d_b, void* workspace, hipStream_t st) {
-    const bool f8 = precision == NERF_AMD_BF16_F8;          // hidden slots of both dumps in scaled e4m3 (arithmetic: bf16)
-    if (f8) precision = NERF_AMD_BF16;
-    const int64_t n_sub = bwd_n_sub(precision, M);
-    if (n_sub == 0) return 0;
-    const size_t breg = precision == NERF_AMD_BF16 ? 1024 : 2048, ls = mlp_train_layer_stride(precision, M);
-    const char* act = reinterpret_cast<const char*>(act_dump);
-    const char* dlt = reinterpret_cast<const char*>(delta_dump);
-    auto A = [&](int slot, int kg0 = 0) { return act + (size_t)slot * ls + (size_t)kg0 * breg; };
-    auto D = [&](int slot, int kg0 = 0) { return dlt + (size_t)slot * ls + (size_t)kg0 * breg; };
-    const int w0 = wgrad_workgroups(n_sub, 6, true), w1 = wgrad_workgroups(n_sub, 2, false), w2 = wgrad_workgroups(n_sub, 1, true),
-              w3 = wgrad_workgroups(n_sub, 1, false);
-    Carver ws{reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255)};
-    float *pw[6], *pb[6];
-    for (int i = 0; i < 6; ++i) { pw[i] = ws.take((size_t)w0 * 256 * 256); pb[i] = ws.take((size_t)w0 * 256); }
-    float* pe0 = ws.take((size_t)w1 * 256 * 64); float* pe4 = ws.take((size_t)w1 * 256 * 64); float* pe0_b = ws.take((size_t)w1 * 256);
-    float* pg = ws.take((size_t)w2 * 160 * 256); float* pg_b = ws.take((size_t)w2 * 160);
-    float* phc = ws.take((size_t)w3 * 32 * 128);
-    float* pcd = ws.take((size_t)w3 * 128 * 32);
-    float* G = ws.take((size_t)128 * 256);
-    // the six 256 x 256 products in one launch: layer L = delta_L^T y_{L-1} for L = 1, 2, 3, 5, 6 and the hidden columns of the skip layer 4
-    const int Ls[6] = {1, 2, 3, 4, 5, 6};
-    Product p0[6];
-    for (int i = 0; i < 6; ++i) p0[i] = Product{D(Ls[i]), 16, nullptr, A(Ls[i] - 1), pw[i], pb[i]};
-    if (int e = run_wgrad(0, precision, p0, 6, w0, n_sub, st, f8)) return e;
-    // lin_block1.0 and the encoding columns of lin_block2.0: delta^T [x | PE10(x)]
-    const Product p1[2] = {Product{D(0), 16, nullptr, A(8), pe0, pe0_b}, Product{D(4), 16, nullptr, A(8), pe4, nullptr}};
-    if (int e = run_wgrad(1, precision, p1, 2, w1, n_sub, st, f8)) return e;
-    // heads: [dc | dpre dsigma]^T g6 -> G (rows 0..127), rows 128..130 unused, row 131 = opacity_head.0
-    const Product p2{D(7), 8, D(8), A(6), pg, pg_b};
-    if (int e = run_wgrad(2, precision, &p2, 1, w2, n_sub, st, f8)) return e;
-    const Product p3{D(8), 1, nullptr, A(7), phc, nullptr};                // rgb_layer.2: dpre^T c
-    if (int e = run_wgrad(3, precision, &p3, 1, w3, n_sub, st, f8)) return e;
-    const Product p4{D(7), 8, nullptr, A(8, 4), pcd, nullptr};             // rgb_layer.0's direction columns: dc^T [d | PE4(d)]
-    if (int e = run_wgrad(4, precision, &p4, 1, w3, n_sub, st, f8)) return e;
+    const BwdPlan plan(PLAN_MIP, precision, M, workspace);
+    if (plan.n_sub == 0) return 0;
+    if (int e = plan.run_products(act_dump, delta_dump, st)) return e;
+    const Batch &hid = plan.b[0], &enc = plan.b[1], &heads = plan.b[2], &rgb = plan.b[3], &dir = plan.b[4];
+    float* G = plan.G;
     FinalizeJob f[13];
     int n = 0;
     for (int i = 0; i < 6; ++i) {
-        const int L = Ls[i];
-        if (L == 4) f[n++] = FinalizeJob{pw[i], 256, 256, d_w[4], 319, 63, 0, 256, 256, pb[i], d_b[4], 256, 0, 256, w0};
-        else f[n++] = FinalizeJob{pw[i], 256, 256, d_w[L], 256, 0, 0, 256, 256, pb[i], d_b[L], 256, 0, 256, w0};
+        const int L = i + 1;                                                                      // (the skip layer 4: behind its 63 encoding columns)
+        f[n++] = L == 4 ? hid.matrix(i, 256, d_w[4], 319, 63, d_b[4]) : hid.matrix(i, 256, d_w[L], 256, 0, d_b[L]);
     }
-    f[n++] = FinalizeJob{pe4, 256, 64, d_w[4], 319, 0, 0, 256, 63, nullptr, nullptr, 0, 0, 0, w1};
-    f[n++] = FinalizeJob{pe0, 256, 64, d_w[0], 63, 0, 0, 256, 63, pe0_b, d_b[0], 256, 0, 256, w1};
-    f[n++] = FinalizeJob{pg, 160, 256, G, 256, 0, 0, 128, 256, pg_b, d_b[9], 160, 0, 128, w2};            // G and db9 = sum dc
-    f[n++] = FinalizeJob{pg, 160, 256, d_w[8], 256, 0, 131, 1, 256, pg_b, d_b[8], 160, 131, 1, w2};       // opacity_head.0
-    f[n++] = FinalizeJob{phc, 32, 128, d_w[10], 128, 0, 0, 3, 128, nullptr, nullptr, 0, 0, 0, w3};        // rgb_layer.2
-    f[n++] = FinalizeJob{pg, 160, 256, G, 256, 0, 0, 0, 256, pg_b, d_b[10], 160, 128, 3, w2};             // its bias: sum dpre (no matrix rows)
-    f[n++] = FinalizeJob{pcd, 128, 32, d_w[9], 283, 256, 0, 128, 27, nullptr, nullptr, 0, 0, 0, w3};
+    f[n++] = enc.matrix(1, 63, d_w[4], 319, 0, nullptr);                                          // lin_block2.0's encoding columns
+    f[n++] = enc.matrix(0, 63, d_w[0], 63, 0, d_b[0]);                                            // lin_block1.0
+    f[n++] = heads.rows(0, 0, 128, G, 256, d_b[9]);                                               // G and db9 = sum dc
+    f[n++] = heads.rows(0, 131, 1, d_w[8], 256, d_b[8]);                                          // opacity_head.0
+    f[n++] = rgb.rows(0, 0, 3, d_w[10], 128, nullptr);                                            // rgb_layer.2
+    f[n++] = heads.bias_rows(0, 128, 3, d_b[10]);                                                 // its bias: sum dpre
+    f[n++] = dir.matrix(0, 27, d_w[9], 283, 256, nullptr);                                        // rgb_layer.0's direction columns
     if (int e = run_finalize(f, n, st)) return e;
     // bottle_neck.0 and the folded columns of rgb_layer.0 from G (mip_fold_grads_kernel)
     const int total = 128 * 256 + 256 * 256 + 256;
@@ -1699,29 +1745,14 @@ int nk::bwd_mip_weight_grads(int precision, int64_t M, const void* act_dump, con
 }
 
 // ------------------------------------------------------------------------------------------------ Ref-NeRF backward: host side
-namespace {
-struct ChainCtx {                     // addressing of fragment dumps: slot l, K group kg
-    int precision; int64_t M; size_t breg, ls, sub;
-    ChainCtx(int prec, int64_t m) : precision(prec), M(m), breg(prec == NERF_AMD_BF16 ? 1024 : 2048), ls(nk::mlp_train_layer_stride(prec, m)), sub(16 * breg) {}
-    const char* at(const void* dump, int slot, int kg = 0) const { return reinterpret_cast<const char*>(dump) + (size_t)slot * ls + (size_t)kg * breg; }
-    char* at(void* dump, int slot, int kg = 0) const { return reinterpret_cast<char*>(dump) + (size_t)slot * ls + (size_t)kg * breg; }
-};
-int blocks_1d(int64_t work) { int64_t b = (work + 255) / 256; return (int)(b > 4096 ? 4096 : (b < 1 ? 1 : b)); }
-
-}  // namespace
-
 // d density / d position, times scale[m] (RefNeRF.get_grad, ref_model.py:119-125; train.py:165-168,178) for the proposal network
 // (net 0: activation slots 0..3) and Ref-NeRF's spatial network (net 2: slots 0..7): a dgrad-only chain from the density row down to
-// the encoded position, then the encoding's derivative.  workspace: two delta buffers of one slot each + d_enc rows (M, 64) fp32.
-size_t nk::bwd_density_grad_workspace_bytes(int precision, int64_t M) {
-    return align256((size_t)M * 64 * 4) + 256;
-}
+// the encoded position, then the encoding's derivative.  workspace: d_enc rows (M, 64) fp32.
+size_t nk::bwd_density_grad_workspace_bytes(int precision, int64_t M) { return BwdPlan(PLAN_DENSITY, precision, M, nullptr).bytes; }
 int nk::bwd_density_grad(int net, const void* blob, int precision, int64_t M, const void* act, const float* x, int x_stride, const float* scale, int scale_stride,
                      float* out, void* workspace, hipStream_t st, int contract) {
     if (M == 0) return 0;
-    const ChainCtx c(precision, M);
-    Carver ws{reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255)};
-    float* denc = ws.take((size_t)M * 64);
+    float* denc = BwdPlan(PLAN_DENSITY, precision, M, workspace).d_enc;
     if (net == NERF_AMD_NET_PROPOSAL) { if (int e = bwd_launch_chain(3, precision, blob, 0, M, act, nullptr, denc, st)) return e; }
     else if (int e = bwd_launch_chain(2, precision, blob, RefBwdLayout::DEN_START, M, act, nullptr, denc, st)) return e;
     if (contract) hipLaunchKernelGGL(pe_grad_contract_kernel, dim3(blocks_1d(M)), dim3(256), 0, st, denc, 64, x, x_stride, scale, scale_stride, M, 10, out);
@@ -1731,17 +1762,7 @@ int nk::bwd_density_grad(int net, const void* blob, int precision, int64_t M, co
 
 // Ref-NeRF parameter backward (what autograd computes for ref_model.py:68-106 inside train.py:176-199).
 // workspace: delta dump (REF_DUMP_SLOTS slots) | d_allin rows (M,192) | wgrad partials
-size_t nk::bwd_ref_workspace_bytes(int precision, int64_t M) {
-    const int64_t n_sub = bwd_n_sub(precision, M);
-    const size_t w7 = wgrad_workgroups(n_sub, 7, true), w2 = wgrad_workgroups(n_sub, 2, false), w1h = wgrad_workgroups(n_sub, 1, true),
-                 w1 = wgrad_workgroups(n_sub, 1, false);
-    size_t b = align256((size_t)REF_DUMP_SLOTS * mlp_train_layer_stride(precision, M)) + align256((size_t)M * 192 * 4);
-    b += 14 * (align256(w7 * 256 * 256 * 4) + align256(w7 * 256 * 4));                       // 2 x 7 hidden products
-    b += 2 * align256(w2 * 256 * 64 * 4) + align256(w2 * 256 * 4);                           // encoding columns
-    b += 2 * (align256(w2 * 256 * 128 * 4) + align256(w2 * 256 * 4)) + 2 * align256(w2 * 256 * 64 * 4);   // x bottle-neck, x IDE
-    b += align256(w1h * 160 * 256 * 4) + align256(w1h * 160 * 4) + align256(w1 * 32 * 256 * 4) + align256(w1 * 32 * 4);
-    return b + 512;
-}
+size_t nk::bwd_ref_workspace_bytes(int precision, int64_t M) { return BwdPlan(PLAN_REF, precision, M, nullptr).bytes; }
 // w: the 20 tensors of nerf_amd_pack_weights(NET_REF) (only the ide_table, index 19, is read here).  d_w / d_b (20 each): 0..7 spatial,
 // 8 bottle_neck, 9 norm_col_tint_head (9 rows), 10 rho_tau_head (2 rows), 11..18 directional, 19 spec_rgb_head.0
 int nk::bwd_ref_backward(const void* blob, int precision, int64_t M, const void* act, const float* aux, const float* dirs, int dir_stride,
@@ -1749,81 +1770,52 @@ int nk::bwd_ref_backward(const void* blob, int precision, int64_t M, const void*
     if (M == 0) return 0;
     using L = RefBwdLayout;
     const int srgb = (flags & NERF_AMD_REF_SRGB) ? 1 : 0;
-    const ChainCtx c(precision, M);
-    const int64_t n_sub = bwd_n_sub(precision, M);
-    Carver ws{reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255)};
-    char* dlt = reinterpret_cast<char*>(ws.take((size_t)REF_DUMP_SLOTS * c.ls / 4));
-    float* dallin = ws.take((size_t)M * 192);                // (M, 192): the 6 feature blocks of the 167-wide input vector
-    const int elem = precision == NERF_AMD_BF16 ? 2 : 4;
-    auto A = [&](int slot, int kg = 0) { return c.at(act, slot, kg); };
-    auto D = [&](int slot, int kg = 0) { return c.at((void*)dlt, slot, kg); };
+    const BwdPlan plan(PLAN_REF, precision, M, workspace);
+    const ChainCtx& c = plan.c;
+    char* const dlt = plan.dlt;
+    float* const dallin = plan.d_allin;                      // (M, 192): the 6 feature blocks of the 167-wide input vector
+    const bool bf = precision == NERF_AMD_BF16;              // (element size of the delta slots the two element-wise kernels write)
     // slot 8 of the delta dump: K groups 0..7 delta of the bottle-neck, 8 the head rows, 9 the spec head -- each written COMPLETELY by the two
     // element-wise kernels below (unused features and the padding samples up to the tile boundary as zeros): no memset
-    const int64_t Mpad = (int64_t)(c.ls / c.sub) * 32;
+    const int64_t Mpad = plan.n_sub * 32;
+    const dim3 grid(blocks_1d(Mpad)), block(256);
     // stage 1: spec head delta, then the directional network backwards
-    if (elem == 2) hipLaunchKernelGGL(ref_spec_delta_kernel<2>, dim3(blocks_1d(Mpad)), dim3(256), 0, st, g_out, g_stride, aux, M, Mpad, D(8, 9), (unsigned long long)c.sub, srgb);
-    else hipLaunchKernelGGL(ref_spec_delta_kernel<4>, dim3(blocks_1d(Mpad)), dim3(256), 0, st, g_out, g_stride, aux, M, Mpad, D(8, 9), (unsigned long long)c.sub, srgb);
+    hipLaunchKernelGGL(bf ? ref_spec_delta_kernel<2> : ref_spec_delta_kernel<4>, grid, block, 0, st, g_out, g_stride, aux, M, Mpad, c.at((void*)dlt, 8, 9),
+                       (unsigned long long)c.sub, srgb);
     if (int e = bwd_launch_chain(0, precision, blob, L::DIR_START, M, act, dlt, dallin, st)) return e;                            // D7 .. D0 + the input-vector columns
     // stage 2: IDE / reflection / normal / head activations backwards -> delta of the heads and of the bottle-neck
-    if (elem == 2) hipLaunchKernelGGL(ref_heads_delta_kernel<2>, dim3(blocks_1d(Mpad)), dim3(256), 0, st, g_out, g_stride, aux, dallin, 192, dirs, dir_stride, ide_table, M, Mpad,
-                                      D(8), (unsigned long long)c.sub, srgb);
-    else hipLaunchKernelGGL(ref_heads_delta_kernel<4>, dim3(blocks_1d(Mpad)), dim3(256), 0, st, g_out, g_stride, aux, dallin, 192, dirs, dir_stride, ide_table, M, Mpad, D(8),
-                            (unsigned long long)c.sub, srgb);
+    hipLaunchKernelGGL(bf ? ref_heads_delta_kernel<2> : ref_heads_delta_kernel<4>, grid, block, 0, st, g_out, g_stride, aux, dallin, 192, dirs, dir_stride, ide_table, M,
+                       Mpad, c.at((void*)dlt, 8), (unsigned long long)c.sub, srgb);
     // stage 3: the spatial network backwards
     if (int e = bwd_launch_chain(1, precision, blob, L::SPA_START, M, act, dlt, nullptr, st)) return e;                           // S7 .. S0
     // weight gradients
-    const int w7 = wgrad_workgroups(n_sub, 7, true), w2 = wgrad_workgroups(n_sub, 2, false), w1h = wgrad_workgroups(n_sub, 1, true),
-              w1 = wgrad_workgroups(n_sub, 1, false);
-    float *pS[7], *pSb[7], *pD[7], *pDb[7];
-    for (int i = 0; i < 7; ++i) { pS[i] = ws.take((size_t)w7 * 65536); pSb[i] = ws.take((size_t)w7 * 256); }
-    for (int i = 0; i < 7; ++i) { pD[i] = ws.take((size_t)w7 * 65536); pDb[i] = ws.take((size_t)w7 * 256); }
-    float* pe0 = ws.take((size_t)w2 * 256 * 64); float* pe4 = ws.take((size_t)w2 * 256 * 64); float* pe0b = ws.take((size_t)w2 * 256);
-    float *pb0 = ws.take((size_t)w2 * 256 * 128), *pb0b = ws.take((size_t)w2 * 256), *pb4 = ws.take((size_t)w2 * 256 * 128), *pb4b = ws.take((size_t)w2 * 256);
-    float *pi0 = ws.take((size_t)w2 * 256 * 64), *pi4 = ws.take((size_t)w2 * 256 * 64);
-    float *ph = ws.take((size_t)w1h * 160 * 256), *phb = ws.take((size_t)w1h * 160), *psp = ws.take((size_t)w1 * 32 * 256), *pspb = ws.take((size_t)w1 * 32);
-    const int SL[7] = {1, 2, 3, 4, 5, 6, 7};                 // spatial layer l: delta slot l x activation slot l-1 (layer 4: its hidden columns)
-    Product pj[7];
-    for (int i = 0; i < 7; ++i) pj[i] = Product{D(SL[i]), 16, nullptr, A(SL[i] - 1), pS[i], pSb[i]};
-    if (int e = run_wgrad(0, precision, pj, 7, w7, n_sub, st)) return e;
-    for (int i = 0; i < 7; ++i) pj[i] = Product{D(9 + SL[i]), 16, nullptr, A(9 + SL[i] - 1), pD[i], pDb[i]};                  // directional layers 1..7
-    if (int e = run_wgrad(0, precision, pj, 7, w7, n_sub, st)) return e;
-    const Product pe[2] = {Product{D(0), 16, nullptr, A(8, 11), pe0, pe0b}, Product{D(4), 16, nullptr, A(8, 11), pe4, nullptr}};
-    if (int e = run_wgrad(1, precision, pe, 2, w2, n_sub, st)) return e;
-    const Product pb[2] = {Product{D(9), 16, nullptr, A(8, 0), pb0, pb0b}, Product{D(13), 16, nullptr, A(8, 0), pb4, pb4b}};  // x bottle-neck
-    if (int e = run_wgrad(6, precision, pb, 2, w2, n_sub, st)) return e;
-    const Product pi[2] = {Product{D(9), 16, nullptr, A(8, 8), pi0, nullptr}, Product{D(13), 16, nullptr, A(8, 8), pi4, nullptr}};   // x [IDE | n.d]
-    if (int e = run_wgrad(7, precision, pi, 2, w2, n_sub, st)) return e;
-    const Product phd{D(8), 9, nullptr, A(7), ph, phb};                                                                      // [bottle-neck | heads]^T S7
-    if (int e = run_wgrad(2, precision, &phd, 1, w1h, n_sub, st)) return e;
-    const Product pspec{D(8, 9), 1, nullptr, A(16), psp, pspb};                                                              // spec head
-    if (int e = run_wgrad(5, precision, &pspec, 1, w1, n_sub, st)) return e;
-    FinalizeJob f[40];
+    if (int e = plan.run_products(act, dlt, st)) return e;
+    const Batch &spa = plan.b[0], &dir = plan.b[1], &enc = plan.b[2], &bottle = plan.b[3], &ide = plan.b[4], &heads = plan.b[5], &spec = plan.b[6];
+    FinalizeJob f[20];
     int n = 0;
-    for (int i = 0; i < 7; ++i) {                            // spatial
-        const int l = SL[i];
-        if (l == 4) f[n++] = FinalizeJob{pS[i], 256, 256, d_w[4], 319, 63, 0, 256, 256, pSb[i], d_b[4], 256, 0, 256, w7};
-        else f[n++] = FinalizeJob{pS[i], 256, 256, d_w[l], 256, 0, 0, 256, 256, pSb[i], d_b[l], 256, 0, 256, w7};
+    for (int i = 0; i < 7; ++i) {                            // spatial layers 1..7
+        const int l = i + 1;
+        f[n++] = l == 4 ? spa.matrix(i, 256, d_w[4], 319, 63, d_b[4]) : spa.matrix(i, 256, d_w[l], 256, 0, d_b[l]);
     }
-    f[n++] = FinalizeJob{pe0, 256, 64, d_w[0], 63, 0, 0, 256, 63, pe0b, d_b[0], 256, 0, 256, w2};
-    f[n++] = FinalizeJob{pe4, 256, 64, d_w[4], 319, 0, 0, 256, 63, nullptr, nullptr, 0, 0, 0, w2};
+    f[n++] = enc.matrix(0, 63, d_w[0], 63, 0, d_b[0]);
+    f[n++] = enc.matrix(1, 63, d_w[4], 319, 0, nullptr);
     for (int i = 0; i < 7; ++i) {                            // directional: tensors 11..18 = dir layers 0..7
-        const int l = SL[i];
-        if (l == 4) f[n++] = FinalizeJob{pD[i], 256, 256, d_w[15], 423, 167, 0, 256, 256, pDb[i], d_b[15], 256, 0, 256, w7};
-        else f[n++] = FinalizeJob{pD[i], 256, 256, d_w[11 + l], 256, 0, 0, 256, 256, pDb[i], d_b[11 + l], 256, 0, 256, w7};
+        const int l = i + 1;
+        f[n++] = l == 4 ? dir.matrix(i, 256, d_w[15], 423, 167, d_b[15]) : dir.matrix(i, 256, d_w[11 + l], 256, 0, d_b[11 + l]);
     }
-    f[n++] = FinalizeJob{pb0, 256, 128, d_w[11], 167, 0, 0, 256, 128, pb0b, d_b[11], 256, 0, 256, w2};
-    f[n++] = FinalizeJob{pi0, 256, 64, d_w[11], 167, 128, 0, 256, 39, nullptr, nullptr, 0, 0, 0, w2};
-    f[n++] = FinalizeJob{pb4, 256, 128, d_w[15], 423, 0, 0, 256, 128, nullptr, nullptr, 0, 0, 0, w2};
-    f[n++] = FinalizeJob{pi4, 256, 64, d_w[15], 423, 128, 0, 256, 39, nullptr, nullptr, 0, 0, 0, w2};
+    f[n++] = bottle.matrix(0, 128, d_w[11], 167, 0, d_b[11]);                 // dir layer 0 = [bottle-neck 128 | IDE 38, n.d]
+    f[n++] = ide.matrix(0, 39, d_w[11], 167, 128, nullptr);
+    f[n++] = bottle.matrix(1, 128, d_w[15], 423, 0, nullptr);                 // dir layer 4: the same columns in front of its hidden ones
+    f[n++] = ide.matrix(1, 39, d_w[15], 423, 128, nullptr);
     if (int e = run_finalize(f, n, st)) return e;
     n = 0;
-    f[n++] = FinalizeJob{ph, 160, 256, d_w[8], 256, 0, 0, 128, 256, phb, d_b[8], 160, 0, 128, w1h};                          // bottle_neck
-    f[n++] = FinalizeJob{ph, 160, 256, d_w[9], 256, 0, 128, 3, 256, phb, d_b[9], 160, 128, 3, w1h};                          // norm_col_tint rows 0-2 (normal)
-    f[n++] = FinalizeJob{ph, 160, 256, d_w[9] + 3 * 256, 256, 0, 132, 3, 256, phb, d_b[9] + 3, 160, 132, 3, w1h};            //   rows 3-5 (diffuse)
-    f[n++] = FinalizeJob{ph, 160, 256, d_w[9] + 6 * 256, 256, 0, 136, 3, 256, phb, d_b[9] + 6, 160, 136, 3, w1h};            //   rows 6-8 (tint)
-    f[n++] = FinalizeJob{ph, 160, 256, d_w[10], 256, 0, 131, 1, 256, phb, d_b[10], 160, 131, 1, w1h};                        // rho_tau row 0 (roughness)
-    f[n++] = FinalizeJob{ph, 160, 256, d_w[10] + 256, 256, 0, 135, 1, 256, phb, d_b[10] + 1, 160, 135, 1, w1h};              //   row 1 (density)
-    f[n++] = FinalizeJob{psp, 32, 256, d_w[19], 256, 0, 0, 3, 256, pspb, d_b[19], 32, 0, 3, w1};                             // spec_rgb_head.0
+    f[n++] = heads.rows(0, 0, 128, d_w[8], 256, d_b[8]);                      // bottle_neck
+    f[n++] = heads.rows(0, 128, 3, d_w[9], 256, d_b[9]);                      // norm_col_tint rows 0-2 (normal)
+    f[n++] = heads.rows(0, 132, 3, d_w[9] + 3 * 256, 256, d_b[9] + 3);        //   rows 3-5 (diffuse)
+    f[n++] = heads.rows(0, 136, 3, d_w[9] + 6 * 256, 256, d_b[9] + 6);        //   rows 6-8 (tint)
+    f[n++] = heads.rows(0, 131, 1, d_w[10], 256, d_b[10]);                    // rho_tau row 0 (roughness)
+    f[n++] = heads.rows(0, 135, 1, d_w[10] + 256, 256, d_b[10] + 1);          //   row 1 (density)
+    f[n++] = spec.rows(0, 0, 3, d_w[19], 256, d_b[19]);                       // spec_rgb_head.0
     return run_finalize(f, n, st);
 }
 

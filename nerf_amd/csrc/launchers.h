@@ -12,6 +12,7 @@ int mlp_launch_dir_table(const float* rays, int64_t N, void* table, hipStream_t 
 int mlp_launch_mip128(const void* packed, int precision, const nerf_amd_samples& s, float* rgbo, hipStream_t st);
 int mlp_launch_mip_composite(const void* packed, int precision, const nerf_amd_samples& s, float* rgb, float* depth, float* weights, int white_bkg, float near, float far, hipStream_t st);
 int mlp_launch_proposal128(const void* packed, int precision, const nerf_amd_samples& s, float* density, hipStream_t st);
+int64_t mlp_train_n_sub(int precision, int64_t M);
 size_t mlp_train_layer_stride(int precision, int64_t M);
 size_t mlp_train_mask_stride(int precision, int64_t M);
 int mlp_launch_proposal_train(const void* packed, int precision, const nerf_amd_samples& s, float* density, void* dump, hipStream_t st);

@@ -1521,13 +1521,15 @@ int nk::mlp_launch_proposal128(const void* packed, int precision, const nerf_amd
     return launch_proposal128<PF32>(packed, s, density, st);
 }
 // training forwards: the same kernels, also dumping the hidden activations (ActDump) for the backward
-size_t nk::mlp_train_layer_stride(int precision, int64_t M) {
+// 32-sample subtiles of a dump slot: up to the end of the last tile of the training kernels (the dgrad chains and the weight-gradient
+// products walk the same subtiles)
+int64_t nk::mlp_train_n_sub(int precision, int64_t M) {
     const int64_t ts = (precision != NERF_AMD_F32) ? (int64_t)PB16::NW * PB16::NT * 32 : (int64_t)PF32::NW * PF32::NT * 32;   // (BF16_F8 slots keep the bf16 footprint)
-    const int64_t n_sub = ((M + ts - 1) / ts) * (ts / 32);
-    return (size_t)n_sub * 16 * (precision != NERF_AMD_F32 ? 1024 : 2048);
+    return ((M + ts - 1) / ts) * (ts / 32);
 }
+size_t nk::mlp_train_layer_stride(int precision, int64_t M) { return (size_t)mlp_train_n_sub(precision, M) * 16 * (precision != NERF_AMD_F32 ? 1024 : 2048); }
 // the ReLU bit masks sit behind the `slots` activation slots of a dump: 1 KiB per slot and subtile
-size_t nk::mlp_train_mask_stride(int precision, int64_t M) { return mlp_train_layer_stride(precision, M) / (16 * (precision != NERF_AMD_F32 ? 1024 : 2048)) * 1024; }
+size_t nk::mlp_train_mask_stride(int precision, int64_t M) { return (size_t)mlp_train_n_sub(precision, M) * 1024; }
 int nk::mlp_launch_proposal_train(const void* packed, int precision, const nerf_amd_samples& s, float* density, void* dump, hipStream_t st) {
     if (precision == NERF_AMD_BF16_F8) {                    // bf16 arithmetic, hidden slots of the dump in scaled e4m3 (mlp_layout.h)
         const ActDump d8 = make_dump(dump, NERF_AMD_BF16, s.M, PROP_DUMP_SLOTS);

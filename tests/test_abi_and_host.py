@@ -457,6 +457,82 @@ def test_render_workspace_sizes_are_the_documented_closed_forms():
     assert n_checked == 72 + 144 and sum(len(t) for t in table.values()) == 72 + 144
 
 
+# the closed forms of the training backward's workspaces, as bwd_kernels.hip typed them by hand before each workspace was described once.
+# Launch geometry: 32-sample subtiles up to the end of the last tile (256 samples in bf16, 128 in fp32); a batch of `jobs` products gets
+# cu / jobs workgroups per product for the big-accumulator shapes (heavy) and 2 cu / jobs for the others, at most one per subtile, at least 1.
+def _bwd_n_sub(bf16, M):
+    ts = 256 if bf16 else 128
+    return (M + ts - 1) // ts * (ts // 32)
+
+
+def _bwd_wg(n_sub, jobs, heavy, cu):
+    return max(1, min(cu * (1 if heavy else 2) // jobs, n_sub))
+
+
+def _bwd_prop_form(bf16, M, cu):
+    n = _bwd_n_sub(bf16, M)
+    w0, w1 = _bwd_wg(n, 3, True, cu), _bwd_wg(n, 1, False, cu)
+    return (3 * (_ws256(w0 * 256 * 256 * 4) + _ws256(w0 * 256 * 4)) + _ws256(w1 * 256 * 64 * 4) + _ws256(w1 * 256 * 4)
+            + _ws256(w1 * 32 * 256 * 4) + _ws256(w1 * 32 * 4) + 256)
+
+
+def _bwd_mip_form(bf16, M, cu):
+    n = _bwd_n_sub(bf16, M)
+    w0, w1, w2, w3 = _bwd_wg(n, 6, True, cu), _bwd_wg(n, 2, False, cu), _bwd_wg(n, 1, True, cu), _bwd_wg(n, 1, False, cu)
+    return (6 * (_ws256(w0 * 256 * 256 * 4) + _ws256(w0 * 256 * 4)) + 2 * _ws256(w1 * 256 * 64 * 4) + _ws256(w1 * 256 * 4)
+            + _ws256(w2 * 160 * 256 * 4) + _ws256(w2 * 160 * 4) + _ws256(w3 * 32 * 128 * 4) + _ws256(w3 * 128 * 32 * 4)
+            + _ws256(128 * 256 * 4) + 256)
+
+
+def _bwd_ref_form(bf16, M, cu):
+    n = _bwd_n_sub(bf16, M)
+    w7, w2, w1h, w1 = _bwd_wg(n, 7, True, cu), _bwd_wg(n, 2, False, cu), _bwd_wg(n, 1, True, cu), _bwd_wg(n, 1, False, cu)
+    b = _ws256(17 * n * 16 * (1024 if bf16 else 2048)) + _ws256(M * 192 * 4)          # delta dump (17 slots) | d_allin (M, 192)
+    b += 14 * (_ws256(w7 * 256 * 256 * 4) + _ws256(w7 * 256 * 4))                      # 2 x 7 hidden products
+    b += 2 * _ws256(w2 * 256 * 64 * 4) + _ws256(w2 * 256 * 4)                          # encoding columns
+    b += 2 * (_ws256(w2 * 256 * 128 * 4) + _ws256(w2 * 256 * 4)) + 2 * _ws256(w2 * 256 * 64 * 4)   # x bottle-neck, x IDE
+    b += _ws256(w1h * 160 * 256 * 4) + _ws256(w1h * 160 * 4) + _ws256(w1 * 32 * 256 * 4) + _ws256(w1 * 32 * 4)
+    return b + 512
+
+
+def test_backward_workspace_sizes_are_the_documented_closed_forms():
+    """nerf_amd_weight_grads_workspace_bytes, nerf_amd_ref_backward_workspace_bytes and nerf_amd_density_grad_workspace_bytes against the
+    closed forms above AND against the table recorded from the build that still typed them by hand (tests/golden/
+    backward_workspace_bytes.json, for 256 compute units: the MI355X's count and what the library assumes without a GPU): byte for byte,
+    the + 256 / + 512 alignment slack, the non-zero sizes of an empty batch and the 0 of every refused combination included."""
+    import json
+    from nerf_amd import _lib
+    cu = 256
+    if torch.cuda.is_available():                                                      # (another device: the closed forms alone)
+        n_cu, is950 = ctypes.c_int(0), ctypes.c_int(0)
+        assert _lib.lib.nerf_amd_device_info(ctypes.byref(n_cu), ctypes.byref(is950)) == 0
+        cu = int(n_cu.value)
+    table = json.load(open(os.path.join(ROOT, "tests", "golden", "backward_workspace_bytes.json")))
+    assert "256 compute units" in table.pop("_header")
+    recorded = (lambda name, key, want: table[name][key] == want) if cu == 256 else (lambda name, key, want: True)
+    nets = (("PROPOSAL", _lib.NET_PROPOSAL), ("MIP", _lib.NET_MIP), ("REF", _lib.NET_REF))
+    precisions = (("F32", _lib.F32), ("BF16", _lib.BF16), ("BF16_F8", _lib.BF16_F8))
+    n_checked = 0
+    for p, pc in precisions:
+        bf16, f8 = pc != _lib.F32, pc == _lib.BF16_F8
+        for M in (-1, 0, 1, 32, 33, 2048, 2049, 4097, 16384, 65537, 1048576):
+            want = 0 if M < 0 or f8 else _bwd_ref_form(bf16, M, cu)                        # (no fp8 dumps for Ref-NeRF)
+            assert recorded("nerf_amd_ref_backward_workspace_bytes", "%s,%d" % (p, M), want), (p, M)
+            assert _lib.lib.nerf_amd_ref_backward_workspace_bytes(pc, M) == want, (p, M)
+            n_checked += 1
+            for n, nc in nets:
+                # products only: Ref-NeRF's lie in the workspace of nerf_amd_ref_backward
+                want = 0 if M < 0 or n == "REF" else (_bwd_prop_form if n == "PROPOSAL" else _bwd_mip_form)(bf16, M, cu)
+                assert recorded("nerf_amd_weight_grads_workspace_bytes", "%s,%s,%d" % (n, p, M), want), (n, p, M)
+                assert _lib.lib.nerf_amd_weight_grads_workspace_bytes(nc, pc, M) == want, (n, p, M)
+                # d_enc (M, 64) + slack; density gradients exist for the proposal and Ref-NeRF networks, without fp8 dumps
+                want = 0 if M < 0 or n == "MIP" or f8 else _ws256(M * 64 * 4) + 256
+                assert recorded("nerf_amd_density_grad_workspace_bytes", "%s,%s,%d" % (n, p, M), want), (n, p, M)
+                assert _lib.lib.nerf_amd_density_grad_workspace_bytes(nc, pc, M) == want, (n, p, M)
+                n_checked += 2
+    assert n_checked == 33 + 99 + 99 and sum(len(t) for t in table.values()) == 33 + 99 + 99
+
+
 def test_shapes_whose_launch_exceeds_the_lds_are_refused_before_any_hip_call():
     """A shape is accepted only if the dynamic LDS of the launch it leads to fits the 64 KiB a kernel gets without an opt-in: four rays
     per workgroup x the kernel's per-ray rows.  nerf_amd_resample holds 5 C + 2 K + 1280 floats per ray (5 C + 2 K <= 2816),

@@ -93,14 +93,16 @@ def _g_out(M, seed):
     return torch.randn(M, 7, generator=torch.Generator().manual_seed(seed)).cuda()
 
 
-def _backward(A, net, prec, dump, aux, dirs, g_out, flags, fill=0x00):
-    """nerf_amd_ref_backward on storage of this test -> (workspace, {name: gradient})"""
+def _backward(A, net, prec, dump, aux, dirs, g_out, flags, fill=0x00, ws=None):
+    """nerf_amd_ref_backward on storage of this test (`ws`: a caller's workspace, at any alignment) -> (workspace, {name: gradient})"""
     ops, P = A.ops, _code(A, prec)
     M = g_out.shape[0]
     need = A.lib.nerf_amd_ref_backward_workspace_bytes(P, M)
     assert RB.partials_offset(prec, M) < need                     # the delta dump and d_allin lie where ref_backward_ref reads them
-    ws = _filled(need, fill)
-    assert ws.data_ptr() % 256 == 0
+    if ws is None:
+        ws = _filled(need, fill)
+        assert ws.data_ptr() % 256 == 0
+    assert ws.numel() == need
     shapes = ops.REF_GRAD_SHAPES
     gw = [_filled(4 * s[0] * s[1], fill).view(torch.float32).view(s) for s in shapes]
     gb = [_filled(4 * s[0], fill).view(torch.float32) for s in shapes]
