@@ -628,8 +628,9 @@ int nerf_amd_ray_depth_stats(const float* weights, const float* z, int z_stride,
                              float* depth_q, void* stream);
 
 /* (added after ABI 125; additive) The four render entry points above behind ONE request: the same pipeline, the same launches, plus
- * optional outputs they have no argument for.  `size` = sizeof(nerf_amd_render_request) of the caller's header (a smaller one is refused:
- * this is the first layout); zero-fill the struct, then set what the call uses.
+ * optional outputs they have no argument for.  `size` = sizeof(nerf_amd_render_request) of the caller's header (the first layout's 200 bytes --
+ * everything up to fine_depths -- are accepted too, with the later fields off; anything smaller is refused); zero-fill the struct, then
+ * set what the call uses.
  *   which entry point:  ref != 0 -> nerf_amd_render_rays_ref;  else prop_pnum != 0 -> nerf_amd_render_rays_rounds (in-kernel uniforms only);
  *                       else spacing == NERF_AMD_SPACING_DISPARITY -> nerf_amd_render_rays_warped;  else nerf_amd_render_rays.
  *   Every field means what the argument of that name means there (`normal_img` / `cam_dir` / `ref_flags` are read for Ref-NeRF only;
@@ -674,9 +675,58 @@ typedef struct nerf_amd_render_request {
     float* opacity;                    /* (N) or NULL */
     float* depth_q;                    /* (N, n_quantiles) or NULL */
     float* fine_depths;                /* (N, E) or NULL */
+    /* -- end of the first layout (200 bytes); a `size` of exactly that is accepted and leaves everything below off -- */
+    double skip_min_optical_depth;     /* D_min of the empty-ray skip (below); <= 0: off */
+    int32_t* row_of_ray;               /* (N) device output or NULL: the compact row of each ray, -1 = skipped (skip on only) */
+    int64_t* n_alive;                  /* HOST output or NULL: the number of rays the fine network ran on (skip on only) */
 } nerf_amd_render_request;
 size_t nerf_amd_render_request_workspace_bytes(const nerf_amd_render_request* request);
 int    nerf_amd_render(const nerf_amd_render_request* request, void* workspace, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * (added after ABI 125; additive) Skip the fine pass for rays the proposal histogram leaves empty.  Opt-in; not in the reference: the
+ * build's own definition, restated in fp64 by tests/skip_empty_ref.py.  Per ray, with the raw proposal densities sigma_0 .. sigma_{C-1}
+ * (fp32), their ascending metric depths z_0 .. z_{C-1} (fp32) and the direction d, everything in fp64 from those fp32 values:
+ *
+ *     D     = |d| * sum_{s < C-1} max(sigma_s, 0) * (z_{s+1} - z_s)  +  max(sigma_{C-1}, 0) * 1e10        |d| = sqrt(dx^2 + dy^2 + dz^2)
+ *     alive = !(D < D_min)
+ *
+ * the optical depth of ProposalNetwork.get_weights (addtional.py:103-104: the last delta is 1e10 and is not scaled by |d|).  max keeps a
+ * NaN, so a NaN density keeps the ray alive and it renders as the dense path would; any positive density at the far sample keeps it alive
+ * too (it makes the ray opaque in the reference's own weights).  The user-facing threshold is an opacity tau in (0, 1):
+ * D_min = -log1p(-tau), computed by the caller in double.  fp64 summation order is not specified: a ray with |D - D_min| <= 1e-9 max(D,
+ * D_min) may fall either way.
+ *
+ * nerf_amd_ray_alive: density (N,C) contiguous, z rows of z_stride >= C floats, dirs rows of dirs_stride >= 3 floats ->
+ *   row_of_ray (N) int32: the rank of ray n among the alive rays, -1 for a dead one;  ray_of_row (>= N' entries are written, N' <= N)
+ *   int64: the inverse list, ascending;  count_dev: one int64 ON THE DEVICE = N'.  Alive rays keep their order: the tables are a pure
+ *   function of the inputs (ballot + popcount per wave, a two-level scan of 256-ray tiles; no atomics).  Four launches; workspace of
+ *   nerf_amd_ray_alive_workspace_bytes(N) bytes.  Refused before the first launch: NULL arguments (N > 0), N < 0 or N >= 2^31, C < 2,
+ *   z_stride < C, dirs_stride < 3, a NaN min_optical_depth.  N == 0 is fine (*count_dev = 0).
+ * nerf_amd_gather_rows: dst (n_rows, cols) contiguous = rows ray_of_row[0 .. n_rows) of src (row stride src_stride >= cols floats).
+ *
+ * In nerf_amd_render (skip_min_optical_depth > 0) the stage runs after the last resampling (Ref-NeRF: after the depth merge), on the
+ * histogram the fine depths were drawn from -- one round: the proposal densities at the 64 coarse depths (linear spacing: the resampling
+ * kernel also stores the depths it drew, through the z_coarse output it has for Ref-NeRF; disparity: the metric row z_c); two rounds: the
+ * second pass's densities at z_mid; Ref-NeRF: the densities at z_coarse -- then: N' is read back to the host (one hipMemcpyAsync + one
+ * hipStreamSynchronize), the alive rays' ray records and fine depth rows are gathered into compact tables, the fine network runs on N'
+ * rays (none is launched for N' = 0) and writes compact rows, and compositing reads ray n's row at row_of_ray[n], an ALL-ZERO row for a
+ * dead ray; depths, weights and every output stay (N, ...) and are indexed by the ray.  So every output equals the dense call's with the
+ * fine network's rows of the dead rays replaced by zeros, bit for bit: an alive ray is the dense ray; a dead MipNeRF ray is
+ * nerf_amd_composite of zero density on its own depth row -- background colour, zero weights, opacity 0, the far edge as quantile depth;
+ * with D_min so small that every ray is alive the call is the dense call.  (Ref-NeRF composites softplus(sigma + 0.5): a zero row is
+ * NOT zero density there -- a dead Ref-NeRF ray is the composite of that constant density with zero colour.)  This is an approximation
+ * of the image: its error is the fine opacity of the rays the proposal network calls empty.  The integrated PE keeps the direction norm
+ * of the whole ray list.  The call reads a count on the host: it is NOT capturable and is refused with NERF_AMD_EUNSUPPORTED on a
+ * capturing stream.  The skip's workspace parts (tables, flags, the compact ray and depth tables, the stored coarse depths) are appended
+ * behind everything else: only nerf_amd_render_request_workspace_bytes grows; the four argument-list entry points cannot carry the skip.
+ * ------------------------------------------------------------------------------------------------ */
+size_t nerf_amd_ray_alive_workspace_bytes(int64_t N);
+int    nerf_amd_ray_alive(const float* density, const float* z, int z_stride, const float* dirs, int dirs_stride, int64_t N, int C,
+                          double min_optical_depth, int32_t* row_of_ray, int64_t* ray_of_row, int64_t* count_dev, void* workspace,
+                          void* stream);
+int    nerf_amd_gather_rows(const float* src, int64_t src_stride, const int64_t* ray_of_row, int64_t n_rows, int cols, float* dst,
+                            void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Generic-shape layer product (ABI 119): the path of networks LARGER than the shapes the fused MLP kernels are compiled for -- hidden

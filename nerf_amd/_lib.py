@@ -45,7 +45,9 @@ class RenderRequest(C.Structure):
                 ("z_base", c_void), ("u_strat", c_void), ("u_inv", c_void), ("N", C.c_int64), ("n_fine", C.c_int32), ("prop_pnum", C.c_int32),
                 ("spacing", C.c_int32), ("near", C.c_float), ("far", C.c_float), ("n_quantiles", C.c_int32),
                 ("quantiles", C.c_float * DEPTH_QUANTILES_MAX), ("cam_dir", c_void), ("rgb", c_void), ("depth", c_void), ("weights", c_void),
-                ("normal_img", c_void), ("opacity", c_void), ("depth_q", c_void), ("fine_depths", c_void)]
+                ("normal_img", c_void), ("opacity", c_void), ("depth_q", c_void), ("fine_depths", c_void),
+                # appended behind the first layout (200 bytes, which the library still accepts): the empty-ray skip
+                ("skip_min_optical_depth", C.c_double), ("row_of_ray", c_void), ("n_alive", C.POINTER(C.c_int64))]
 
     def __init__(self, **fields):
         super().__init__(**fields)
@@ -158,6 +160,9 @@ SIGNATURES = {
                                           c_void, c_void, c_void]),
     "nerf_amd_render_request_workspace_bytes": (C.c_size_t, [C.POINTER(RenderRequest)]),
     "nerf_amd_render": (C.c_int, [C.POINTER(RenderRequest), c_void, c_void]),
+    "nerf_amd_ray_alive_workspace_bytes": (C.c_size_t, [i64]),
+    "nerf_amd_ray_alive": (C.c_int, [c_void, c_void, C.c_int, c_void, C.c_int, i64, C.c_int, C.c_double, c_void, c_void, c_void, c_void, c_void]),
+    "nerf_amd_gather_rows": (C.c_int, [c_void, i64, c_void, i64, C.c_int, c_void, c_void]),
     "nerf_amd_gemm_workspace_bytes": (C.c_size_t, [i64, i64, i64]),
     "nerf_amd_gemm": (C.c_int, [C.c_int, i64, i64, i64, c_void, i64, i64, c_void, i64, i64, c_void, i64, c_void, C.c_int, c_void, i64, c_void, c_void]),
     "nerf_amd_sigmoid_backward": (C.c_int, [c_void, i64, c_void, i64, i64, C.c_int, c_void, i64, c_void]),
@@ -175,7 +180,8 @@ SIGNATURES = {
 
 # additive entry points that a library named by NERF_AMD_LIB may predate
 ADDED_AFTER_125 = ("nerf_amd_direction_table", "nerf_amd_render_rounds_workspace_bytes", "nerf_amd_render_rays_rounds",
-                   "nerf_amd_ipe_feature_gaussian", "nerf_amd_ray_depth_stats", "nerf_amd_render_request_workspace_bytes", "nerf_amd_render")
+                   "nerf_amd_ipe_feature_gaussian", "nerf_amd_ray_depth_stats", "nerf_amd_render_request_workspace_bytes", "nerf_amd_render",
+                   "nerf_amd_ray_alive_workspace_bytes", "nerf_amd_ray_alive", "nerf_amd_gather_rows")
 
 
 def _load():

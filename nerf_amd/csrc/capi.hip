@@ -1,5 +1,6 @@
 // extern "C" boundary of libnerf_amd.so (declared in include/nerf_amd.h).
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdio.h>
 #include <string.h>
 
@@ -735,6 +736,13 @@ struct RenderPlan {
     float *opacity = nullptr, *depth_q = nullptr, *fine_depths = nullptr;
     float quantiles[NERF_AMD_DEPTH_QUANTILES_MAX] = {0.0f, 0.0f, 0.0f, 0.0f};
     int n_quantiles = 0;
+    // nerf_amd_render only: the empty-ray skip (include/nerf_amd.h); off unless skip_dmin > 0
+    double skip_dmin = 0.0;
+    int32_t* row_of_ray = nullptr;
+    int64_t* n_alive = nullptr;
+    bool skip() const { return skip_dmin > 0.0; }
+    bool skip_stores_coarse() const { return skip() && !ref && !warped && !prop_pnum; }     // the one route whose coarse depths exist in no buffer
+    int fine_row() const { return fine_samples() + (ref ? 0 : 1); }        // floats of the depth row the fine pass reads: z_fine, Ref-NeRF z_all
     bool want_stats() const { return opacity || (depth_q && n_quantiles); }
     int fine_samples() const { return n_fine + (ref ? RENDER_C : 0); }      // samples per ray of the fine pass
     bool ipe() const { return !ref && camera && camera->ipe; }
@@ -744,21 +752,42 @@ struct RenderPlan {
 };
 // What nerf_amd_render appends BEHIND the entry point's workspace (whose layout and size query stay): the weights the stats kernel reads
 // when the caller takes none, and the raw quantile depths that the un-warp reads under disparity spacing; each rounded up to 256 bytes.
+// Behind those, with the empty-ray skip on: row_of_ray (N) int32 | ray_of_row (N) int64 | the device count | flags and tile counts
+// (sk_ray_alive_workspace_bytes) | the compact ray table (N,6) | the compact fine depth rows (N, fine_row) [| the coarse depths (N,64) of
+// the linear one-round route, which has them in no other buffer].
 struct RenderExtrasWs {
     float *weights = nullptr, *depth_q_raw = nullptr;
+    int32_t* row_of_ray = nullptr;
+    int64_t *ray_of_row = nullptr, *count = nullptr;
+    void* alive_ws = nullptr;
+    float *rays_c = nullptr, *z_rows_c = nullptr, *z_coarse = nullptr;
     size_t bytes;                                           // of the whole workspace, the entry point's part included
     RenderExtrasWs(const RenderPlan& p, void* base) {
         const RenderWs ws = p.ws(base);
         const size_t n = (size_t)p.N;
-        const size_t w_part = (p.want_stats() && !p.weights) ? ((n * p.fine_samples() * 4 + 255) & ~(size_t)255) : 0;
-        const size_t q_part = (p.warped && p.depth_q && p.n_quantiles) ? ((n * p.n_quantiles * 4 + 255) & ~(size_t)255) : 0;
+        auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+        const bool skip = p.skip();
+        const size_t parts[9] = {(p.want_stats() && !p.weights) ? up(n * p.fine_samples() * 4) : 0,
+                                 (p.warped && p.depth_q && p.n_quantiles) ? up(n * p.n_quantiles * 4) : 0,
+                                 skip ? up(n * 4) : 0, skip ? up(n * 8) : 0, skip ? (size_t)256 : 0, skip ? up(sk_ray_alive_workspace_bytes(p.N)) : 0,
+                                 skip ? up(n * 24) : 0, skip ? up(n * p.fine_row() * 4) : 0, p.skip_stores_coarse() ? up(n * RENDER_C * 4) : 0};
+        size_t sum = 0;
+        for (size_t part : parts) sum += part;
         bytes = ws.bytes;
-        if (!(w_part + q_part)) return;
+        if (!sum) return;
         const size_t own = (ws.bytes + 255) & ~(size_t)255;    // ws.bytes counts from the caller's pointer, the parts from the aligned start: past its end
         char* at = reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(base) + 255) & ~(uintptr_t)255) + own;
-        if (w_part) { weights = reinterpret_cast<float*>(at); at += w_part; }
-        if (q_part) depth_q_raw = reinterpret_cast<float*>(at);
-        bytes = own + w_part + q_part + 256;
+        auto take = [&at](size_t part) { char* r = part ? at : nullptr; at += part; return r; };
+        weights = reinterpret_cast<float*>(take(parts[0]));
+        depth_q_raw = reinterpret_cast<float*>(take(parts[1]));
+        row_of_ray = reinterpret_cast<int32_t*>(take(parts[2]));
+        ray_of_row = reinterpret_cast<int64_t*>(take(parts[3]));
+        count = reinterpret_cast<int64_t*>(take(parts[4]));
+        alive_ws = take(parts[5]);
+        rays_c = reinterpret_cast<float*>(take(parts[6]));
+        z_rows_c = reinterpret_cast<float*>(take(parts[7]));
+        z_coarse = reinterpret_cast<float*>(take(parts[8]));
+        bytes = own + sum + 256;
     }
 };
 int check_quantiles(const float* q, int nq) {
@@ -774,6 +803,7 @@ int check_quantiles(const float* q, int nq) {
 int check_plan_shape(RenderPlan& p, int layouts, const char* bad_precision) {
     if (split_precision(p.precision, p.lflags, layouts)) return fail(NERF_AMD_EINVAL, bad_precision);
     if ((p.lflags & NERF_AMD_FINE_W128) && p.ipe()) return fail(NERF_AMD_EINVAL, "the 128-wide fine layout has no integrated-PE kernel: pack the network 256-wide");
+    if (p.skip() && p.N > 0x7fffffff) return fail(NERF_AMD_EINVAL, "the empty-ray skip indexes rays in int32: N must be below 2^31");
     if (p.N < 0 || p.n_fine < 1 || p.n_fine > 1023) return fail(NERF_AMD_EINVAL, "bad N or n_fine");
     if (p.camera && (p.camera->contract < 0 || p.camera->contract > NERF_AMD_CONTRACT_GAUSSIAN)) return fail(NERF_AMD_EINVAL, "contract must be 0, 1 or NERF_AMD_CONTRACT_GAUSSIAN");
     if (p.camera && !p.ref && p.camera->contract == NERF_AMD_CONTRACT_GAUSSIAN && !p.camera->ipe)
@@ -812,16 +842,16 @@ int provide_dir_norm(const RenderPlan& p, const float* rays, const RenderWs& ws,
     return hip_status((p.N >= 8) ? sk_dirs_norm_scratch(rays, p.N, ws.dir_norm, ws.density, st) : sk_dirs_norm(rays, p.N, ws.dir_norm, st), "direction norm");
 }
 // S samples per ray at the depths z (row stride z_stride); the descriptor may accompany explicit rays just to carry `contract`
-nerf_amd_samples ray_samples(const RenderPlan& p, const float* rays, int S, const float* z, int z_stride) {
+nerf_amd_samples ray_samples(const RenderPlan& p, const float* rays, int S, const float* z, int z_stride, int64_t n_rays = -1) {    // n_rays < 0: all of the plan's
     nerf_amd_samples s{};
-    s.mode = 1; s.rays = rays; s.S = S; s.M = p.N * S; s.z = z; s.z_stride = z_stride; s.contract = p.camera ? p.camera->contract : 0;
+    s.mode = 1; s.rays = rays; s.S = S; s.M = (n_rays < 0 ? p.N : n_rays) * S; s.z = z; s.z_stride = z_stride; s.contract = p.camera ? p.camera->contract : 0;
     return s;
 }
 // rows 2-7: the coarse draw and the proposal pass, then weights -> max-blur(0.01) -> inverse sampling of K sorted depths into z_out
 // (procedures.py:59,68-70).  Linear spacing: the stratified z is fused into the proposal MLP, and ws.z_coarse (Ref-NeRF) also receives the
 // depths it used.  Disparity spacing: the draw happens in s (no position tensor: the proposal MLP forms o + z d itself), s_out receives the
-// resampled s next to z_out = W(s).
-int coarse_pass(const RenderPlan& p, const float* rays, int K, float* z_out, float* s_out, const RenderWs& ws, hipStream_t st) {
+// resampled s next to z_out = W(s).  z_coarse (linear spacing; may be NULL): receives the coarse depths the resampling kernel drew.
+int coarse_pass(const RenderPlan& p, const float* rays, int K, float* z_out, float* s_out, float* z_coarse, const RenderWs& ws, hipStream_t st) {
     constexpr int C = RENDER_C;
     if (p.warped) {
         if (int e = sk_warped_stratified(rays, p.u_strat, p.N, C, p.seed(), p.ray0(), p.near, p.far, p.gn, p.gf, ws.s_c, ws.z_c, nullptr, st))
@@ -836,7 +866,7 @@ int coarse_pass(const RenderPlan& p, const float* rays, int K, float* z_out, flo
     sc.z_base = p.z_base; sc.u = p.u_strat; sc.z_jitter = jitter; sc.rng_seed = p.seed(); sc.rng_ray_offset = p.ray0();
     if (int e = launch_proposal_any(p.lflags, p.packed_prop, p.precision, sc, ws.density, st)) return hip_status(e, "proposal MLP");
     return hip_status(sk_resample(ws.density, nullptr, p.z_base, p.u_strat, jitter, rays + 3, 6, p.u_inv, p.N, C, K, 0, 0.01f, p.seed(), p.ray0(), z_out, nullptr, nullptr,
-                                  ws.z_coarse, st), "resample");
+                                  z_coarse, st), "resample");
 }
 // the second round: the proposal network at the first round's P depths, then the n_fine + 1 fine depths from that histogram with columns
 // [P, P + n_fine + 1) of each ray's inverse-CDF stream (the first round used [0, P))
@@ -850,19 +880,25 @@ int second_round(const RenderPlan& p, const float* rays, const RenderWs& ws, hip
     return hip_status(sk_resample_window(ws.density2, ws.z_mid, rays + 3, 6, p.N, P, K, P, 0.01f, p.seed(), p.ray0(), ws.z_fine, st), "resample, second round");
 }
 // rows 8-9: drop the last depth, length2pts fused into the fine MLP (`dir_norm`: integrated PE, frustum s = [z_fine[s], z_fine[s+1]])
-int fine_pass(const RenderPlan& p, const float* rays, const float* dir_norm, const RenderWs& ws, hipStream_t st) {
-    nerf_amd_samples sf = ray_samples(p, rays, p.n_fine, ws.z_fine, p.n_fine + 1);
+// (the empty-ray skip hands over its compact ray table and depth rows, n_rays of them: ws.rgbo then holds compact rows)
+int fine_pass(const RenderPlan& p, const float* rays, const float* z_fine, int64_t n_rays, const float* dir_norm, const RenderWs& ws, hipStream_t st) {
+    nerf_amd_samples sf = ray_samples(p, rays, p.n_fine, z_fine, p.n_fine + 1, n_rays);
     if (dir_norm) { sf.ipe = 1; sf.ipe_radius = p.camera->ipe_radius; sf.ipe_dir_norm = dir_norm; }
     return hip_status(launch_mip_any(p.lflags, p.packed_fine, p.precision, sf, ws.rgbo, st), "fine MLP");
 }
 // row 10.  Rows 9 and 10 are two launches: measured 2-3 % faster than the fused epilogue of nerf_amd_mip_forward_composite on MI355X
 // (DESIGN.md section 3.3), and the composite kernel's HBM rate stays individually measurable.  Disparity spacing: composited with near = 0,
 // far = 1 -- the kernel's depth is then the raw expected metric depth sum w z |d| -- and un-warped by one more launch.
-int composite_pass(const RenderPlan& p, const float* rays, const RenderWs& ws, hipStream_t st) {
+// `rows` (the empty-ray skip; else NULL): ws.rgbo holds compact rows, ray n's at rows[n], none (zeros) where that is -1.
+int composite_pass(const RenderPlan& p, const float* rays, const int32_t* rows, const RenderWs& ws, hipStream_t st) {
     const int flags = 1 | (p.white_bkg ? 2 : 0);
     const bool unwarp = p.warped && p.depth;
-    if (int e = sk_composite(ws.rgbo, ws.z_fine, p.n_fine + 1, rays + 3, 6, p.N, p.n_fine, flags, NERF_AMD_ACT_RELU, 0.0f, p.warped ? 0.0f : p.near,
-                             p.warped ? 1.0f : p.far, nullptr, nullptr, p.rgb, p.weights, unwarp ? ws.depth_raw : p.depth, nullptr, st)) return hip_status(e, "composite");
+    const float near = p.warped ? 0.0f : p.near, far = p.warped ? 1.0f : p.far;
+    float* depth = unwarp ? ws.depth_raw : p.depth;
+    if (int e = rows ? sk_composite_rows(ws.rgbo, rows, ws.z_fine, p.n_fine + 1, rays + 3, 6, p.N, p.n_fine, flags, NERF_AMD_ACT_RELU, 0.0f, near, far, nullptr, nullptr,
+                                         p.rgb, p.weights, depth, nullptr, st)
+                     : sk_composite(ws.rgbo, ws.z_fine, p.n_fine + 1, rays + 3, 6, p.N, p.n_fine, flags, NERF_AMD_ACT_RELU, 0.0f, near, far, nullptr, nullptr, p.rgb,
+                                    p.weights, depth, nullptr, st)) return hip_status(e, "composite");
     return unwarp ? hip_status(sk_warp_depths(ws.depth_raw, nullptr, p.N, 1, 1, p.near, p.far, p.gn, p.gf, p.depth, nullptr, st), "depth un-warp") : NERF_AMD_OK;
 }
 // nerf_amd_render's optional outputs, appended to the entry point's launches (nothing is launched when none is asked for): the stats
@@ -879,23 +915,58 @@ int extras_pass(const RenderPlan& p, const float* rays, const float* z_row, bool
     if (p.fine_depths) return hip_status((int)hipMemcpyAsync(p.fine_depths, z_row, (size_t)p.N * E * 4, hipMemcpyDeviceToDevice, st), "fine depth copy");
     return NERF_AMD_OK;
 }
+// The empty-ray skip (include/nerf_amd.h), between the last resampling and the fine pass: flags and ordered compaction of the histogram
+// (density, z) of C depths per ray, N' read back to the host -- the one synchronisation of a render call, which is why the mode cannot be
+// captured --, then the alive rays' ray records and fine depth rows (z_rows, E floats each) gathered into the compact tables.
+int skip_stage(const RenderPlan& p, const float* rays, const float* density, const float* z, int C, const float* z_rows, const RenderExtrasWs& x, hipStream_t st,
+               int64_t* n_alive, const int32_t** rows) {
+    int32_t* row_of_ray = p.row_of_ray ? p.row_of_ray : x.row_of_ray;
+    if (int e = sk_ray_alive(density, z, C, rays + 3, 6, p.N, C, p.skip_dmin, row_of_ray, x.ray_of_row, x.count, x.alive_ws, st)) return hip_status(e, "empty-ray flags and compaction");
+    int64_t count = -1;
+    if (int e = (int)hipMemcpyAsync(&count, x.count, sizeof count, hipMemcpyDeviceToHost, st)) return hip_status(e, "alive-ray count read-back");
+    if (int e = (int)hipStreamSynchronize(st)) return hip_status(e, "alive-ray count read-back");
+    if (count < 0 || count > p.N) return fail(NERF_AMD_EHIP, "the alive-ray count read back from the device is outside 0..N");
+    if (p.n_alive) *p.n_alive = count;
+    *n_alive = count;
+    *rows = row_of_ray;
+    if (int e = sk_gather_rows(rays, 6, x.ray_of_row, count, 6, x.rays_c, st)) return hip_status(e, "ray gather");
+    return hip_status(sk_gather_rows(z_rows, p.fine_row(), x.ray_of_row, count, p.fine_row(), x.z_rows_c, st), "depth row gather");
+}
+// refused before the first launch: a capturing stream (the skip reads a count on the host)
+int check_skip_stream(const RenderPlan& p, hipStream_t st) {
+    if (!p.skip()) return NERF_AMD_OK;
+    hipStreamCaptureStatus status = hipStreamCaptureStatusNone;
+    if (int e = (int)hipStreamIsCapturing(st, &status)) return hip_status(e, "hipStreamIsCapturing");
+    return status == hipStreamCaptureStatusNone ? NERF_AMD_OK
+                                                : fail(NERF_AMD_EUNSUPPORTED, "the empty-ray skip reads the alive-ray count on the host: not on a capturing stream");
+}
 // the three MipNeRF entry points behind their own checks: shape, N == 0, inputs, then the launches in pipeline order
 int render_mip(RenderPlan& p, void* workspace, hipStream_t st) {
     if (int e = check_plan_shape(p, NERF_AMD_PROP_W128 | NERF_AMD_FINE_W128, "unknown precision")) return e;
     if (p.N == 0) return NERF_AMD_OK;
     if (int e = check_plan_inputs(p, workspace)) return e;
+    if (int e = check_skip_stream(p, st)) return e;
     const RenderWs ws = p.ws(workspace);
+    const RenderExtrasWs x(p, workspace);
     const float *rays, *dir_norm;
     if (int e = provide_rays(p, ws, st, &rays)) return e;
-    if (int e = provide_dir_norm(p, rays, ws, st, &dir_norm)) return e;
+    if (int e = provide_dir_norm(p, rays, ws, st, &dir_norm)) return e;       // (of the whole ray list: the skip compacts after it)
     const int P = p.prop_pnum;
-    if (int e = coarse_pass(p, rays, P ? P : p.n_fine + 1, P ? ws.z_mid : ws.z_fine, P ? ws.s_mid : nullptr, ws, st)) return e;
+    if (int e = coarse_pass(p, rays, P ? P : p.n_fine + 1, P ? ws.z_mid : ws.z_fine, P ? ws.s_mid : nullptr, x.z_coarse, ws, st)) return e;
     if (P)
         if (int e = second_round(p, rays, ws, st)) return e;
-    if (int e = fine_pass(p, rays, dir_norm, ws, st)) return e;
-    const RenderExtrasWs x(p, workspace);
+    const int32_t* rows = nullptr;                          // the skip: the histogram the fine depths were drawn from -> compact rays and depth rows
+    const float *fine_rays = rays, *fine_z = ws.z_fine;
+    int64_t n_fine_rays = p.N;
+    if (p.skip()) {
+        if (int e = skip_stage(p, rays, P ? ws.density2 : ws.density, P ? ws.z_mid : (p.warped ? ws.z_c : x.z_coarse), P ? P : RENDER_C, ws.z_fine, x, st, &n_fine_rays,
+                               &rows)) return e;
+        fine_rays = x.rays_c; fine_z = x.z_rows_c;
+    }
+    if (n_fine_rays)
+        if (int e = fine_pass(p, fine_rays, fine_z, n_fine_rays, dir_norm, ws, st)) return e;
     if (x.weights) p.weights = x.weights;                   // (nerf_amd_render with stats and no weights output: composited into the appended part)
-    if (int e = composite_pass(p, rays, ws, st)) return e;
+    if (int e = composite_pass(p, rays, rows, ws, st)) return e;
     return extras_pass(p, rays, ws.z_fine, true, x, st);
 }
 // the Ref-NeRF entry point, likewise: the checks, then the launches in pipeline order
@@ -905,22 +976,33 @@ int render_ref(RenderPlan& p, void* workspace, hipStream_t st) {
     if (p.N == 0) return NERF_AMD_OK;
     if (int e = check_plan_inputs(p, workspace)) return e;
     if ((p.normal_img != nullptr) != (p.cam_dir != nullptr)) return fail(NERF_AMD_EINVAL, "normal_img and cam_dir go together");
+    if (int e = check_skip_stream(p, st)) return e;
     constexpr int C = RENDER_C;
     const int S_all = p.fine_samples();                     // (n_fine + 1) fine + 64 coarse depths, the last one dropped
     const RenderWs ws = p.ws(workspace);
     const float* rays;
     if (int e = provide_rays(p, ws, st, &rays)) return e;
-    if (int e = coarse_pass(p, rays, p.n_fine + 1, ws.z_fine, nullptr, ws, st)) return e;
+    if (int e = coarse_pass(p, rays, p.n_fine + 1, ws.z_fine, nullptr, ws.z_coarse, ws, st)) return e;
     // row 8, Ref-NeRF branch (procedures.py:71-74): fine and coarse depths merged, the last one dropped
     if (int e = sk_merge_sorted(ws.z_fine, ws.z_coarse, p.N, p.n_fine + 1, C, ws.z_all, st)) return hip_status(e, "depth merge");
-    const nerf_amd_samples sf = ray_samples(p, rays, S_all, ws.z_all, S_all);   // row 13
-    float* normals = p.normal_img ? ws.normals : nullptr;
-    if (int e = mlp_launch_ref(p.packed_fine, p.precision, sf, ws.rgbo, normals, nullptr, p.ref_flags, st)) return hip_status(e, "Ref-NeRF MLP");
     const RenderExtrasWs x(p, workspace);
+    const int32_t* rows = nullptr;                          // the skip: compact rays and merged depth rows, compact rgbo / normal rows
+    const float *fine_rays = rays, *fine_z = ws.z_all;
+    int64_t n_fine_rays = p.N;
+    if (p.skip()) {
+        if (int e = skip_stage(p, rays, ws.density, ws.z_coarse, C, ws.z_all, x, st, &n_fine_rays, &rows)) return e;
+        fine_rays = x.rays_c; fine_z = x.z_rows_c;
+    }
+    const nerf_amd_samples sf = ray_samples(p, fine_rays, S_all, fine_z, S_all, n_fine_rays);   // row 13
+    float* normals = p.normal_img ? ws.normals : nullptr;
+    if (n_fine_rays)
+        if (int e = mlp_launch_ref(p.packed_fine, p.precision, sf, ws.rgbo, normals, nullptr, p.ref_flags, st)) return hip_status(e, "Ref-NeRF MLP");
     if (x.weights) p.weights = x.weights;
     const int flags = 1 | (p.white_bkg ? 2 : 0);            // row 10 with sigma -> softplus(sigma + 0.5) (procedures.py:73)
-    if (int e = sk_composite(ws.rgbo, ws.z_all, S_all, rays + 3, 6, p.N, S_all, flags, NERF_AMD_ACT_SOFTPLUS, 0.5f, p.near, p.far, normals, p.cam_dir, p.rgb, p.weights,
-                             p.depth, p.normal_img, st)) return hip_status(e, "composite");
+    if (int e = rows ? sk_composite_rows(ws.rgbo, rows, ws.z_all, S_all, rays + 3, 6, p.N, S_all, flags, NERF_AMD_ACT_SOFTPLUS, 0.5f, p.near, p.far, normals, p.cam_dir, p.rgb,
+                                         p.weights, p.depth, p.normal_img, st)
+                     : sk_composite(ws.rgbo, ws.z_all, S_all, rays + 3, 6, p.N, S_all, flags, NERF_AMD_ACT_SOFTPLUS, 0.5f, p.near, p.far, normals, p.cam_dir, p.rgb, p.weights,
+                                    p.depth, p.normal_img, st)) return hip_status(e, "composite");
     return extras_pass(p, rays, ws.z_all, false, x, st);
 }
 // the sizes nerf_amd_render_rays_rounds takes, for the entry point and its workspace query alike: NULL, or what is wrong
@@ -933,7 +1015,9 @@ const char* rounds_shape_error(int64_t N, int n_fine, int prop_pnum, int spacing
 // request -> plan, the one place a plan is filled: which pipeline (ref, prop_pnum, spacing) and what is refused before it starts
 int plan_from_request(const nerf_amd_render_request* r, RenderPlan& p, bool sizing) {     // sizing: the workspace query, which needs no descriptor
     if (!r) return fail(NERF_AMD_EINVAL, "NULL argument: request");
-    if (r->size < sizeof(nerf_amd_render_request)) return fail(NERF_AMD_EINVAL, "request->size is smaller than nerf_amd_render_request");
+    constexpr size_t first_layout = offsetof(nerf_amd_render_request, skip_min_optical_depth);     // everything up to fine_depths
+    if (r->size < first_layout) return fail(NERF_AMD_EINVAL, "request->size is smaller than nerf_amd_render_request");
+    const bool has_skip = r->size >= sizeof(nerf_amd_render_request);
     if (r->spacing != NERF_AMD_SPACING_LINEAR && r->spacing != NERF_AMD_SPACING_DISPARITY)
         return fail(NERF_AMD_EINVAL, "unknown spacing (NERF_AMD_SPACING_LINEAR or NERF_AMD_SPACING_DISPARITY)");
     const bool warped = r->spacing == NERF_AMD_SPACING_DISPARITY, rounds = !r->ref && r->prop_pnum != 0;
@@ -951,12 +1035,17 @@ int plan_from_request(const nerf_amd_render_request* r, RenderPlan& p, bool sizi
     if (int e = check_quantiles(r->quantiles, r->n_quantiles)) return e;
     p.opacity = r->opacity; p.depth_q = r->depth_q; p.fine_depths = r->fine_depths; p.n_quantiles = r->n_quantiles;
     for (int j = 0; j < r->n_quantiles; ++j) p.quantiles[j] = r->quantiles[j];
+    if (has_skip) {
+        if (r->skip_min_optical_depth != r->skip_min_optical_depth) return fail(NERF_AMD_EINVAL, "skip_min_optical_depth is NaN");
+        if (r->skip_min_optical_depth > 0.0) { p.skip_dmin = r->skip_min_optical_depth; p.row_of_ray = r->row_of_ray; p.n_alive = r->n_alive; }
+    }
     return NERF_AMD_OK;
 }
 // every render entry point ends here: nerf_amd_render directly, the four argument-list entry points with a request they fill themselves
 int render_request(const nerf_amd_render_request* r, void* workspace, void* stream) {
     RenderPlan p{};
     if (int e = plan_from_request(r, p, false)) return e;
+    if (p.skip() && p.N == 0 && p.n_alive) *p.n_alive = 0;  // (no ray, none alive: the pipelines return before their first stage)
     return p.ref ? render_ref(p, workspace, S(stream)) : render_mip(p, workspace, S(stream));
 }
 }  // namespace
@@ -1055,6 +1144,25 @@ size_t nerf_amd_render_request_workspace_bytes(const nerf_amd_render_request* re
 }
 int nerf_amd_render(const nerf_amd_render_request* request, void* workspace, void* stream) {
     return render_request(request, workspace, stream);
+}
+
+size_t nerf_amd_ray_alive_workspace_bytes(int64_t N) { return (N < 0 || N > 0x7fffffff) ? 0 : sk_ray_alive_workspace_bytes(N); }
+int nerf_amd_ray_alive(const float* density, const float* z, int z_stride, const float* dirs, int dirs_stride, int64_t N, int C, double min_optical_depth,
+                       int32_t* row_of_ray, int64_t* ray_of_row, int64_t* count_dev, void* workspace, void* stream) {
+    if (N < 0 || N > 0x7fffffff) return fail(NERF_AMD_EINVAL, "need 0 <= N < 2^31 (rays are ranked in int32)");
+    if (C < 2) return fail(NERF_AMD_EINVAL, "need C >= 2 depths per ray");
+    if (z_stride < C) return fail(NERF_AMD_EINVAL, "z_stride is smaller than the depth row (C)");
+    if (dirs_stride < 3) return fail(NERF_AMD_EINVAL, "dirs_stride < 3");
+    if (min_optical_depth != min_optical_depth) return fail(NERF_AMD_EINVAL, "min_optical_depth is NaN");
+    if (!count_dev) return fail(NERF_AMD_EINVAL, "NULL argument: count_dev");
+    if (N && (!density || !z || !dirs || !row_of_ray || !ray_of_row || !workspace)) return fail(NERF_AMD_EINVAL, "NULL argument");
+    return hip_status(sk_ray_alive(density, z, z_stride, dirs, dirs_stride, N, C, min_optical_depth, row_of_ray, ray_of_row, count_dev, workspace, S(stream)),
+                      "nerf_amd_ray_alive");
+}
+int nerf_amd_gather_rows(const float* src, int64_t src_stride, const int64_t* ray_of_row, int64_t n_rows, int cols, float* dst, void* stream) {
+    if (n_rows < 0 || cols < 0 || src_stride < cols) return fail(NERF_AMD_EINVAL, "bad size or stride (n_rows >= 0, 0 <= cols <= src_stride)");
+    if (n_rows * cols && (!src || !ray_of_row || !dst)) return fail(NERF_AMD_EINVAL, "NULL argument");
+    return hip_status(sk_gather_rows(src, src_stride, ray_of_row, n_rows, cols, dst, S(stream)), "nerf_amd_gather_rows");
 }
 
 int nerf_amd_ray_depth_stats(const float* weights, const float* z, int z_stride, int closed, const float* dirs, int dirs_stride, int64_t N, int Sn, int mul_norm,

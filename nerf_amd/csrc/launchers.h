@@ -89,6 +89,14 @@ int sk_warped_resample_window(const float* density, const float* s_c, const floa
                               float far, float gn, float gf, uint64_t rng_seed, int64_t rng_ray_offset, float* z_fine, float* s_fine, hipStream_t st);
 int sk_composite(const float* rgbo, const float* z, int z_stride, const float* dirs, int dirs_stride, int64_t N, int S, int flags, int act, float sigma_shift, float near, float far,
                  const float* normal, const float* cam_dir, float* rgb, float* weights, float* depth, float* normal_img, hipStream_t st);
+// the same on COMPACT rgbo / normal rows: ray n reads row row_of_ray[n], an all-zero row where that is -1 (the empty-ray skip)
+int sk_composite_rows(const float* rgbo, const int32_t* row_of_ray, const float* z, int z_stride, const float* dirs, int dirs_stride, int64_t N, int S, int flags, int act,
+                      float sigma_shift, float near, float far, const float* normal, const float* cam_dir, float* rgb, float* weights, float* depth, float* normal_img, hipStream_t st);
+// the empty-ray skip (nerf_amd_ray_alive / nerf_amd_gather_rows): N < 2^31; workspace of sk_ray_alive_workspace_bytes(N) bytes
+size_t sk_ray_alive_workspace_bytes(int64_t N);
+int sk_ray_alive(const float* density, const float* z, int z_stride, const float* dirs, int dirs_stride, int64_t N, int C, double d_min, int32_t* row_of_ray, int64_t* ray_of_row,
+                 int64_t* count_dev, void* workspace, hipStream_t st);
+int sk_gather_rows(const float* src, int64_t src_stride, const int64_t* ray_of_row, int64_t n_rows, int cols, float* dst, hipStream_t st);
 // quantiles: host, n_quantiles <= NERF_AMD_DEPTH_QUANTILES_MAX values in (0, 1), passed to the kernel by value (validated by the caller)
 int sk_ray_depth_stats(const float* w, const float* z, int z_stride, int closed, const float* dirs, int dirs_stride, int64_t N, int S, int mul_norm,
                        const float* quantiles, int n_quantiles, float near, float far, float* opacity, float* depth_q, hipStream_t st);

@@ -940,17 +940,23 @@ struct CompositeArgs {
 // one is reduced, so two rays' worth of HBM requests are in flight per wave.  Same arithmetic, same order as the generic path.
 template <int NCH>
 struct RayRecs { f32x4 c[NCH]; float z[NCH]; float dx, dy, dz; };
-template <int NCH>
-DEVINL RayRecs<NCH> load_ray(const CompositeArgs& a, int64_t n, int lane) {
+// ROWS (the empty-ray skip, nerf_amd_render with skip_min_optical_depth > 0): the rgbo (and normal) rows are COMPACT -- ray n's row is
+// rows[n], -1 for a ray the fine network was not run on, which reads an all-zero row; depths, directions and every output stay indexed
+// by n.  Without ROWS nothing of this is compiled in.
+template <int NCH, bool ROWS>
+DEVINL RayRecs<NCH> load_ray(const CompositeArgs& a, const int32_t* rows, int64_t n, int lane) {
     RayRecs<NCH> r;
     const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
-    const f32x4* px = reinterpret_cast<const f32x4*>(a.rgbo) + n * a.S;
+    int64_t row = n;
+    if (ROWS) row = rows[n];
+    const bool live = !ROWS || row >= 0;
+    const f32x4* px = reinterpret_cast<const f32x4*>(a.rgbo) + row * a.S;
     const float* zz = a.z + n * a.z_stride;
     const float* dd = a.dirs + n * a.dirs_stride;
 #pragma unroll
     for (int k = 0; k < NCH; ++k) {
         const int s = 64 * k + lane;
-        r.c[k] = (s < a.S) ? px[s] : zero;
+        r.c[k] = (s < a.S && live) ? px[s] : zero;
         r.z[k] = (s < a.S) ? zz[s] : 0.0f;
     }
     r.dx = dd[0]; r.dy = dd[1]; r.dz = dd[2];
@@ -996,26 +1002,27 @@ DEVINL void composite_ray_fast(const CompositeArgs& a, int64_t n, const RayRecs<
         if (a.depth) a.depth[n] = (accd - a.near) / (a.far - a.near);
     }
 }
-template <int NCH>
-DEVINL void composite_rays_fast(const CompositeArgs& a, int lane) {
+template <int NCH, bool ROWS>
+DEVINL void composite_rays_fast(const CompositeArgs& a, const int32_t* rows, int lane) {
     const int64_t stride = (int64_t)gridDim.x * WAVES_PER_BLOCK;
     int64_t n = blockIdx.x * (int64_t)WAVES_PER_BLOCK + wave_in_block();
     if (n >= a.N) return;
-    RayRecs<NCH> cur = load_ray<NCH>(a, n, lane);
+    RayRecs<NCH> cur = load_ray<NCH, ROWS>(a, rows, n, lane);
     for (; n < a.N; n += stride) {
         RayRecs<NCH> nxt = cur;
-        if (n + stride < a.N) nxt = load_ray<NCH>(a, n + stride, lane);
+        if (n + stride < a.N) nxt = load_ray<NCH, ROWS>(a, rows, n + stride, lane);
         composite_ray_fast<NCH>(a, n, cur, lane);
         cur = nxt;
     }
 }
 
-__global__ __launch_bounds__(256) void composite_kernel(CompositeArgs a) {
+template <bool ROWS>
+DEVINL void composite_rays(const CompositeArgs& a, const int32_t* rows) {
     const int S = a.S;
     const int lane = lane_id();
     if (S <= 256 && a.normal == nullptr && a.normal_img == nullptr) {
-        if (S <= 128) composite_rays_fast<2>(a, lane);
-        else composite_rays_fast<4>(a, lane);
+        if (S <= 128) composite_rays_fast<2, ROWS>(a, rows, lane);
+        else composite_rays_fast<4, ROWS>(a, rows, lane);
         return;
     }
     for (int64_t n = blockIdx.x * (int64_t)WAVES_PER_BLOCK + wave_in_block(); n < a.N; n += (int64_t)gridDim.x * WAVES_PER_BLOCK) {
@@ -1023,20 +1030,27 @@ __global__ __launch_bounds__(256) void composite_kernel(CompositeArgs a) {
         const bool mul = (a.flags & 1) != 0;
         const float nrm = mul ? norm3(dd[0], dd[1], dd[2]) : 1.0f;
         const float* zz = a.z + n * a.z_stride;
-        const f32x4* px = reinterpret_cast<const f32x4*>(a.rgbo) + n * S;
+        int64_t row = n;
+        if (ROWS) row = rows[n];
+        const bool live = !ROWS || row >= 0;                        // (ROWS: a ray without a row composites zeros)
+        const f32x4 zero = {0.0f, 0.0f, 0.0f, 0.0f};
+        const f32x4* px = reinterpret_cast<const f32x4*>(a.rgbo) + row * S;
         float accr = 0.0f, accg = 0.0f, accb = 0.0f, accw = 0.0f, accd = 0.0f, accn = 0.0f;
         float cx = 0.0f, cy = 0.0f, cz = 0.0f;
         if (a.normal_img) { cx = a.cam_dir[0]; cy = a.cam_dir[1]; cz = a.cam_dir[2]; }
         float* wout = a.weights ? a.weights + n * S : nullptr;
-        const float* nm = a.normal ? a.normal + n * S * 3 : nullptr;
+        const float* nm = a.normal ? a.normal + row * S * 3 : nullptr;
         const float shift = a.sigma_shift;
-        wave_sigma_to_weights(S, a.act, [&](int s) { return px[s][3] + shift; },
+        wave_sigma_to_weights(S, a.act, [&](int s) { return (live ? px[s][3] : 0.0f) + shift; },
                               [&](int s) { return mul ? zz[s] * nrm : zz[s]; },
                               [&](int s, float w, float zn) {
-                                  const f32x4 c = px[s];
+                                  const f32x4 c = live ? px[s] : zero;
                                   accr += w * c[0]; accg += w * c[1]; accb += w * c[2];
                                   accw += w; accd += w * zn;
-                                  if (nm) accn += w * ((nm[s * 3] * cx + nm[s * 3 + 1] * cy) + nm[s * 3 + 2] * cz);
+                                  if (nm) {
+                                      const float n0 = live ? nm[s * 3] : 0.0f, n1 = live ? nm[s * 3 + 1] : 0.0f, n2 = live ? nm[s * 3 + 2] : 0.0f;
+                                      accn += w * ((n0 * cx + n1 * cy) + n2 * cz);
+                                  }
                                   if (wout) wout[s] = w;
                               });
         accr = wave_sum(accr); accg = wave_sum(accg); accb = wave_sum(accb); accw = wave_sum(accw);
@@ -1048,6 +1062,94 @@ __global__ __launch_bounds__(256) void composite_kernel(CompositeArgs a) {
             if (a.depth) a.depth[n] = (accd - a.near) / (a.far - a.near);
             if (a.normal_img) a.normal_img[n] = (accn + 1.0f) * 0.5f;
         }
+    }
+}
+__global__ __launch_bounds__(256) void composite_kernel(CompositeArgs a) { composite_rays<false>(a, nullptr); }
+__global__ __launch_bounds__(256) void composite_rows_kernel(CompositeArgs a, const int32_t* __restrict__ rows) { composite_rays<true>(a, rows); }
+
+// ---------------------------------------------------------------------------------------- empty-ray skip (include/nerf_amd.h: nerf_amd_ray_alive)
+// The optical depth D of the proposal histogram of one ray, one wavefront per ray, any C >= 2: every term is formed in fp64 from the fp32
+// inputs, the lanes' partial sums meet in an fp64 butterfly (no LDS, no atomics).  max(sigma, 0) is written as a select that keeps a NaN:
+// D is then NaN, D < D_min is false and the ray stays alive.  flags[n] = !(D < D_min).
+struct RayAliveArgs { const float* density; const float* z; int z_stride; const float* dirs; int dirs_stride; int64_t N; int C; double d_min; uint8_t* flags; };
+__global__ __launch_bounds__(256) void ray_alive_kernel(RayAliveArgs a) {
+    const int lane = lane_id();
+    const int C = a.C;
+    for (int64_t n = blockIdx.x * (int64_t)WAVES_PER_BLOCK + wave_in_block(); n < a.N; n += (int64_t)gridDim.x * WAVES_PER_BLOCK) {
+        const float* sg = a.density + n * C;
+        const float* zz = a.z + n * a.z_stride;
+        double acc = 0.0;
+        for (int s = lane; s < C - 1; s += 64) {
+            const float sv = sg[s];
+            const double sig = sv < 0.0f ? 0.0 : (double)sv;
+            acc += sig * ((double)zz[s + 1] - (double)zz[s]);
+        }
+        acc = wave_sum_d(acc);
+        if (lane == 0) {
+            const float* dd = a.dirs + n * a.dirs_stride;
+            const double dx = dd[0], dy = dd[1], dz = dd[2];
+            const float sl = sg[C - 1];
+            const double closing = (sl < 0.0f ? 0.0 : (double)sl) * 1e10;       // the last delta: 1e10, not scaled by |d|
+            const double D = sqrt((dx * dx + dy * dy) + dz * dz) * acc + closing;
+            a.flags[n] = !(D < a.d_min) ? 1 : 0;
+        }
+    }
+}
+// Ordered stream compaction of the flags in tiles of 256 (one per workgroup): a ballot + popcount per wave, the four wave counts through
+// LDS -> one count per tile; ONE workgroup turns the tile counts into exclusive offsets (wave scan + carry, 256 tiles per step) and stores
+// the total; the tiles then rank their alive rays -- offset of the tile + alive rays of the waves before + alive lanes below -- and write both
+// tables.  Alive rays keep their order; no atomics: the result is a pure function of the flags.
+constexpr int ALIVE_TILE = 256;
+DEVINL unsigned long long alive_ballot(const uint8_t* flags, int64_t N, int64_t n, int* wave_count) {
+    const unsigned long long m = __ballot(n < N && flags[n] != 0);
+    if (lane_id() == 0) wave_count[wave_in_block()] = __popcll(m);
+    __syncthreads();
+    return m;
+}
+__global__ __launch_bounds__(256) void alive_count_kernel(const uint8_t* __restrict__ flags, int64_t N, int* __restrict__ tile_count) {
+    __shared__ int wave_count[WAVES_PER_BLOCK];
+    alive_ballot(flags, N, blockIdx.x * (int64_t)ALIVE_TILE + threadIdx.x, wave_count);
+    if (threadIdx.x == 0) tile_count[blockIdx.x] = (wave_count[0] + wave_count[1]) + (wave_count[2] + wave_count[3]);
+}
+__global__ __launch_bounds__(256) void alive_offsets_kernel(int* __restrict__ tiles, int64_t n_tiles, int64_t* __restrict__ count) {
+    __shared__ int wave_total[WAVES_PER_BLOCK];
+    const int lane = lane_id(), wv = wave_in_block();
+    int carry = 0;
+    for (int64_t base = 0; base < n_tiles; base += 256) {
+        const int64_t i = base + threadIdx.x;
+        const int v = i < n_tiles ? tiles[i] : 0;
+        const int incl = wave_incl_scan_add(v);
+        if (lane == 63) wave_total[wv] = incl;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < WAVES_PER_BLOCK; ++k) { before += k < wv ? wave_total[k] : 0; total += wave_total[k]; }
+        if (i < n_tiles) tiles[i] = carry + before + (incl - v);
+        carry += total;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *count = carry;
+}
+__global__ __launch_bounds__(256) void alive_tables_kernel(const uint8_t* __restrict__ flags, int64_t N, const int* __restrict__ tile_offset,
+                                                           int32_t* __restrict__ row_of_ray, int64_t* __restrict__ ray_of_row) {
+    __shared__ int wave_count[WAVES_PER_BLOCK];
+    const int64_t n = blockIdx.x * (int64_t)ALIVE_TILE + threadIdx.x;
+    const unsigned long long m = alive_ballot(flags, N, n, wave_count);
+    if (n >= N) return;
+    const int lane = lane_id(), wv = wave_in_block();
+    int rank = tile_offset[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
+    for (int k = 0; k < wv; ++k) rank += wave_count[k];
+    const bool alive = (m >> lane) & 1ull;
+    row_of_ray[n] = alive ? rank : -1;
+    if (alive) ray_of_row[rank] = n;
+}
+// dst (n_rows, cols) = the rows ray_of_row[0 .. n_rows) of src (row stride src_stride floats)
+__global__ __launch_bounds__(256) void gather_rows_kernel(const float* __restrict__ src, int64_t src_stride, const int64_t* __restrict__ ray_of_row, int64_t n_rows,
+                                                          int cols, float* __restrict__ dst) {
+    const int64_t total = n_rows * cols;
+    for (int64_t i = blockIdx.x * (int64_t)256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / cols;
+        dst[i] = src[ray_of_row[r] * src_stride + (i - r * cols)];
     }
 }
 
@@ -2254,6 +2356,37 @@ int nk::sk_composite(const float* rgbo, const float* z, int z_stride, const floa
     if (N == 0) return 0;
     CompositeArgs a{rgbo, z, z_stride, dirs, dirs_stride, N, S, flags, act, sigma_shift, near, far, normal, cam_dir, rgb, weights, depth, normal_img};
     hipLaunchKernelGGL(composite_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), 0, st, a);
+    return (int)hipGetLastError();
+}
+int nk::sk_composite_rows(const float* rgbo, const int32_t* row_of_ray, const float* z, int z_stride, const float* dirs, int dirs_stride, int64_t N, int S, int flags,
+                      int act, float sigma_shift, float near, float far, const float* normal, const float* cam_dir, float* rgb, float* weights, float* depth,
+                      float* normal_img, hipStream_t st) {
+    if (N == 0) return 0;
+    CompositeArgs a{rgbo, z, z_stride, dirs, dirs_stride, N, S, flags, act, sigma_shift, near, far, normal, cam_dir, rgb, weights, depth, normal_img};
+    hipLaunchKernelGGL(composite_rows_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), 0, st, a, row_of_ray);
+    return (int)hipGetLastError();
+}
+// ---- the empty-ray skip: flags -> ordered compaction (three launches behind the flags) / the gather of the alive rays' rows ----
+size_t nk::sk_ray_alive_workspace_bytes(int64_t N) {                 // flags (N bytes) | tile counts (ceil(N / 256) ints), each rounded up to 256 bytes, + alignment slack
+    const size_t n = (size_t)N, tiles = (n + ALIVE_TILE - 1) / ALIVE_TILE;
+    return ((n + 255) & ~(size_t)255) + ((tiles * 4 + 255) & ~(size_t)255) + 256;
+}
+int nk::sk_ray_alive(const float* density, const float* z, int z_stride, const float* dirs, int dirs_stride, int64_t N, int C, double d_min, int32_t* row_of_ray,
+                 int64_t* ray_of_row, int64_t* count_dev, void* workspace, hipStream_t st) {
+    if (N == 0) return (int)hipMemsetAsync(count_dev, 0, 8, st);
+    uint8_t* flags = reinterpret_cast<uint8_t*>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
+    int* tiles = reinterpret_cast<int*>(flags + (((size_t)N + 255) & ~(size_t)255));
+    const int64_t n_tiles = (N + ALIVE_TILE - 1) / ALIVE_TILE;
+    RayAliveArgs a{density, z, z_stride, dirs, dirs_stride, N, C, d_min, flags};
+    hipLaunchKernelGGL(ray_alive_kernel, dim3(blocks_for(N, WAVES_PER_BLOCK)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(alive_count_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, flags, N, tiles);
+    hipLaunchKernelGGL(alive_offsets_kernel, dim3(1), dim3(256), 0, st, tiles, n_tiles, count_dev);
+    hipLaunchKernelGGL(alive_tables_kernel, dim3((unsigned)n_tiles), dim3(256), 0, st, flags, N, tiles, row_of_ray, ray_of_row);
+    return (int)hipGetLastError();
+}
+int nk::sk_gather_rows(const float* src, int64_t src_stride, const int64_t* ray_of_row, int64_t n_rows, int cols, float* dst, hipStream_t st) {
+    if (n_rows * cols == 0) return 0;
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(blocks_for(n_rows * cols, 256)), dim3(256), 0, st, src, src_stride, ray_of_row, n_rows, cols, dst);
     return (int)hipGetLastError();
 }
 int nk::sk_ray_depth_stats(const float* w, const float* z, int z_stride, int closed, const float* dirs, int dirs_stride, int64_t N, int S, int mul_norm,

@@ -2,6 +2,7 @@
 it owns device memory and the HIP stream; every computation below is a hand-written HIP kernel in
 libnerf_amd.so.  CPU tensors are rejected -- there is no fallback path."""
 import ctypes as C
+import math
 from typing import Optional, Sequence
 
 import torch
@@ -879,17 +880,83 @@ def ray_depth_stats(weights: torch.Tensor, z: torch.Tensor, dirs: Optional[torch
     return depth_q, opacity
 
 
+# ------------------------------------------------------------------------------------------------ the empty-ray skip
+def skip_threshold(tau=None, min_optical_depth=None, who: str = "nerf_amd", required: bool = False) -> float:
+    """The threshold D_min of the empty-ray skip (include/nerf_amd.h) from ONE of: ``tau``, an opacity in (0, 1) -> -log1p(-tau) in double;
+    ``min_optical_depth``, D_min itself (> 0).  Neither: 0.0 = off (``required``: a ValueError).  Checked on the host."""
+    if tau is not None and min_optical_depth is not None:
+        raise ValueError("%s: give tau or min_optical_depth, not both" % who)
+    if tau is None and min_optical_depth is None:
+        if required:
+            raise ValueError("%s: give exactly one of tau and min_optical_depth" % who)
+        return 0.0
+    try:
+        v = float(tau if tau is not None else min_optical_depth)
+    except (TypeError, ValueError):
+        raise ValueError("%s: the skip threshold must be a number (got %r)" % (who, tau if tau is not None else min_optical_depth)) from None
+    if tau is not None:
+        if not 0.0 < v < 1.0:                                  # (NaN fails both comparisons)
+            raise ValueError("%s: tau must lie in (0, 1) (got %r)" % (who, tau))
+        return -math.log1p(-v)
+    if not v > 0.0:
+        raise ValueError("%s: min_optical_depth must be positive (got %r)" % (who, min_optical_depth))
+    return v
+
+
+def ray_alive(density: torch.Tensor, z: torch.Tensor, dirs: torch.Tensor, *, tau=None, min_optical_depth=None):
+    """Which rays the proposal histogram leaves non-empty, and their ordered compaction (nerf_amd_ray_alive; the definition is in
+    include/nerf_amd.h and, in fp64, in tests/skip_empty_ref.py): ``density`` (N,C) raw proposal densities, ``z`` (N,C) ascending metric
+    depths (rows may be a strided view), ``dirs`` (N,3) directions or the (N,6) ray table.  D = |d| sum max(sigma_s, 0) (z_{s+1} - z_s)
+    + max(sigma_{C-1}, 0) 1e10 in fp64; a ray is alive unless D < D_min, with D_min = ``min_optical_depth`` or -log1p(-``tau``) (exactly
+    one of the two).  -> (row_of_ray (N,) int32: the rank among the alive rays or -1, ray_of_row (n_alive,) int64 ascending, n_alive: a
+    Python int -- the call reads it back from the device)."""
+    d_min = skip_threshold(tau, min_optical_depth, "nerf_amd.ray_alive", required=True)
+    if density.dim() != 2 or z.dim() != 2 or z.shape != density.shape or density.shape[1] < 2:
+        raise ValueError("nerf_amd.ray_alive: density and z are (N,C) with C >= 2 (got %s and %s)" % (tuple(density.shape), tuple(z.shape)))
+    N, Cn = density.shape
+    if dirs.dim() != 2 or dirs.shape[0] != N or dirs.shape[1] not in (3, 6):
+        raise ValueError("nerf_amd.ray_alive: dirs is (N,3) directions or the (N,6) ray table (got %s)" % (tuple(dirs.shape),))
+    density, dirs = _dev(density, "density"), _dev(dirs, "dirs")
+    if not (z.is_cuda and z.dtype == torch.float32 and z.stride(1) == 1 and z.stride(0) >= Cn):
+        z = _dev(z, "depths")
+    dev = density.device
+    dirs_ptr = C.c_void_p(dirs.data_ptr() + (12 if dirs.shape[1] == 6 else 0))
+    row_of_ray = torch.empty((N,), dtype=torch.int32, device=dev)
+    ray_of_row = torch.empty((N,), dtype=torch.int64, device=dev)
+    count = torch.empty((1,), dtype=torch.int64, device=dev)
+    ws = torch.empty(max(int(lib.nerf_amd_ray_alive_workspace_bytes(N)), 1), dtype=torch.uint8, device=dev)
+    check(lib.nerf_amd_ray_alive(_ptr(density), _ptr(z), z.stride(0) if N else Cn, dirs_ptr, dirs.shape[1], N, Cn, d_min, _ptr(row_of_ray), _ptr(ray_of_row),
+                                 _ptr(count), _ptr(ws), _stream()), "nerf_amd_ray_alive")
+    n_alive = int(count.item())
+    return row_of_ray, ray_of_row[:n_alive], n_alive
+
+
+def gather_rows(src: torch.Tensor, ray_of_row: torch.Tensor) -> torch.Tensor:
+    """src (N, cols) float32 (rows may be a strided view), ray_of_row (n,) int64 -> (n, cols) = src[ray_of_row] (nerf_amd_gather_rows)"""
+    if src.dim() != 2 or ray_of_row.dim() != 1:
+        raise ValueError("nerf_amd.gather_rows: src is (N, cols), ray_of_row (n,)")
+    if not (src.is_cuda and src.dtype == torch.float32 and src.stride(1) == 1 and src.stride(0) >= src.shape[1]):
+        src = _dev(src, "src")
+    ray_of_row = _dev(ray_of_row, "ray_of_row", torch.int64)
+    n, cols = ray_of_row.shape[0], src.shape[1]
+    dst = torch.empty((n, cols), dtype=torch.float32, device=src.device)
+    check(lib.nerf_amd_gather_rows(_ptr(src), src.stride(0) if src.shape[0] else cols, _ptr(ray_of_row), n, cols, _ptr(dst), _stream()), "nerf_amd_gather_rows")
+    return dst
+
+
 def _render_request(packed_prop, packed_fine, precision, rays, camera, ray_offset, z_base, u_strat, u_inv, N, n_fine, near, far, white_bkg, dev, *,
                     q, want_opacity, want_fine_depths, want_depth, workspace, want_weights=False, prop_pnum=0, spacing=_lib.SPACING_LINEAR, ref=False,
-                    ref_flags=0, cam_dir=None):
+                    ref_flags=0, cam_dir=None, skip_dmin: float = 0.0):
     """The package's one whole-ray render call: nerf_amd_render, which picks the pipeline by `ref`, `prop_pnum` and `spacing`.
     -> (rgb, depth | None, weights | None -- Ref-NeRF: normal_img | None --, workspace: the caller's if it holds the call's bytes, else a new
     one), followed, when a quantile, the opacity or the fine depths are asked for, by {"depth_q" (N,Q) | None, "opacity" (N,) | None,
-    "fine_depths" (N,E) | None}; Ref-NeRF takes its weights output only then, as "weights" of that dict."""
+    "fine_depths" (N,E) | None}; Ref-NeRF takes its weights output only then, as "weights" of that dict.  ``skip_dmin`` > 0 (the empty-ray
+    skip): the dict follows too and also holds "row_of_ray" (N,) int32 and "n_alive" (a Python int)."""
     S = n_fine + (64 if ref else 0)
-    asked = bool(q) or want_opacity or want_fine_depths
+    stats_asked = bool(q) or want_opacity or want_fine_depths
+    asked = stats_asked or skip_dmin > 0.0
     if ref:
-        want_weights = asked
+        want_weights = stats_asked
 
     def out(shape, want=True):
         return torch.empty(shape, dtype=torch.float32, device=dev) if want else None
@@ -906,12 +973,18 @@ def _render_request(packed_prop, packed_fine, precision, rays, camera, ray_offse
             setattr(r, name, t.data_ptr())
     for j, v in enumerate(q):
         r.quantiles[j] = v
+    n_alive = C.c_int64(N)
+    if skip_dmin > 0.0:
+        extras["row_of_ray"] = torch.empty((N,), dtype=torch.int32, device=dev)
+        r.skip_min_optical_depth, r.row_of_ray, r.n_alive = float(skip_dmin), extras["row_of_ray"].data_ptr(), C.pointer(n_alive)
     need = lib.nerf_amd_render_request_workspace_bytes(C.byref(r))
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(need, dtype=torch.uint8, device=dev)
     check(lib.nerf_amd_render(C.byref(r), _ptr(workspace), _stream()), "nerf_amd_render")
     if not asked:
         return rgb, depth, normal_img if ref else w, workspace
+    if skip_dmin > 0.0:
+        extras["n_alive"] = int(n_alive.value) if N else 0
     if ref:
         extras["weights"] = w
     return rgb, depth, normal_img if ref else w, workspace, extras
@@ -920,8 +993,8 @@ def _render_request(packed_prop, packed_fine, precision, rays, camera, ray_offse
 def render_rays(packed_prop, packed_mip, precision, rays, z_base, u_strat, u_inv, n_fine, near, far, white_bkg,
                 want_depth=True, want_weights=False, workspace: Optional[torch.Tensor] = None, camera: Optional[Samples] = None,
                 ray_offset: int = 0, n_rays: Optional[int] = None, contract: bool = False, ipe_radius: Optional[float] = None,
-                seed: Optional[int] = None, rng_ray_offset: int = 0, ipe_dir_norm: Optional[torch.Tensor] = None, *, quantiles=None,
-                want_opacity: bool = False, want_fine_depths: bool = False):
+                seed: Optional[int] = None, rng_ray_offset: int = 0, ipe_dir_norm: Optional[torch.Tensor] = None, *, skip_tau=None,
+                skip_min_optical_depth=None, quantiles=None, want_opacity: bool = False, want_fine_depths: bool = False):
     """The tile body of render_image (procedures.py:64-85) for all given rays in four launches.  `contract`: Mip-NeRF 360 scene
     contraction of every sample position (proposal and fine) before encoding.  `ipe_radius`: the fine pass encodes the conical frusta
     between consecutive fine depths with the integrated PE (mip_methods.py:15-58; explicit `rays` required).
@@ -930,15 +1003,23 @@ def render_rays(packed_prop, packed_mip, precision, rays, z_base, u_strat, u_inv
     ``quantiles`` (up to 4 values in (0, 1)), ``want_opacity``, ``want_fine_depths`` (keyword-only; here and in render_rays_warped,
     _rounds and _ref): when any is set the same launches are followed by ray_depth_stats of the composited weights and depth row, and a
     dict {"depth_q" (N,Q), "opacity" (N,), "fine_depths" (N,E)} (None where not asked for; Ref-NeRF also "weights") follows the usual four
-    results.  The mass is absolute: a ray that never accumulates q reports its far edge.  (All four render through nerf_amd_render.)"""
+    results.  The mass is absolute: a ray that never accumulates q reports its far edge.  (All four render through nerf_amd_render.)
+    ``skip_tau`` / ``skip_min_optical_depth`` (keyword-only, one of them; here, in render_rays_warped and render_rays_ref, and in
+    _render_rays_rounds, the body of render_rays_rounds): the empty-ray skip of
+    include/nerf_amd.h -- the fine network runs only on the rays whose proposal histogram has an optical depth D >= D_min (``skip_tau``: an
+    opacity in (0, 1), D_min = -log1p(-tau)); every output equals the dense call's with the fine network's rows of the skipped rays
+    replaced by zeros, bit for bit (a skipped MipNeRF ray is background, zero weights, opacity 0).  An approximation of the image: its error
+    is the fine opacity of the rays the proposal network calls empty.  The trailing dict then follows and also holds "row_of_ray" (N,) int32
+    (-1: skipped) and "n_alive" (an int).  The call synchronises once with the host and cannot be captured into a graph."""
     q = depth_quantiles(quantiles, "nerf_amd.render_rays")
+    skip_dmin = skip_threshold(skip_tau, skip_min_optical_depth, "nerf_amd.render_rays")
     u_strat, u_inv, seed, dev, N = _render_batch(rays, z_base, u_strat, u_inv, seed, n_rays)
     if ipe_radius is not None and rays is None:
         raise ValueError("nerf_amd: integrated PE needs an explicit ray table")
     camera, _keep = _render_descriptor(camera, contract, ipe_radius, ipe_dir_norm, seed, rng_ray_offset)
     return _render_request(packed_prop, packed_mip, _prop_prec(packed_prop, precision, packed_mip), rays, camera, ray_offset, z_base, u_strat, u_inv, N, n_fine,
                            near, far, white_bkg, dev, q=q, want_opacity=want_opacity, want_fine_depths=want_fine_depths, want_depth=want_depth,
-                           want_weights=want_weights, workspace=workspace)
+                           want_weights=want_weights, workspace=workspace, skip_dmin=skip_dmin)
 
 
 # ------------------------------------------------------------------------------------------------ disparity ray spacing (Mip-NeRF 360 s-space)
@@ -1011,13 +1092,15 @@ def warped_resample(density: torch.Tensor, s_c: torch.Tensor, rays: torch.Tensor
 
 def render_rays_warped(packed_prop, packed_mip, precision, rays, u_strat, u_inv, n_fine, near, far, white_bkg, *, want_depth=True, want_weights=False,
                        workspace: Optional[torch.Tensor] = None, contract: bool = False, ipe_radius: Optional[float] = None, seed: Optional[int] = None,
-                       rng_ray_offset: int = 0, ipe_dir_norm: Optional[torch.Tensor] = None, spacing: str = "disparity", quantiles=None,
-                       want_opacity: bool = False, want_fine_depths: bool = False):
+                       rng_ray_offset: int = 0, ipe_dir_norm: Optional[torch.Tensor] = None, spacing: str = "disparity", skip_tau=None,
+                       skip_min_optical_depth=None, quantiles=None, want_opacity: bool = False, want_fine_depths: bool = False):
     """ops.render_rays under disparity spacing (nerf_amd_render_rays_warped): explicit rays (N,6); ``depth`` is W^-1 of the expected
     metric depth, in [0, 1].  u_strat = u_inv = None with ``seed``: in-kernel Philox uniforms, as in render_rays.  n_fine <= 623 (the
     resampling kernel's LDS rows, include/nerf_amd.h).  ``quantiles`` / ``want_opacity`` / ``want_fine_depths``: as in render_rays; the
-    quantile depths are W^-1 of the metric quantile depths, in the same [0, 1] scale as ``depth``."""
+    quantile depths are W^-1 of the metric quantile depths, in the same [0, 1] scale as ``depth``.  ``skip_tau`` /
+    ``skip_min_optical_depth``: the empty-ray skip, as in render_rays (the histogram's metric depths z_c are used)."""
     q = depth_quantiles(quantiles, "nerf_amd.render_rays_warped")
+    skip_dmin = skip_threshold(skip_tau, skip_min_optical_depth, "nerf_amd.render_rays_warped")
     if _spacing_kind(spacing) != _lib.SPACING_DISPARITY:       # (to nerf_amd_render, linear spacing is the plain pipeline)
         raise ValueError("nerf_amd.render_rays_warped: spacing must be 'disparity' (got %r): linear spacing is render_rays" % (spacing,))
     rays = _dev(rays, "rays")
@@ -1025,7 +1108,7 @@ def render_rays_warped(packed_prop, packed_mip, precision, rays, u_strat, u_inv,
     camera, _keep = _render_descriptor(None, contract, ipe_radius, ipe_dir_norm, seed, rng_ray_offset)
     return _render_request(packed_prop, packed_mip, _prop_prec(packed_prop, precision, packed_mip), rays, camera, 0, None, u_strat, u_inv, N, int(n_fine), near, far,
                            white_bkg, dev, q=q, want_opacity=want_opacity, want_fine_depths=want_fine_depths, want_depth=want_depth, want_weights=want_weights,
-                           workspace=workspace, spacing=_lib.SPACING_DISPARITY)
+                           workspace=workspace, spacing=_lib.SPACING_DISPARITY, skip_dmin=skip_dmin)
 
 
 ROUNDS_PNUM_MIN, ROUNDS_PNUM_MAX = 3, 256      # prop_pnum of nerf_amd_render_rays_rounds (include/nerf_amd.h)
@@ -1040,8 +1123,24 @@ def render_rays_rounds(packed_prop, packed_mip, precision, rays, z_base, n_fine,
     [0, prop_pnum) of each ray's inverse-CDF stream, the proposal network is evaluated there, and the n_fine + 1 fine depths are drawn from
     that second histogram with columns [prop_pnum, prop_pnum + n_fine + 1).  ``z_base`` (64) is read under spacing="linear" only; under
     "disparity" ``depth`` is W^-1 of the expected metric depth.  -> (rgb, depth | None, weights | None, workspace)
-    ``quantiles`` / ``want_opacity`` / ``want_fine_depths``: as in render_rays (the dict then follows the four results)."""
+    ``quantiles`` / ``want_opacity`` / ``want_fine_depths``: as in render_rays (the dict then follows the four results).
+    This function's keyword list is pinned as it stands; the empty-ray skip of render_rays is reached through ``_render_rays_rounds``, the
+    same call with ``skip_tau`` / ``skip_min_optical_depth`` in front (render_image(skip_empty=...) goes that way)."""
+    return _render_rays_rounds(packed_prop, packed_mip, precision, rays, z_base, n_fine, near, far, white_bkg, prop_pnum=prop_pnum, seed=seed,
+                               rng_ray_offset=rng_ray_offset, spacing=spacing, contract=contract, ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm,
+                               want_depth=want_depth, want_weights=want_weights, workspace=workspace, quantiles=quantiles, want_opacity=want_opacity,
+                               want_fine_depths=want_fine_depths)
+
+
+def _render_rays_rounds(packed_prop, packed_mip, precision, rays, z_base, n_fine, near, far, white_bkg, *, prop_pnum, seed, rng_ray_offset: int = 0,
+                        spacing: str = "linear", contract: bool = False, ipe_radius: Optional[float] = None, ipe_dir_norm: Optional[torch.Tensor] = None,
+                        want_depth=True, want_weights=False, workspace: Optional[torch.Tensor] = None, skip_tau=None, skip_min_optical_depth=None,
+                        quantiles=None, want_opacity: bool = False, want_fine_depths: bool = False):
+    """The body of render_rays_rounds, with the empty-ray skip of render_rays: ``skip_tau`` / ``skip_min_optical_depth``, evaluated on the
+    SECOND histogram, the one the fine depths are drawn from; every output equals the dense call's with the skipped rays' fine-network rows
+    replaced by zeros, bit for bit, and the trailing dict also holds "row_of_ray" and "n_alive"."""
     q = depth_quantiles(quantiles, "nerf_amd.render_rays_rounds")
+    skip_dmin = skip_threshold(skip_tau, skip_min_optical_depth, "nerf_amd.render_rays_rounds")
     kind = _spacing_kind(spacing)
     if not ROUNDS_PNUM_MIN <= int(prop_pnum) <= ROUNDS_PNUM_MAX:       # (to nerf_amd_render, prop_pnum = 0 is the one-round pipeline)
         raise ValueError("nerf_amd.render_rays_rounds: prop_pnum must be %d..%d (got %r)" % (ROUNDS_PNUM_MIN, ROUNDS_PNUM_MAX, prop_pnum))
@@ -1050,26 +1149,29 @@ def render_rays_rounds(packed_prop, packed_mip, precision, rays, z_base, n_fine,
     camera, _keep = _render_descriptor(None, contract, ipe_radius, ipe_dir_norm, seed, rng_ray_offset)
     return _render_request(packed_prop, packed_mip, _prop_prec(packed_prop, precision, packed_mip), rays, camera, 0, z_base, None, None, rays.shape[0], int(n_fine),
                            near, far, white_bkg, rays.device, q=q, want_opacity=want_opacity, want_fine_depths=want_fine_depths, want_depth=want_depth,
-                           want_weights=want_weights, workspace=workspace, prop_pnum=int(prop_pnum), spacing=kind)
+                           want_weights=want_weights, workspace=workspace, prop_pnum=int(prop_pnum), spacing=kind, skip_dmin=skip_dmin)
 
 
 def render_rays_ref(packed_prop, packed_ref, precision, rays, z_base, u_strat, u_inv, n_fine, near, far, white_bkg,
                     want_depth=True, cam_dir: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
                     camera: Optional[Samples] = None, ray_offset: int = 0, n_rays: Optional[int] = None, flags: int = 0,
-                    seed: Optional[int] = None, rng_ray_offset: int = 0, contract: bool = False, *, quantiles=None, want_opacity: bool = False,
-                    want_fine_depths: bool = False):
+                    seed: Optional[int] = None, rng_ray_offset: int = 0, contract: bool = False, *, skip_tau=None, skip_min_optical_depth=None,
+                    quantiles=None, want_opacity: bool = False, want_fine_depths: bool = False):
     """The tile body of render_image for a Ref-NeRF fine network (procedures.py:64-85, is_ref_model branch) in six launches.
     `cam_dir` (3,) = render_pose[:, -2] asks for the normal image (procedures.py:79-81).  u_strat = u_inv = None with `seed`: in-kernel
     uniforms as in render_rays.  ``quantiles`` / ``want_opacity`` / ``want_fine_depths``: as in render_rays, on the n_fine + 64 merged
-    depths (an open row); the trailing dict then also holds "weights" (N, n_fine + 64)."""
+    depths (an open row); the trailing dict then also holds "weights" (N, n_fine + 64).  ``skip_tau`` / ``skip_min_optical_depth``: the
+    empty-ray skip, as in render_rays; a skipped ray composites an all-zero row, which under softplus(sigma + 0.5) is a constant density with
+    zero colour, not the background."""
     q = depth_quantiles(quantiles, "nerf_amd.render_rays_ref")
+    skip_dmin = skip_threshold(skip_tau, skip_min_optical_depth, "nerf_amd.render_rays_ref")
     u_strat, u_inv, seed, dev, N = _render_batch(rays, z_base, u_strat, u_inv, seed, n_rays)
     # contract: Mip-NeRF 360 scene contraction of every sample position (the build's own definition); a caller's descriptor keeps its own flag
     camera, _keep = _render_descriptor(camera, True if contract else None, None, None, seed, rng_ray_offset)
     cam_dir = _dev(cam_dir, "cam_dir") if cam_dir is not None else None
     return _render_request(packed_prop, packed_ref, _prop_prec(packed_prop, precision), rays, camera, ray_offset, z_base, u_strat, u_inv, N, n_fine, near, far,
                            white_bkg, dev, q=q, want_opacity=want_opacity, want_fine_depths=want_fine_depths, want_depth=want_depth, workspace=workspace, ref=True,
-                           ref_flags=flags, cam_dir=cam_dir)
+                           ref_flags=flags, cam_dir=cam_dir, skip_dmin=skip_dmin)
 
 
 # ------------------------------------------------------------------------------------------------ backward (SURVEY 8f-1)

@@ -50,7 +50,8 @@ GENERIC_CHUNK_RAYS = 4096
 def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, render_depth, chunk: Optional[int] = None,
                           is_ref_model: bool = False, cam_dir=None, seed: Optional[int] = None, ray_offset: int = 0, contract: bool = False,
                           ipe_radius: Optional[float] = None, ipe_dir_norm=None, *, spacing: str = "linear", prop_rounds: int = 1,
-                          prop_pnum: Optional[int] = None, ipe_cov: str = "metric", depth_quantiles=None, render_opacity: bool = False):
+                          prop_pnum: Optional[int] = None, ipe_cov: str = "metric", skip_min_optical_depth: Optional[float] = None,
+                          depth_quantiles=None, render_opacity: bool = False):
     """The tile body of procedures.py:62-85 as the reference writes it -- stratified depths, ProposalNetwork.forward, get_weights,
     maxBlurFilter, inverseSample, NeRF.length2pts, network.forward, NeRF.render -- on chunks of rays: the route of networks the fused
     render entry (nerf_amd_render_rays) has no packed layout for.  Every call is a HIP kernel of this package; uniforms that were not
@@ -67,11 +68,16 @@ def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sampl
     (MipNeRF.forward_rays); the proposal passes contract positions as before.
     ``depth_quantiles`` / ``render_opacity`` (render_image's): ops.ray_depth_stats of NeRF.render's weights and the depth row it
     composited -- the sample_num + 1 sorted depths with their closing edge, Ref-NeRF the merged open row -- normalised like the depth;
-    when either is set a dict {"depth_q" (N,Q) | None, "opacity" (N,) | None} follows the three results."""
+    when either is set a dict {"depth_q" (N,Q) | None, "opacity" (N,) | None} follows the three results.
+    ``skip_min_optical_depth`` (render_image's ``skip_empty`` as D_min): the empty-ray skip of include/nerf_amd.h on this route --
+    ops.ray_alive on the histogram the fine depths were drawn from, the fine network on the alive rays only (torch indexing gathers its
+    inputs and scatters its rows into zeros: plumbing), compositing on all rays; the same image as the fused routes.  The dict then
+    follows too and also holds "row_of_ray" (N,) int32 and "n_alive"."""
     from .mip_methods import maxBlurFilter
     ops.ipe_contract(contract, ipe_radius, ipe_cov, "nerf_amd.render_image")
     quantiles = ops.depth_quantiles(depth_quantiles, "nerf_amd.render_image")
     want_stats = bool(quantiles) or bool(render_opacity)
+    skip_dmin = ops.skip_threshold(None, skip_min_optical_depth, "nerf_amd.render_image")
     from .utils import inverseSample
     N = rays.shape[0]
     chunk = GENERIC_CHUNK_RAYS if chunk is None else chunk
@@ -80,6 +86,10 @@ def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sampl
     normal_px = torch.empty((N,), dtype=torch.float32, device=rays.device) if cam_dir is not None else None
     stats = {"depth_q": torch.empty((N, len(quantiles)), dtype=torch.float32, device=rays.device) if quantiles else None,
              "opacity": torch.empty((N,), dtype=torch.float32, device=rays.device) if render_opacity else None}
+    if skip_dmin:
+        stats.update(row_of_ray=torch.empty((N,), dtype=torch.int32, device=rays.device), n_alive=0)
+        if ipe_radius is not None and ipe_dir_norm is None:
+            ipe_dir_norm = ops.dirs_norm(rays)                                      # the norm of the whole ray list, not of the alive rays
     resolution = (far - near) / sample_num                                           # procedures.py:57
     warped = _check_spacing(spacing, near, far)
     for s in range(0, N, chunk):
@@ -113,17 +123,35 @@ def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sampl
             fine, _ = inverseSample(prop_w, z, sample_num + 1, sort=True, u=u2.contiguous())
         normal = None
         edges = fine                                                                 # the depth row of the quantiles: the closing edge still on it
+        alive = None                                                                 # the empty-ray skip: the alive rays' indices in this chunk
+        if skip_dmin:
+            row, alive, n_alive = ops.ray_alive(density.reshape(n, -1), z, r, min_optical_depth=skip_dmin)
+            stats["row_of_ray"][s: s + n] = torch.where(row >= 0, row + stats["n_alive"], row)
+            stats["n_alive"] += n_alive
+
+        def on_alive(run, *full):
+            """run(*inputs) on the alive rays' rows of `full`; its outputs scattered into zeros of the chunk's size (dense: run(*full))"""
+            if alive is None:
+                return run(*full)
+            if alive.numel() == 0:
+                return None
+            return tuple(torch.zeros((n,) + o.shape[1:], dtype=o.dtype, device=o.device).index_copy_(0, alive, o) for o in run(*[t[alive].contiguous() for t in full]))
         if is_ref_model:                                                             # :71-74
             samples, fine = NeRF.coarseFineMerge(r, z, fine)
             edges = fine                                                             # (Ref-NeRF: the merged row, open)
-            rgbo, normal = network.forward(samples, contract=True) if contract else network.forward(samples)
+            out = on_alive(lambda sm: tuple(network.forward(sm, contract=True) if contract else network.forward(sm)), samples)
+            S_all = fine.shape[-1]
+            rgbo, normal = out if out is not None else (torch.zeros((n, S_all, 4), device=r.device), torch.zeros((n, S_all, 3), device=r.device))
             rgbo[..., -1] = torch.nn.functional.softplus(rgbo[..., -1] + 0.5)
         elif ipe_radius is not None:                                                  # frusta between the sample_num + 1 sorted depths
-            rgbo = network.forward_rays(r, fine.contiguous(), sample_num, ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, contract=contract, ipe_cov=ipe_cov)
+            out = on_alive(lambda rr, ff: (network.forward_rays(rr, ff, sample_num, ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, contract=contract, ipe_cov=ipe_cov),),
+                           r, fine.contiguous())
+            rgbo = out[0] if out is not None else torch.zeros((n, sample_num, 4), device=r.device)
             fine = fine[..., :-1].contiguous()
         else:
             fine = fine[..., :-1].contiguous()
-            rgbo = network.forward(NeRF.length2pts(r, fine), contract=True) if contract else network.forward(NeRF.length2pts(r, fine))
+            out = on_alive(lambda pp: (network.forward(pp, contract=True) if contract else network.forward(pp),), NeRF.length2pts(r, fine))
+            rgbo = out[0] if out is not None else torch.zeros((n, sample_num, 4), device=r.device)
         part, weights, extras = NeRF.render(rgbo, fine, r[:, 3:], white_bkg=white_bkg, density_act=torch.nn.functional.relu,
                                             render_depth=((0.0, 1.0) if warped else (near, far)) if render_depth else None,
                                             normal_info=(normal, cam_dir) if cam_dir is not None else None)
@@ -140,7 +168,7 @@ def _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sampl
             depth[s: s + n] = (ops.warp_depths(d, near, far, inverse=True, spacing=spacing)[0] if warped else d).reshape(-1)
         if cam_dir is not None:
             normal_px[s: s + n] = extras["normal_img"].reshape(-1)
-    if want_stats:
+    if want_stats or skip_dmin:
         return rgb, depth, normal_px, stats
     return rgb, depth, normal_px
 
@@ -184,7 +212,7 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
                  near: float, far: float, sample_num: int = 128, white_bkg: bool = False, render_depth=False,
                  render_normal=False, rng: str = "philox", contract: bool = False, ipe=False, seed: Optional[int] = None,
                  _shard=None, *, spacing: str = "linear", prop_rounds: int = 1, prop_pnum: Optional[int] = None, ipe_cov: str = "metric",
-                 depth_quantiles=None, render_opacity: bool = False) -> dict:
+                 skip_empty: Optional[float] = None, depth_quantiles=None, render_opacity: bool = False) -> dict:
     """Whole-image inference (procedures.py:34-97) -> {"rgb" (3,H,W) [, "depth_img" (3,H,W)]} on
     ``render_pose.device``.  The caller provides ``no_grad``/``eval()`` like for the reference.
     ``rng``, ``contract`` and ``ipe`` are additions.  ``rng``: where the stratified / inverse-CDF uniforms come from --
@@ -231,9 +259,19 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
     The mass is ABSOLUTE, not renormalised: a ray that never accumulates q (it leaves the scene with opacity < q) reports its far edge.
     ``render_opacity`` (keyword-only; an addition): ``result["opacity_img"]`` (H,W), the accumulated opacity sum_s w_s -- masks, RGBA
     export, background replacement.  Both come from one more kernel on what compositing leaves in the workspace, on every route; with
-    neither set the call and the dict are exactly what they were.  A ``_shard`` call adds "depth_q_rays" (n,Q) and "opacity_rays" (n,)."""
+    neither set the call and the dict are exactly what they were.  A ``_shard`` call adds "depth_q_rays" (n,Q) and "opacity_rays" (n,).
+    ``skip_empty`` (keyword-only; an addition, off by default): an opacity tau in (0, 1) -- the fine network is not run on the rays whose
+    PROPOSAL histogram (the one the fine depths are drawn from) has an opacity below tau, i.e. an optical depth D < -log1p(-tau)
+    (include/nerf_amd.h, tests/skip_empty_ref.py).  Every output equals the dense render's with the fine network's rows of the skipped rays
+    replaced by zeros, bit for bit: an alive pixel is the dense pixel; a skipped MipNeRF pixel is the background colour with zero weights,
+    opacity 0 and the far edge as quantile depth (Ref-NeRF composites softplus(sigma + 0.5): a zero row is a constant density with zero colour
+    there, not the background).  This is an APPROXIMATION of the image: its error is the fine opacity of the rays the proposal network calls
+    empty, so it suits models whose proposal network was trained to bound the fine weights.  The result gains "alive_img" (H,W) bool and
+    "alive_fraction" (a Python float); a ``_shard`` call adds "alive_rays" (n,) bool.  The mask is a pure function of per-ray data: shards
+    reproduce it bit for bit.  The call synchronises once with the host (it reads the alive-ray count) and cannot be captured into a graph."""
     ops.ipe_contract(contract, ipe, ipe_cov, "nerf_amd.render_image")
     quantiles = ops.depth_quantiles(depth_quantiles, "nerf_amd.render_image")
+    skip_dmin = ops.skip_threshold(skip_empty, None, "nerf_amd.render_image")
     render_opacity = bool(render_opacity)
     want_stats = bool(quantiles) or render_opacity
     if prop_rounds not in (1, 2):
@@ -294,11 +332,14 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
     cam_dir = render_pose[:, -2].contiguous() if render_normal else None
     # depth quantiles / opacity: every route takes them as keywords and returns its dict last when either is set
     stat_kw = dict(quantiles=quantiles, want_opacity=render_opacity)
+    if skip_dmin:
+        stat_kw.update(skip_min_optical_depth=skip_dmin)
     if route == "calls":
         out = _render_rays_by_calls(network, prop_net, rays, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, bool(render_depth),
                                     is_ref_model=is_ref_model, cam_dir=cam_dir, seed=seed, ray_offset=off, contract=contract,
                                     ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, spacing=spacing, prop_rounds=prop_rounds,
-                                    prop_pnum=prop_pnum, ipe_cov=ipe_cov, depth_quantiles=quantiles, render_opacity=render_opacity)
+                                    prop_pnum=prop_pnum, ipe_cov=ipe_cov, skip_min_optical_depth=skip_dmin or None, depth_quantiles=quantiles,
+                                    render_opacity=render_opacity)
         rgb, depth, normal_px = out[:3]
     elif route == "ref":
         # procedures.py:71-74: coarse and fine depths are merged and sorted (a merge of two ascending sets), the last one dropped,
@@ -313,13 +354,14 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
         common = dict(want_depth=bool(render_depth), contract=ops.ipe_contract(contract, ipe, ipe_cov), ipe_radius=ipe_radius, ipe_dir_norm=ipe_dir_norm, seed=seed, rng_ray_offset=off,
                       **stat_kw)
         if route == "rounds":
-            out = ops.render_rays_rounds(*packed, z_base, sample_num, near, far, white_bkg, prop_pnum=prop_pnum, spacing=spacing, **common)
+            out = ops._render_rays_rounds(*packed, z_base, sample_num, near, far, white_bkg, prop_pnum=prop_pnum, spacing=spacing, **common)
         elif route == "warped":
             out = ops.render_rays_warped(*packed, u_strat, u_inv, sample_num, near, far, white_bkg, spacing=spacing, **common)
         else:
             out = ops.render_rays(*packed, z_base, u_strat, u_inv, sample_num, near, far, white_bkg, **common)
         rgb, depth = out[:2]
-    stats = out[-1] if want_stats else {"depth_q": None, "opacity": None}
+    stats = out[-1] if (want_stats or skip_dmin) else {"depth_q": None, "opacity": None}
+    alive = stats["row_of_ray"] >= 0 if skip_dmin else None
 
     def to_image(t, ch):
         if sz is None:
@@ -333,6 +375,8 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
         part = {"rgb_rays": rgb, "depth_rays": depth, "normal_rays": normal_px, "range": (off, off + rays.shape[0]), "to_image": to_image}
         if want_stats:
             part.update(depth_q_rays=stats["depth_q"], opacity_rays=stats["opacity"])
+        if skip_dmin:
+            part.update(alive_rays=alive)
         return part
     result = dict()
     result["rgb"] = to_image(rgb, 3)
@@ -344,6 +388,9 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
         result["depth_quantiles"] = to_image(stats["depth_q"], len(quantiles))
     if render_opacity:
         result["opacity_img"] = to_image(stats["opacity"].unsqueeze(-1), 1)[0]
+    if skip_dmin:
+        result["alive_img"] = to_image(alive.to(torch.float32).unsqueeze(-1), 1)[0] > 0.5
+        result["alive_fraction"] = stats["n_alive"] / (H * W)                   # of the image's pixels = alive_img.mean(); the host already has the count
     return result
 
 
@@ -389,7 +436,7 @@ def render_only(args, model_path: str, opt_level: str, dataset_root: str = "../d
             pose[:3, -1] *= args.scene_scale
             with torch.autocast("cuda", dtype=torch.bfloat16, enabled=low_precision):
                 result = render_image(mip_net, prop_net, pose[:3, :], r_c, test_focal, args.near, args.far, 128, white_bkg=args.white_bkg,
-                                      render_normal=render_normal, render_depth=render_depth)
+                                      render_normal=render_normal, render_depth=render_depth, skip_empty=getattr(args, "skip_empty", None))
             if eval_poses:
                 gt_img = testset[i][0].cuda()
                 loss = loss_func(result["rgb"], gt_img)
@@ -423,6 +470,7 @@ def get_parser():
         ("--warmup_step", int, 500, "Warm up step (from lowest lr to starting lr)"), ("--lr", float, 1.5e-4, "Start lr"),
         ("--ide_level", int, 4, "Max level of spherical harmonics to be used"),
         ("--bottle_neck_noise", float, 0.02, "Noise std for perturbing bottle_neck vector"),
+        ("--skip_empty", float, None, "(Render only; an addition) skip the fine network on rays whose proposal opacity is below this tau in (0, 1)"),
     ):
         p.add_argument(name, type=typ, default=default, help=hlp)
     for short, long_, hlp in (
