@@ -208,6 +208,30 @@ int nerf_amd_dirs_norm(const float* rays, int64_t N, float* out, void* stream);
 int nerf_amd_generate_rays(const float* pose_host, int H, int W, float fx, float fy, int64_t ray_offset, int64_t N,
                            float* rays, void* stream);
 
+/* (added after ABI 125; additive) The camera model: principal point, lens distortion, per-view intrinsics.
+ * A camera is a row of NERF_AMD_CAMERA_ROW fp32 values
+ *     fx, fy, cx, cy, k1, k2, k3, p1, p2, 0, 0, 0
+ * with cx, cy in pixels in COLMAP's convention -- the centre of pixel (col, row) is at (col + 0.5, row + 0.5) -- and the last three
+ * entries reserved (a non-zero value there is NERF_AMD_EINVAL).  The distorted image-plane point of a pixel, with true divisions:
+ *     xd = (((float)col + 0.5f) - cx) / fx        yd = (((float)row + 0.5f) - cy) / fy
+ * The forward model (OpenCV / COLMAP), r2 = x^2 + y^2, rad = 1 + r2 (k1 + r2 (k2 + r2 k3)):
+ *     xd = x rad + 2 p1 x y + p2 (r2 + 2 x^2)      yd = y rad + 2 p2 x y + p1 (r2 + 2 y^2)
+ * The undistorted (xu, yu) solves it for (x, y): NERF_AMD_CAMERA_NEWTON_STEPS steps of Newton's method from (xd, yd) with the analytic
+ * 2x2 Jacobian, every one taken (no convergence test), except that a step whose |determinant| is below NERF_AMD_CAMERA_DET_EPS is
+ * skipped.  When all five coefficients are zero no step is taken: (xu, yu) = (xd, yd) exactly.  The ray is o = pose[:,3],
+ * d = R.(xu, -yu, -1): the cameras look down -z with y up; converting a COLMAP world-to-camera pose is the caller's job.
+ * The ray table of nerf_amd_generate_rays adds its 0.5 after the flip, so it IS this model at cx = W/2, cy = H/2 + 1, and the training
+ * samplers are it at cx = W/2 (integer halves), cy = H/2 + 1: every numerator is a small integer or half, exact in fp32, and those
+ * cameras reproduce today's rays bit for bit.  The steps suffice (the fp64 iteration's residual is below 1e-12) where the forward model's
+ * Jacobian determinant stays well away from zero over the image -- above 0.3 for the cameras tests/test_camera_host.py walks through;
+ * tests/camera_ref.py is the fp64 specification and derives the fp32 bounds. */
+#define NERF_AMD_CAMERA_ROW 12
+#define NERF_AMD_CAMERA_NEWTON_STEPS 3
+#define NERF_AMD_CAMERA_DET_EPS 1e-6f
+/* nerf_amd_generate_rays for one camera row (HOST, validated: finite, fx, fy > 0, zero tail): same indexing, rays (N, 6). */
+int nerf_amd_generate_rays_camera(const float* pose_host, int H, int W, const float* camera_host, int64_t ray_offset, int64_t N, float* rays,
+                                  void* stream);
+
 /* NeRF.length2pts (nerf_base.py:53-56): out (N, S, 6) = [o + z d | d]. */
 int nerf_amd_length2pts(const float* rays, const float* z, int64_t N, int S, float* out, void* stream);
 
@@ -264,6 +288,15 @@ int nerf_amd_philox_uniforms(float* out, int64_t N, int K, uint64_t rng_seed, co
 int nerf_amd_sample_scene_rays(const float* images, const float* poses, int64_t V, int H, int W, const int64_t* view_ids, int64_t K, int x0,
                                int x1, int y0, int y1, float fx, float fy, float near, float far, int64_t N, int C, uint64_t rng_seed,
                                const uint64_t* seed_dev, float* pts, float* lengths, float* rgb, float* rays, int64_t* index, void* stream);
+/* (added after ABI 125; additive) nerf_amd_sample_scene_rays with per-view cameras: `cameras` (V, NERF_AMD_CAMERA_ROW) fp32 on the DEVICE,
+ * row v the camera of view v (the model above), read when the kernel runs -- the host never sees its values, so a captured step replays
+ * with whatever the table then holds.  rays (N,6) = [poses[v][:,3] | R_v.(xu, -yu, -1)] of pixel (col, row) under cameras[v]; every
+ * draw, the window, view_ids, index, rgb, lengths and pts are nerf_amd_sample_scene_rays' own (the same Philox words).  With every row
+ * (fx, fy, W/2, H/2 + 1, 0 ...) in integer halves the outputs are bit-identical to nerf_amd_sample_scene_rays. */
+int nerf_amd_sample_scene_rays_camera(const float* images, const float* poses, int64_t V, int H, int W, const int64_t* view_ids, int64_t K, int x0,
+                                      int x1, int y0, int y1, const float* cameras, float near, float far, int64_t N, int C, uint64_t rng_seed,
+                                      const uint64_t* seed_dev, float* pts, float* lengths, float* rgb, float* rays, int64_t* index,
+                                      void* stream);
 /* (ABI 121) Either Philox stream of the render kernels as a tensor, for rows that are GLOBAL rays ray_offset .. ray_offset + N - 1: the
  * uniforms the reference draws per tile with torch.rand (procedures.py:65 stratified jitter -> NERF_AMD_PHILOX_STRAT, K <= 64;
  * utils.py:115 inverse-CDF -> NERF_AMD_PHILOX_INV), bit-identical to what nerf_amd_render_rays draws in place for the same seed and ray

@@ -87,6 +87,9 @@ SIGNATURES = {
                                                    c_void, c_void, c_void, c_void, c_void]),
     "nerf_amd_sample_scene_rays": (C.c_int, [c_void, c_void, i64, C.c_int, C.c_int, c_void, i64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float,
                                             C.c_float, C.c_float, i64, C.c_int, C.c_uint64, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
+    "nerf_amd_generate_rays_camera": (C.c_int, [c_float_p, C.c_int, C.c_int, c_float_p, i64, i64, c_void, c_void]),
+    "nerf_amd_sample_scene_rays_camera": (C.c_int, [c_void, c_void, i64, C.c_int, C.c_int, c_void, i64, C.c_int, C.c_int, C.c_int, C.c_int, c_void,
+                                                   C.c_float, C.c_float, i64, C.c_int, C.c_uint64, c_void, c_void, c_void, c_void, c_void, c_void, c_void]),
     "nerf_amd_philox_uniforms": (C.c_int, [c_void, i64, C.c_int, C.c_uint64, c_void, c_void]),
     "nerf_amd_philox_stream": (C.c_int, [c_void, i64, C.c_int, C.c_uint64, c_void, i64, C.c_int, c_void]),
     "nerf_amd_advance_seed": (C.c_int, [c_void, c_void]),
@@ -181,7 +184,8 @@ SIGNATURES = {
 # additive entry points that a library named by NERF_AMD_LIB may predate
 ADDED_AFTER_125 = ("nerf_amd_direction_table", "nerf_amd_render_rounds_workspace_bytes", "nerf_amd_render_rays_rounds",
                    "nerf_amd_ipe_feature_gaussian", "nerf_amd_ray_depth_stats", "nerf_amd_render_request_workspace_bytes", "nerf_amd_render",
-                   "nerf_amd_ray_alive_workspace_bytes", "nerf_amd_ray_alive", "nerf_amd_gather_rows")
+                   "nerf_amd_ray_alive_workspace_bytes", "nerf_amd_ray_alive", "nerf_amd_gather_rows", "nerf_amd_generate_rays_camera",
+                   "nerf_amd_sample_scene_rays_camera")
 
 
 def _load():

@@ -248,6 +248,27 @@ int nerf_amd_generate_rays(const float* pose_host, int H, int W, float fx, float
     return hip_status(sk_generate_rays(pose_host, H, W, fx, fy, ray_offset, N, rays, S(stream)), "nerf_amd_generate_rays");
 }
 
+// a HOST camera row (nerf_amd.h): finite, fx, fy > 0, reserved tail zero
+static int check_camera_row(const char* name, const float* c) {
+    if (!c) return fail(NERF_AMD_EINVAL, "%s: camera is NULL", name);
+    for (int i = 0; i < NERF_AMD_CAMERA_ROW; ++i)
+        if (!(c[i] - c[i] == 0.0f)) return fail(NERF_AMD_EINVAL, "%s: camera has a non-finite value", name);
+    if (!(c[0] > 0.0f && c[1] > 0.0f)) return fail(NERF_AMD_EINVAL, "%s: camera needs fx, fy > 0", name);
+    for (int i = 9; i < NERF_AMD_CAMERA_ROW; ++i)
+        if (c[i] != 0.0f) return fail(NERF_AMD_EINVAL, "%s: camera reserved tail (entries 9..11) must be zero", name);
+    return NERF_AMD_OK;
+}
+int nerf_amd_generate_rays_camera(const float* pose_host, int H, int W, const float* camera_host, int64_t ray_offset, int64_t N, float* rays,
+                                  void* stream) {
+    const char* name = "nerf_amd_generate_rays_camera";
+    if (!pose_host) return fail(NERF_AMD_EINVAL, "%s: pose_host is NULL", name);
+    if (!rays) return fail(NERF_AMD_EINVAL, "%s: rays is NULL", name);
+    if (H <= 0 || W <= 0) return fail(NERF_AMD_EINVAL, "%s: H, W must be positive", name);
+    if (int e = check_camera_row(name, camera_host)) return e;
+    if (ray_offset < 0 || N < 0 || ray_offset + N > (int64_t)H * W) return fail(NERF_AMD_EINVAL, "%s: ray range outside the image", name);
+    return hip_status(sk_generate_rays_camera(pose_host, H, W, camera_host, ray_offset, N, rays, S(stream)), name);
+}
+
 int nerf_amd_length2pts(const float* rays, const float* z, int64_t N, int Sn, float* out, void* stream) {
     if (N < 0 || Sn < 0) return fail(NERF_AMD_EINVAL, "negative size");
     if (N * Sn && (!rays || !z || !out)) return fail(NERF_AMD_EINVAL, "NULL argument");
@@ -309,25 +330,42 @@ int nerf_amd_sample_training_rays_dev(const float* rgbs, const int64_t* coords, 
     return train_sampler_any(rgbs, coords, n_pixels, nullptr, pose_dev, fx, fy, near, far, N, C, 0, seed_dev, pts, lengths, rgb, rays, stream,
                              "nerf_amd_sample_training_rays_dev");
 }
+// the argument checks nerf_amd_sample_scene_rays and its camera twin share (everything but the intrinsics), named for the caller
+static int check_scene_sampler(const char* name, const float* images, const float* poses, int64_t V, int H, int W, const int64_t* view_ids, int64_t K, int x0, int x1,
+                               int y0, int y1, int64_t N, int C, const float* pts, const float* lengths, const float* rgb, const float* rays) {
+    if (!images) return fail(NERF_AMD_EINVAL, "%s: images is NULL", name);
+    if (!poses) return fail(NERF_AMD_EINVAL, "%s: poses is NULL", name);
+    if (V < 1 || H < 1 || W < 1) return fail(NERF_AMD_EINVAL, "%s: V, H, W must be positive", name);
+    if (K < 1 || (!view_ids && K > V)) return fail(NERF_AMD_EINVAL, "%s: need 1 <= K (and K <= V without view_ids)", name);
+    if (x0 < 0 || x1 > W || x0 >= x1) return fail(NERF_AMD_EINVAL, "%s: window x0, x1 empty or outside the image (0 <= x0 < x1 <= W)", name);
+    if (y0 < 0 || y1 > H || y0 >= y1) return fail(NERF_AMD_EINVAL, "%s: window y0, y1 empty or outside the image (0 <= y0 < y1 <= H)", name);
+    if (N < 0) return fail(NERF_AMD_EINVAL, "%s: N is negative", name);
+    if (C < 0) return fail(NERF_AMD_EINVAL, "%s: C is negative", name);
+    if (pts && !lengths) return fail(NERF_AMD_EINVAL, "%s: pts given without lengths", name);
+    if (lengths && C > 0 && !pts) return fail(NERF_AMD_EINVAL, "%s: lengths given without pts", name);
+    if (!rgb) return fail(NERF_AMD_EINVAL, "%s: rgb is NULL", name);
+    if (!rays) return fail(NERF_AMD_EINVAL, "%s: rays is NULL", name);
+    return NERF_AMD_OK;
+}
 int nerf_amd_sample_scene_rays(const float* images, const float* poses, int64_t V, int H, int W, const int64_t* view_ids, int64_t K, int x0, int x1,
                                int y0, int y1, float fx, float fy, float near, float far, int64_t N, int C, uint64_t rng_seed,
                                const uint64_t* seed_dev, float* pts, float* lengths, float* rgb, float* rays, int64_t* index, void* stream) {
-    if (!images) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: images is NULL");
-    if (!poses) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: poses is NULL");
-    if (V < 1 || H < 1 || W < 1) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: V, H, W must be positive");
-    if (K < 1 || (!view_ids && K > V)) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: need 1 <= K (and K <= V without view_ids)");
-    if (x0 < 0 || x1 > W || x0 >= x1) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: window x0, x1 empty or outside the image (0 <= x0 < x1 <= W)");
-    if (y0 < 0 || y1 > H || y0 >= y1) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: window y0, y1 empty or outside the image (0 <= y0 < y1 <= H)");
-    if (N < 0) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: N is negative");
-    if (C < 0) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: C is negative");
-    if (pts && !lengths) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: pts given without lengths");
-    if (lengths && C > 0 && !pts) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: lengths given without pts");
-    if (!rgb) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: rgb is NULL");
-    if (!rays) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays: rays is NULL");
+    if (int e = check_scene_sampler("nerf_amd_sample_scene_rays", images, poses, V, H, W, view_ids, K, x0, x1, y0, y1, N, C, pts, lengths, rgb, rays)) return e;
     if (N == 0) return NERF_AMD_OK;
     return hip_status(sk_scene_sampler(images, poses, V, H, W, view_ids, K, x0, x1, y0, y1, fx, fy, near, far, N, C, rng_seed, seed_dev, pts, lengths, rgb,
                                        rays, index, S(stream)),
                       "nerf_amd_sample_scene_rays");
+}
+// the device table's values are the caller's: only the pointer can be checked here
+int nerf_amd_sample_scene_rays_camera(const float* images, const float* poses, int64_t V, int H, int W, const int64_t* view_ids, int64_t K, int x0, int x1,
+                                      int y0, int y1, const float* cameras, float near, float far, int64_t N, int C, uint64_t rng_seed,
+                                      const uint64_t* seed_dev, float* pts, float* lengths, float* rgb, float* rays, int64_t* index, void* stream) {
+    if (int e = check_scene_sampler("nerf_amd_sample_scene_rays_camera", images, poses, V, H, W, view_ids, K, x0, x1, y0, y1, N, C, pts, lengths, rgb, rays)) return e;
+    if (!cameras) return fail(NERF_AMD_EINVAL, "nerf_amd_sample_scene_rays_camera: cameras is NULL");
+    if (N == 0) return NERF_AMD_OK;
+    return hip_status(sk_scene_sampler_camera(images, poses, cameras, V, H, W, view_ids, K, x0, x1, y0, y1, near, far, N, C, rng_seed, seed_dev, pts, lengths,
+                                              rgb, rays, index, S(stream)),
+                      "nerf_amd_sample_scene_rays_camera");
 }
 int nerf_amd_philox_uniforms(float* out, int64_t N, int K, uint64_t rng_seed, const uint64_t* seed_dev, void* stream) {
     if (N < 0 || K < 0) return fail(NERF_AMD_EINVAL, "negative size");

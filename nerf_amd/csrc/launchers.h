@@ -66,6 +66,10 @@ int sk_train_sampler(const float* rgbs, const int64_t* coords, int64_t P, const 
                      uint64_t seed, const uint64_t* seed_dev, float* pts, float* lengths, float* rgb, float* rays, hipStream_t st);
 int sk_scene_sampler(const float* images, const float* poses, int64_t V, int H, int W, const int64_t* view_ids, int64_t K, int x0, int x1, int y0, int y1, float fx, float fy, float near,
                      float far, int64_t N, int C, uint64_t seed, const uint64_t* seed_dev, float* pts, float* lengths, float* rgb, float* rays, int64_t* index, hipStream_t st);
+int sk_scene_sampler_camera(const float* images, const float* poses, const float* cameras, int64_t V, int H, int W, const int64_t* view_ids, int64_t K, int x0, int x1, int y0, int y1,
+                            float near, float far, int64_t N, int C, uint64_t seed, const uint64_t* seed_dev, float* pts, float* lengths, float* rgb, float* rays, int64_t* index,
+                            hipStream_t st);
+int sk_generate_rays_camera(const float* pose, int H, int W, const float* camera, int64_t first, int64_t count, float* rays, hipStream_t st);
 int sk_philox_normal(float* out, int64_t M, uint64_t seed, const uint64_t* seed_dev, float std, int64_t sample_offset, hipStream_t st);
 int sk_philox_uniforms(float* out, int64_t N, int K, uint64_t seed, const uint64_t* seed_dev, int64_t ray_offset, int strat, hipStream_t st);
 int sk_advance_seed(uint64_t* seed_dev, hipStream_t st);

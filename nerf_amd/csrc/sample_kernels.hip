@@ -197,6 +197,53 @@ __global__ void pixel_rays_kernel(Cam cam, const int64_t* __restrict__ coords, i
     }
 }
 
+// ---------------------------------------------------------------------------------------- camera model (include/nerf_amd.h)
+// A camera row of NERF_AMD_CAMERA_ROW floats: fx fy cx cy k1 k2 k3 p1 p2 (+ reserved zeros).  The one definition of pixel -> ray for every
+// kernel that takes a camera row: the distorted image-plane point of the pixel centre, COLMAP's convention, then the OpenCV model
+//   xd = x rad + 2 p1 x y + p2 (r2 + 2 x^2),  yd = y rad + 2 p2 x y + p1 (r2 + 2 y^2),  rad = 1 + r2 (k1 + r2 (k2 + r2 k3))
+// solved for (x, y) by NERF_AMD_CAMERA_NEWTON_STEPS Newton steps from (xd, yd) with the analytic Jacobian (a step whose |det| is below
+// NERF_AMD_CAMERA_DET_EPS is skipped); all five coefficients zero: no step, (x, y) = (xd, yd) exactly.  Plain mul / add / div in the
+// order written (the build contracts nothing): tests/camera_ref.py restates it operation by operation.
+struct CameraRow { float v[NERF_AMD_CAMERA_ROW]; };
+DEVINL void pixel_camera_ray(int col, int row, const float* cam, const float* pose, float* r) {
+    const float fx = cam[0], fy = cam[1], k1 = cam[4], k2 = cam[5], k3 = cam[6], p1 = cam[7], p2 = cam[8];
+    const float xd = (((float)col + 0.5f) - cam[2]) / fx;
+    const float yd = (((float)row + 0.5f) - cam[3]) / fy;
+    float x = xd, y = yd;
+    if (k1 != 0.0f || k2 != 0.0f || k3 != 0.0f || p1 != 0.0f || p2 != 0.0f) {
+#pragma unroll 1
+        for (int it = 0; it < NERF_AMD_CAMERA_NEWTON_STEPS; ++it) {
+            const float xx = x * x, yy = y * y, xy = x * y;
+            const float r2 = xx + yy;
+            const float rad = 1.0f + r2 * (k1 + r2 * (k2 + r2 * k3));
+            const float drad = k1 + r2 * (2.0f * k2 + r2 * (3.0f * k3));                 // d rad / d r2
+            const float ex = ((x * rad + (2.0f * p1) * xy) + p2 * (r2 + 2.0f * xx)) - xd;
+            const float ey = ((y * rad + (2.0f * p2) * xy) + p1 * (r2 + 2.0f * yy)) - yd;
+            const float jxx = ((rad + (2.0f * xx) * drad) + (2.0f * p1) * y) + (6.0f * p2) * x;
+            const float jyy = ((rad + (2.0f * yy) * drad) + (2.0f * p2) * x) + (6.0f * p1) * y;
+            const float jxy = ((2.0f * xy) * drad + (2.0f * p1) * x) + (2.0f * p2) * y;   // = d ex / d y = d ey / d x
+            const float det = jxx * jyy - jxy * jxy;
+            if (!(fabsf(det) >= NERF_AMD_CAMERA_DET_EPS)) continue;
+            x = x - (jyy * ex - jxy * ey) / det;
+            y = y - (jxx * ey - jxy * ex) / det;
+        }
+    }
+    camera_ray(pose, x, -y, r);
+}
+
+// row 1 for one camera row: raygen_kernel's indexing (rays n = row W + col of [first, first + count)); the camera travels in the launch
+// arguments, so its reads are wave-uniform
+__global__ __launch_bounds__(256) void raygen_camera_kernel(CameraRow cam, Cam pose, int64_t first, int64_t count, float* __restrict__ out) {
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t n = first + i;
+        const int row = (int)(n / pose.W), col = (int)(n - (int64_t)row * pose.W);
+        float r[6];
+        pixel_camera_ray(col, row, cam.v, pose.pose, r);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) out[i * 6 + k] = r[k];
+    }
+}
+
 // row 2 (utils.py:87-90 / procedures.py:65-66): z = z_base + u*jitter ; pts = o + d*z
 __global__ void stratified_points_kernel(const float* __restrict__ rays, const float* __restrict__ z_base,
                                          const float* __restrict__ u, float jitter, int64_t N, int S,
@@ -302,6 +349,54 @@ __global__ __launch_bounds__(256) void scene_sampler_kernel(const float* __restr
             if (v >= 0 && v < V) {
                 sampler_ray(poses + v * 12, fx, fy, (float)(col - W / 2), (float)(H / 2 - row), q, rays + n * 6);
                 const float* px = images + ((v * 3) * (int64_t)H + row) * W + col;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) rgb[n * 3 + c] = px[(int64_t)c * H * W];
+                if (index != nullptr) index[n] = (v * H + row) * W + col;
+            } else {
+                const float nan = __builtin_nanf("");
+#pragma unroll
+                for (int c = 0; c < 6; ++c) { q[c] = nan; rays[n * 6 + c] = nan; }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) rgb[n * 3 + c] = nan;
+                if (index != nullptr) index[n] = -1;
+            }
+        }
+        __syncthreads();
+        if (lengths == nullptr) continue;
+        sampler_samples(n0, N, C, seed, near, res, ray_s, lengths, pts);
+    }
+}
+
+// The camera twin of scene_sampler_kernel: view v's ray goes through pixel_camera_ray with row v of `cameras` (V, NERF_AMD_CAMERA_ROW), a
+// DEVICE table read when the kernel runs (a captured step replays with it).  Everything else is scene_sampler_kernel's: the same Philox
+// words, cell -> (view, row, col) decode, window, view_ids, NaN / -1 for a view id outside [0, V), index and stratified depths.
+__global__ __launch_bounds__(256) void scene_sampler_camera_kernel(const float* __restrict__ images, const float* __restrict__ poses,
+                                                                   const float* __restrict__ cameras, int64_t V, int H, int W,
+                                                                   const int64_t* __restrict__ view_ids, int64_t K, int x0, int ww, int y0, int64_t wp,
+                                                                   float near, float res, int64_t N, int C, uint64_t seed,
+                                                                   const uint64_t* __restrict__ seed_dev, float* __restrict__ pts, float* __restrict__ lengths,
+                                                                   float* __restrict__ rgb, float* __restrict__ rays, int64_t* __restrict__ index) {
+    __shared__ float ray_s[4][6];
+    if (seed_dev != nullptr) seed = seed_dev[0];
+    // the key lives in vector registers: as a wave-uniform value Philox's whole key schedule (two words for each of ten rounds) is hoisted
+    // into scalar registers, which with this argument list spills some of them (the same words come out either way)
+    asm volatile("" : "+v"(seed));
+    const uint64_t P = (uint64_t)K * (uint64_t)wp;
+    for (int64_t n0 = blockIdx.x * (int64_t)4; n0 < N; n0 += (int64_t)gridDim.x * 4) {
+        __syncthreads();
+        if (threadIdx.x < 4 && n0 + threadIdx.x < N) {
+            const int64_t n = n0 + threadIdx.x;
+            const int64_t cell = (int64_t)__umul64hi(sampler_index_word(n, seed), P);               // uniform in [0, K wp)
+            const int64_t k = cell / wp, r = cell - k * wp;
+            const int64_t wr = r / ww;
+            const int64_t row = y0 + wr, col = x0 + (r - wr * ww);
+            const int64_t v = view_ids != nullptr ? view_ids[k] : k;
+            float* q = ray_s[threadIdx.x];
+            if (v >= 0 && v < V) {
+                pixel_camera_ray((int)col, (int)row, cameras + v * NERF_AMD_CAMERA_ROW, poses + v * 12, q);
+                const float* px = images + ((v * 3) * (int64_t)H + row) * W + col;
+#pragma unroll
+                for (int c = 0; c < 6; ++c) rays[n * 6 + c] = q[c];
 #pragma unroll
                 for (int c = 0; c < 3; ++c) rgb[n * 3 + c] = px[(int64_t)c * H * W];
                 if (index != nullptr) index[n] = (v * H + row) * W + col;
@@ -2203,6 +2298,18 @@ int nk::sk_scene_sampler(const float* images, const float* poses, int64_t V, int
     return (int)hipGetLastError();
 }
 
+// `cameras`: (V, NERF_AMD_CAMERA_ROW) on the device; the window as in sk_scene_sampler
+int nk::sk_scene_sampler_camera(const float* images, const float* poses, const float* cameras, int64_t V, int H, int W, const int64_t* view_ids, int64_t K, int x0,
+                            int x1, int y0, int y1, float near, float far, int64_t N, int C, uint64_t seed, const uint64_t* seed_dev, float* pts, float* lengths,
+                            float* rgb, float* rays, int64_t* index, hipStream_t st) {
+    if (N == 0) return 0;
+    const int ww = x1 - x0;
+    const int64_t wp = (int64_t)(y1 - y0) * ww;
+    hipLaunchKernelGGL(scene_sampler_camera_kernel, dim3(blocks_for(N, 4)), dim3(256), 0, st, images, poses, cameras, V, H, W, view_ids, K, x0, ww, y0, wp, near,
+                       C > 0 ? (far - near) / (float)C : 0.0f, N, C, seed, seed_dev, pts, C > 0 ? lengths : nullptr, rgb, rays, index);
+    return (int)hipGetLastError();
+}
+
 // Philox uniforms as a tensor, u (N,K) = the inverse-CDF stream of device_common.h (philox_u_inv) -- for callers that keep the
 // reference's op-by-op structure (inverseSample(weights, depths, u)) but want the draw on the device and, with `seed_dev`, replayable
 // from a captured graph.  One thread per element.
@@ -2261,6 +2368,16 @@ int nk::sk_generate_rays(const float* pose, int H, int W, float fx, float fy, in
     for (int i = 0; i < 12; ++i) c.pose[i] = pose[i];
     if (count == 0) return 0;
     hipLaunchKernelGGL(raygen_kernel, dim3(blocks_for(count, 256)), dim3(256), 0, st, c, first, count, rays);
+    return (int)hipGetLastError();
+}
+// `camera`: a HOST row of NERF_AMD_CAMERA_ROW floats (validated by the caller)
+int nk::sk_generate_rays_camera(const float* pose, int H, int W, const float* camera, int64_t first, int64_t count, float* rays, hipStream_t st) {
+    Cam c; c.H = H; c.W = W; c.fx = camera[0]; c.fy = camera[1];
+    for (int i = 0; i < 12; ++i) c.pose[i] = pose[i];
+    CameraRow row;
+    for (int i = 0; i < NERF_AMD_CAMERA_ROW; ++i) row.v[i] = camera[i];
+    if (count == 0) return 0;
+    hipLaunchKernelGGL(raygen_camera_kernel, dim3(blocks_for(count, 256)), dim3(256), 0, st, row, c, first, count, rays);
     return (int)hipGetLastError();
 }
 int nk::sk_pixel_rays(const float* pose, float fx, float fy, const int64_t* coords, int64_t N, float* rays, hipStream_t st) {

@@ -401,6 +401,36 @@ def generate_rays(pose: torch.Tensor, H: int, W: int, fx: float, fy: float, devi
     return rays
 
 
+def generate_camera_rays(pose: torch.Tensor, H: int, W: int, camera, device, ray_offset: int = 0, n: Optional[int] = None) -> torch.Tensor:
+    """generate_rays for a ``nerf_amd.camera.Camera`` (principal point, lens distortion; nerf_amd_generate_rays_camera): rays (n, 6) of
+    pixels ray_offset .. ray_offset + n - 1 in raster order.  ``Camera.reference(H, W, focal)`` gives generate_rays' bits."""
+    n = H * W - ray_offset if n is None else n
+    host = (C.c_float * 12)(*pose.detach().float().cpu().reshape(-1).tolist()[:12])
+    row = (C.c_float * 12)(*camera.row())
+    rays = torch.empty((n, 6), dtype=torch.float32, device=device)
+    check(lib.nerf_amd_generate_rays_camera(host, H, W, row, ray_offset, n, _ptr(rays), _stream()), "nerf_amd_generate_rays_camera")
+    return rays
+
+
+def scene_cameras(cameras, n_views: int, device) -> Optional[torch.Tensor]:
+    """``cameras`` of sample_scene_rays / TrainStep as the (V, 12) fp32 device table the kernel reads (None stays None): one Camera shared
+    by all views, a sequence of V cameras, or a device tensor of that form, which is taken as it is (the caller vouches for its rows)."""
+    from .camera import ROW, Camera
+    if cameras is None:
+        return None
+    if isinstance(cameras, torch.Tensor):
+        if not (cameras.is_cuda and cameras.dtype == torch.float32 and cameras.is_contiguous() and tuple(cameras.shape) == (n_views, ROW)
+                and cameras.device == torch.device(device)):
+            raise ValueError("nerf_amd: a 'cameras' tensor must be a contiguous (V, %d) fp32 tensor on the images' device, V = %d" % (ROW, n_views))
+        return cameras
+    if isinstance(cameras, Camera):
+        cameras = [cameras] * n_views
+    cameras = list(cameras)
+    if len(cameras) != n_views:
+        raise ValueError("nerf_amd: 'cameras' needs one Camera per view (%d), got %d" % (n_views, len(cameras)))
+    return Camera.table(cameras, device)
+
+
 def length2pts(rays: torch.Tensor, z: torch.Tensor) -> torch.Tensor:
     rays, z = _dev(rays, "rays"), _dev(z, "z")
     N, S = z.shape
@@ -517,14 +547,17 @@ def scene_view_ids(view_ids, n_views: int, device) -> Optional[torch.Tensor]:
 
 def sample_scene_rays(images: torch.Tensor, poses: torch.Tensor, fx: float, fy: float, near: float, far: float, n_rays: int, n_points: int,
                       seed: int = 0, seed_dev: Optional[torch.Tensor] = None, window=None, view_ids=None, want_samples: bool = True,
-                      want_index: bool = True, index_out: Optional[torch.Tensor] = None):
+                      want_index: bool = True, index_out: Optional[torch.Tensor] = None, cameras=None):
     """The training batch drawn uniformly over ALL pixels of a scene in one launch (nerf_amd_sample_scene_rays): images (V,3,H,W) fp32
     planar and poses (V,3,4) fp32, contiguous device tensors read in place (they are never copied or converted: anything else raises).
     ``window`` = (x0, x1, y0, y1), columns x0..x1-1 and rows y0..y1-1 of every view (None: the whole image); ``view_ids``: the views to
     draw from (None: all V).  A list or CPU tensor is range-checked against V and uploaded; a DEVICE int64 tensor is taken as it is --
     the caller vouches for its entries (an entry outside [0, V) yields NaN rays with index -1, nothing is read).  Key: ``seed``, or the
     (1,) int64 device tensor ``seed_dev`` read when the kernel RUNS (replayable from a captured hipGraph).  ``index_out``: a persistent
-    (N,) int64 device tensor to write the indices into instead of a fresh one.
+    (N,) int64 device tensor to write the indices into instead of a fresh one.  ``cameras`` (None: the pinhole ``fx, fy`` of the integer-half
+    sampler table, the kernel as it was): one ``nerf_amd.camera.Camera`` for all views, V of them, or a (V,12) fp32 device table read when
+    the kernel RUNS -- each view's rays then follow its own principal point and lens distortion (nerf_amd_sample_scene_rays_camera) and
+    ``fx, fy`` are ignored; every draw stays what it was.
     -> (pts (N,C,3) | None, lengths (N,C) | None, rgb (N,3), rays (N,6), index (N,) int64 = (v H + row) W + col | None)"""
     for t, name, tail in ((images, "images", (3,)), (poses, "poses", (3, 4))):
         if not (isinstance(t, torch.Tensor) and t.is_cuda):
@@ -553,7 +586,14 @@ def sample_scene_rays(images: torch.Tensor, poses: torch.Tensor, fx: float, fy: 
                 and index_out.device == dev):
             raise ValueError("nerf_amd: index_out must be a contiguous (n_rays,) int64 tensor on the images' device")
         index = index_out
+    cameras = scene_cameras(cameras, V, dev)
     if n_rays == 0:                                           # (empty tensors have no address to hand over; the entry point launches nothing either)
+        return pts, z, rgb, rays, index
+    if cameras is not None:
+        check(lib.nerf_amd_sample_scene_rays_camera(_ptr(images), _ptr(poses), V, H, W, _ptr(view_ids), K, x0, x1, y0, y1, _ptr(cameras), float(near),
+                                                    float(far), n_rays, n_points if samples else 0, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(seed_dev),
+                                                    _ptr(pts), _ptr(z), _ptr(rgb), _ptr(rays), _ptr(index), _stream()),
+              "nerf_amd_sample_scene_rays_camera")
         return pts, z, rgb, rays, index
     check(lib.nerf_amd_sample_scene_rays(_ptr(images), _ptr(poses), V, H, W, _ptr(view_ids), K, x0, x1, y0, y1, float(fx), float(fy), float(near),
                                          float(far), n_rays, n_points if samples else 0, int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(seed_dev), _ptr(pts),

@@ -237,7 +237,7 @@ def broadcast_parameters(modules: Sequence[torch.nn.Module], src: int = 0, group
 def render_image_sharded(network, prop_net, render_pose, image_size, focal, near, far, sample_num=128, white_bkg=False,
                          render_depth=False, gather: bool = True, seed: int = 0, group=None, render_normal=False, contract: bool = False,
                          ipe=False, *, spacing: str = "linear", prop_rounds: int = 1, prop_pnum: Optional[int] = None, ipe_cov: str = "metric",
-                         skip_empty: Optional[float] = None, depth_quantiles=None, render_opacity: bool = False) -> dict:
+                         skip_empty: Optional[float] = None, camera=None, depth_quantiles=None, render_opacity: bool = False) -> dict:
     """Ray-sharded whole-image render: rank r renders a contiguous 256-aligned slice of the image's (tile-ordered) ray list through
     ``procedures.render_image``'s own body -- MipNeRF, Ref-NeRF and layer-by-layer networks alike.  Every uniform is drawn in the kernels
     with Philox keyed by (``seed``, GLOBAL ray index), so the gathered image does not depend on the world size: it is bit-identical to
@@ -251,7 +251,8 @@ def render_image_sharded(network, prop_net, render_pose, image_size, focal, near
     (gather=False: "depth_q_rays", "opacity_rays").  ``skip_empty`` is render_image's: whether a ray is skipped is a pure function of that ray's
     own histogram and direction, so the shards reproduce the single-process image and mask bit for bit; "alive_img" (H,W) bool and
     "alive_fraction" are gathered (gather=False: "alive_rays").  With it on the shards are UNEVENLY LOADED: each runs the fine network on
-    its own alive rays only, and a rank whose slice is background finishes early and waits in the gather."""
+    its own alive rays only, and a rank whose slice is background finishes early and waits in the gather.  ``camera`` is render_image's: every
+    rank forms the whole ray table from it and cuts its slice, so the shards reproduce the single call."""
     from . import ops
     from .procedures import get_patch_size, render_image
     ops.ipe_contract(contract, ipe, ipe_cov, "nerf_amd.parallel.render_image_sharded")
@@ -263,7 +264,7 @@ def render_image_sharded(network, prop_net, render_pose, image_size, focal, near
     part = render_image(network, prop_net, render_pose, image_size, focal, near, far, sample_num, white_bkg, render_depth, render_normal,
                         rng="philox", contract=contract, ipe=ipe, seed=int(seed), _shard=(start, end), spacing=spacing,
                         prop_rounds=prop_rounds, prop_pnum=prop_pnum, ipe_cov=ipe_cov, skip_empty=skip_empty, depth_quantiles=depth_quantiles,
-                        render_opacity=render_opacity)
+                        render_opacity=render_opacity, camera=camera)
     if not gather:
         part.pop("to_image")
         return part

@@ -212,7 +212,7 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
                  near: float, far: float, sample_num: int = 128, white_bkg: bool = False, render_depth=False,
                  render_normal=False, rng: str = "philox", contract: bool = False, ipe=False, seed: Optional[int] = None,
                  _shard=None, *, spacing: str = "linear", prop_rounds: int = 1, prop_pnum: Optional[int] = None, ipe_cov: str = "metric",
-                 skip_empty: Optional[float] = None, depth_quantiles=None, render_opacity: bool = False) -> dict:
+                 skip_empty: Optional[float] = None, camera=None, depth_quantiles=None, render_opacity: bool = False) -> dict:
     """Whole-image inference (procedures.py:34-97) -> {"rgb" (3,H,W) [, "depth_img" (3,H,W)]} on
     ``render_pose.device``.  The caller provides ``no_grad``/``eval()`` like for the reference.
     ``rng``, ``contract`` and ``ipe`` are additions.  ``rng``: where the stratified / inverse-CDF uniforms come from --
@@ -268,7 +268,12 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
     there, not the background).  This is an APPROXIMATION of the image: its error is the fine opacity of the rays the proposal network calls
     empty, so it suits models whose proposal network was trained to bound the fine weights.  The result gains "alive_img" (H,W) bool and
     "alive_fraction" (a Python float); a ``_shard`` call adds "alive_rays" (n,) bool.  The mask is a pure function of per-ray data: shards
-    reproduce it bit for bit.  The call synchronises once with the host (it reads the alive-ray count) and cannot be captured into a graph."""
+    reproduce it bit for bit.  The call synchronises once with the host (it reads the alive-ray count) and cannot be captured into a graph.
+    ``camera`` (keyword-only; an addition): a ``nerf_amd.camera.Camera`` -- focal lengths, principal point and OpenCV / COLMAP lens distortion
+    (include/nerf_amd.h) -- for a real capture: the ray table then comes from nerf_amd_generate_rays_camera, ``focal`` is IGNORED (pass
+    anything), and ``ipe=True`` takes its pixel radius from ``camera.fx``.  Everything downstream of the ray table -- tiling, shards, every
+    route and output -- is unchanged; ``Camera.reference(H, W, focal)`` renders the bits of the call without it.  The pose is the
+    project's camera-to-world (3,4), looking down -z with y up: converting a COLMAP pose is the caller's job."""
     ops.ipe_contract(contract, ipe, ipe_cov, "nerf_amd.render_image")
     quantiles = ops.depth_quantiles(depth_quantiles, "nerf_amd.render_image")
     skip_dmin = ops.skip_threshold(skip_empty, None, "nerf_amd.render_image")
@@ -298,7 +303,11 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
     network._check_config()
     prop_net._check_config()
     prec = ops.current_precision()
-    rays = ops.generate_rays(render_pose[:3], H, W, fx, fy, dev)                   # (H*W, 6), raster order
+    if camera is not None:
+        fx, fy = camera.fx, camera.fy
+        rays = ops.generate_camera_rays(render_pose[:3], H, W, camera, dev)         # (H*W, 6), raster order
+    else:
+        rays = ops.generate_rays(render_pose[:3], H, W, fx, fy, dev)               # (H*W, 6), raster order
     sz, patch_num = get_patch_size((H, W))
     if sz is not None:                                                             # reorder rays tile by tile
         pr, pc = patch_num

@@ -66,7 +66,7 @@ class TrainStep:
     def __init__(self, prop_net, mip_net, optimizer: Adam, image_hw: Tuple[int, int], focal, near: float, far: float, ray_num: int = 512,
                  coarse_pnum: int = 64, fine_pnum: int = 128, crop_xy=(1.0, 1.0), seed: Optional[int] = None, white_bkg: bool = False,
                  prop_normal: bool = False, grad_hook=None, ipe_radius: Optional[float] = None, contract: bool = False, flat_grads=None,
-                 *, scene=None, view_ids=None, spacing: str = "linear", prop_loss: str = "reference", prop_rounds: int = 1,
+                 *, scene=None, view_ids=None, cameras=None, spacing: str = "linear", prop_loss: str = "reference", prop_rounds: int = 1,
                  prop_pnum: Optional[int] = None, ipe_cov: str = "metric", grad_clip: float = -0.01, distortion: float = 0.0):
         """``grad_hook``: called between ``loss.backward()`` and ``optimizer.step()`` -- the place of ddp_train.py's gradient all-reduce
         (``lambda: parallel.allreduce_gradients([mip_net, prop_net])``).  An iteration with a hook runs eagerly (``capture`` refuses).
@@ -110,8 +110,13 @@ class TrainStep:
         ``ipe_cov`` (BASELINE configs[4]; with ``ipe_radius`` and ``contract`` only): "metric" (default) leaves the iteration as it is --
         the frustum mean is contracted, its covariance stays metric; "contracted" = Mip-NeRF 360's Sigma' = J Sigma J^T (eq. 11-14) in
         the fine network's sample fetch.  The backward is unchanged: the parameters' gradients read the dumped encoding.
-        ``scene``, ``view_ids``, ``spacing``, ``grad_clip``, ``distortion``, ``prop_loss``, ``prop_rounds``, ``prop_pnum`` and ``ipe_cov``
-        are keyword-only (their order carries no meaning)."""
+        ``cameras`` (needs ``scene``; not in the reference): the views' intrinsics for a real capture -- one ``nerf_amd.camera.Camera``
+        shared by all views, a sequence of V of them, or a (V,12) fp32 device table (include/nerf_amd.h) -- principal point, lens
+        distortion and focal lengths per view; the sampler kernel reads the table when it RUNS, so ``capture()`` / replay work with it and
+        writing into a table of your own in place is seen by the next step.  The step keeps the table alive like ``scene``.  ``focal`` is
+        then unused by the sampler; ``ipe_radius`` stays the caller's scalar.  None (default) leaves the iteration as it is.
+        ``scene``, ``view_ids``, ``spacing``, ``grad_clip``, ``distortion``, ``prop_loss``, ``prop_rounds``, ``prop_pnum``, ``ipe_cov`` and
+        ``cameras`` are keyword-only (their order carries no meaning)."""
         ops.ipe_contract(contract, ipe_radius, ipe_cov, "nerf_amd.training.TrainStep")
         self.ipe_cov = ipe_cov
         if not isinstance(optimizer, Adam) or not optimizer.lr_on_device:
@@ -152,7 +157,11 @@ class TrainStep:
         H, W = image_hw
         self.image_hw = (int(H), int(W))
         self.scene = None
+        self.cameras = None
         if scene is None:
+            if cameras is not None:
+                raise ValueError("nerf_amd.training.TrainStep: cameras needs scene=(images, poses); a single image is a one-view scene "
+                                 "(scene=(img[None], pose[None]))")
             if view_ids is not None:
                 raise ValueError("nerf_amd.training.TrainStep: view_ids needs scene=(images, poses)")
             self.image = torch.zeros((3, H, W), dtype=torch.float32, device=dev)         # static inputs of the (captured) step
@@ -169,6 +178,7 @@ class TrainStep:
                 raise ValueError("nerf_amd.training.TrainStep: image_hw %s is not the scene's %s" % (self.image_hw, tuple(images.shape[2:])))
             self.scene = (images, poses)                                                  # (kept alive: a captured graph holds their addresses)
             self.view_ids = ops.scene_view_ids(view_ids, images.shape[0], dev)
+            self.cameras = ops.scene_cameras(cameras, images.shape[0], dev)               # (kept alive like the scene)
             self.ray_index = torch.zeros((self.ray_num,), dtype=torch.int64, device=dev)
             self.image = self.pose = None
         self.crop_xy = tuple(crop_xy)
@@ -226,7 +236,7 @@ class TrainStep:
         if self.scene is not None:                                                        # one gather over the whole stack, read in place
             pts, z_c, rgb_tgt, rays, _ = ops.sample_scene_rays(self.scene[0], self.scene[1], self.fx, self.fy, near, far, self.ray_num,
                                                                self.coarse_pnum, seed_dev=self.seed, window=crop_window(*self.image_hw, self.crop_xy),
-                                                               view_ids=self.view_ids, index_out=self.ray_index)
+                                                               view_ids=self.view_ids, index_out=self.ray_index, cameras=self.cameras)
         else:
             pixels, coords = randomFromOneImage(self.image, self.crop_xy)                 # pure indexing on the device (cached table)
             pts, z_c, rgb_tgt, rays = ops.sample_training_rays_dev(pixels, coords, self.pose, self.fx, self.fy, near, far, self.ray_num,
