@@ -49,4 +49,41 @@ inline int cu_count() {
     return slot;
 }
 
+// Tile counters of the render MLP kernels that hand their tiles out dynamically (mlp_kernels.hip, "Elastic tiles"): one 32-bit counter
+// per STREAM that launches such a kernel, in a small pool that the library owns per device.  Launches of one stream are ordered, so they
+// may share a counter -- the launcher zeroes it with a stream-ordered memset ahead of each launch that needs it --; launches in flight on
+// different streams never do.  The pool, described once:
+constexpr int TILE_COUNTER_SLOTS = 32;            // streams per device that hold a counter at one time
+constexpr size_t TILE_COUNTER_STRIDE = 128;       // bytes from one counter to the next (each in a cache line of its own)
+constexpr size_t TILE_COUNTER_POOL_BYTES = TILE_COUNTER_SLOTS * TILE_COUNTER_STRIDE;
+// When a further stream finds the pool full, the device is synchronised -- nothing that counts is in flight any more -- and the pool is
+// handed out afresh.
+inline int tile_counter(hipStream_t st, unsigned** counter) {
+    struct Pool { int dev; char* base; int used; hipStream_t owner[TILE_COUNTER_SLOTS]; };
+    static std::vector<Pool> pools;
+    const int dev = current_device();
+    std::lock_guard<std::mutex> lock(table_mutex());
+    Pool* p = nullptr;
+    for (auto& q : pools)
+        if (q.dev == dev) p = &q;
+    if (!p) {
+        void* mem = nullptr;
+        if (hipError_t err = hipMalloc(&mem, TILE_COUNTER_POOL_BYTES)) return (int)err;
+        pools.push_back(Pool{dev, reinterpret_cast<char*>(mem), 0, {}});
+        p = &pools.back();
+    }
+    int k = 0;
+    while (k < p->used && p->owner[k] != st) ++k;
+    if (k == p->used) {
+        if (p->used == TILE_COUNTER_SLOTS) {
+            if (hipError_t err = hipDeviceSynchronize()) return (int)err;
+            p->used = 0;
+            k = 0;
+        }
+        p->owner[p->used++] = st;
+    }
+    *counter = reinterpret_cast<unsigned*>(p->base + (size_t)k * TILE_COUNTER_STRIDE);
+    return 0;
+}
+
 }  // namespace nerf_host

@@ -11,6 +11,7 @@ extern __shared__ __attribute__((aligned(16))) char smem[];
 // (The round-1..4 timing ablations -- builds without epilogues / encodings / barriers / LDS re-reads / ring refills / dump stores /
 // mask bits -- are retired: their results are in DESIGN.md section 3.2 and profiles/r0[1-4]_*; the switches left the sources in round 5.)
 // MLP_CLOCKPROBE: workgroup 0 overwrites output record 0 with (shader cycles, 100 MHz ticks) -- scripts/gpu_clockprobe.sh
+// MLP_TILEPROBE: every workgroup's entry / finish stamps, XCD and tile count in a buffer of the probe's own -- scripts/gpu_tile_probe.py
 namespace {
 
 
@@ -384,6 +385,9 @@ struct WeightStream {
         }
         return a;
     }
+    // (The elastic render kernels -- mlp_kernels.hip TileQueue -- add one returning global atomic per tile in wave 0, issued with the
+    //  tile's sample loads.  Returning atomics count in vmcnt in issue order like loads, so like the training kernels' stores above one in
+    //  flight only adds to the counter: the counted waits here get stricter, never weaker.)
     template <int PARITY>
     DEVINL void boundary() {
         if constexpr (!TWO_GROUPS && PARITY != 0) {          // single group, odd boundary: nothing to wait for, no barrier

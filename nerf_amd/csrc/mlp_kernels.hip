@@ -369,6 +369,112 @@ struct MipResident {
     static_assert(TOTAL <= 160 * 1024, "LDS");
 };
 
+// ------------------------------------------------------------------------------------------------
+// MLP_TILEPROBE (diagnostic builds only: make variant_tu FLAGS=-DMLP_TILEPROBE; scripts/gpu_tile_probe.py): do the persistent workgroups
+// of a launch finish together?  EVERY workgroup of the two ray-tile render kernels stamps the 100 MHz real-time counter and the shader
+// clock counter at kernel entry and after ws.drain() and leaves them, with its XCD and the number of tiles it ran, in a buffer of the
+// probe's own (a __device__ array of this translation unit; the outputs are what they are in the shipped library).  The buffer keeps the
+// last TILEPROBE_LAUNCHES launches of each kernel: a one-thread launch ahead of every probed launch advances the slot, in stream order.
+// nerf_amd_tileprobe_read_{prop,mip} copy it to the host.  Without the switch none of this is compiled: the shipped objects are unchanged.
+// ------------------------------------------------------------------------------------------------
+template <bool ON> struct TileProbe {       // off: nothing is compiled
+    unsigned tiles;
+    DEVINL void begin() { tiles = 0u; }
+    DEVINL void end() {}
+};
+#ifndef MLP_TILEPROBE
+constexpr bool TILEPROBE = false;
+#else
+constexpr bool TILEPROBE = true;
+constexpr int TILEPROBE_LAUNCHES = 8, TILEPROBE_WGS = 1024;
+struct TileProbeRec {
+    unsigned long long real0, real1;       // s_memrealtime (100 MHz) at entry / after the drain
+    unsigned long long clk0, clk1;         // s_memtime (shader clock) at the same two points
+    unsigned xcc, tiles, grid, seq;        // HW_REG_XCC_ID, tiles this workgroup ran, gridDim.x, launch number (from 1)
+};
+__device__ TileProbeRec g_tileprobe[TILEPROBE_LAUNCHES][TILEPROBE_WGS];
+__device__ unsigned g_tileprobe_seq;
+__global__ void tileprobe_advance() { g_tileprobe_seq = g_tileprobe_seq + 1; }
+template <> struct TileProbe<true> {
+    unsigned long long real0, clk0;
+    unsigned tiles;
+    DEVINL void begin() { real0 = __builtin_amdgcn_s_memrealtime(); clk0 = __builtin_amdgcn_s_memtime(); tiles = 0u; }
+    DEVINL void end() {
+        const unsigned long long real1 = __builtin_amdgcn_s_memrealtime(), clk1 = __builtin_amdgcn_s_memtime();
+        unsigned xcc;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+        if (threadIdx.x == 0 && blockIdx.x < TILEPROBE_WGS) {
+            const unsigned seq = g_tileprobe_seq;
+            g_tileprobe[seq % TILEPROBE_LAUNCHES][blockIdx.x] = TileProbeRec{real0, real1, clk0, clk1, xcc & 0xfu, tiles, gridDim.x, seq};
+        }
+    }
+};
+int tileprobe_read(void* dst, size_t bytes) {
+    if (bytes != sizeof(g_tileprobe)) return (int)hipErrorInvalidValue;
+    if (hipError_t e = hipDeviceSynchronize()) return (int)e;
+    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_tileprobe), bytes);
+}
+#endif
+
+// ------------------------------------------------------------------------------------------------
+// Elastic tiles (profiles/elastic_tiles_probe.md, elastic_tiles_ab.md): the bf16 render instantiations -- PBF16WR and
+// PBF16W, inference, point PE, two launches -- hand their tiles out dynamically.  The eight XCDs of the chip do not hold the same clock
+// under the power cap (measured: 1.87-1.96 GHz inside one launch), so with a static share of tiles per workgroup seven XCDs wait for
+// the slowest at the end of every launch.  Protocol:
+//   * tile blockIdx.x is a workgroup's first tile, as before; every further one is gridDim.x + atomicAdd(counter, 1).
+//   * lane 0 of wave 0 issues the returning atomic in the tile prologue, with the tile's other global loads, and so fetches the index of
+//     the NEXT tile a whole tile ahead; once the prologue has consumed its loads it parks the index in an LDS word (park()), one word per
+//     tile parity.  No other VMEM instruction is added, and none between a tile's first and last next<>().
+//   * all four waves read that word at the tile end (next()).
+//   Why every wave sees the same index: wave 0 parks the word before its first next<>() of the tile, every wave reads it behind its last
+//   one, and the ring barriers of the tile lie in between (52 in a fine tile, 21 in a proposal tile): a wave that reads has passed a
+//   barrier which wave 0 reached after the ds_write -- and after the counted LDS waits of its own A-fragment reads, which complete in
+//   order behind that write.  The word of tile k is overwritten in tile k + 2, which wave 0 enters only after barriers of tile k + 1 that
+//   every wave reaches behind its read in tile k: hence two words.  All waves therefore leave the tile loop in the same iteration;
+//   otherwise their barrier counts would differ and the workgroup would hang.
+//   A tile's results depend on its index alone, and every index below n_tiles is handed out exactly once (the atomic), so the outputs
+//   are those of the static loop bit for bit, whichever workgroup computes which tile (tests/test_gpu_elastic_tiles.py).
+// The counter: host_common.h tile_counter(), zeroed by the launcher in stream order.  A launch with no more tiles than workgroups needs
+// no zeroing: whatever the atomic returns, gridDim.x + it is past the last tile.
+// -DMLP_ELASTIC=0 restores the static loop for A/B runs (make variant_tu).
+// ------------------------------------------------------------------------------------------------
+#ifndef MLP_ELASTIC
+#define MLP_ELASTIC 1
+#endif
+template <bool ON> struct TileQueue {       // off: the static loop
+    DEVINL void init(unsigned*, uint32_t) {}
+    DEVINL void fetch() {}
+    DEVINL void park() {}
+    DEVINL int64_t next(int64_t tile) { return tile + gridDim.x; }
+};
+template <> struct TileQueue<true> {
+    unsigned* counter;
+    uint32_t word;          // LDS address of this tile's word
+    uint32_t flip;          // ... xor this = the other tile parity's
+    unsigned got;           // (lane 0 of wave 0) the index fetched in this tile
+    DEVINL void init(unsigned* c, uint32_t lds) { counter = c; word = lds; flip = lds ^ (lds + 4); }
+    // (The zero offset in a VGPR that the compiler cannot see through keeps hipcc's atomic optimizer away: on a wave-uniform address it
+    //  rewrites the atomic as a wave reduction whose s_waitcnt vmcnt(0) + v_readfirstlane follow the atomic at once -- wave 0 would then
+    //  sit out the atomic's whole latency, and the ring's loads in flight, at every tile top instead of at park().)
+    DEVINL void fetch() {
+        if (threadIdx.x == 0) {
+            uint32_t zero = 0u;
+            asm volatile("" : "+v"(zero));
+            got = __hip_atomic_fetch_add(counter + zero, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    DEVINL void park() { if (threadIdx.x == 0) *reinterpret_cast<volatile uint32_t*>(smem + word) = got; }
+    DEVINL int64_t next(int64_t) {
+        asm volatile("" ::: "memory");
+        const uint32_t nx = (uint32_t)__builtin_amdgcn_readfirstlane((int)*reinterpret_cast<volatile uint32_t*>(smem + word));
+        word ^= flip;
+        return (int64_t)gridDim.x + nx;
+    }
+};
+template <class P, bool TRAIN, bool IPE = false, bool F8 = false, bool FUSED = false>
+constexpr bool elastic_tiles() { return MLP_ELASTIC && (same_type<P, PBF16W>::value || same_type<P, PBF16WR>::value) && !TRAIN && !IPE && !F8 && !FUSED; }
+constexpr uint32_t ELASTIC_LDS = 8;         // the two words, behind everything else of the instantiation's LDS map
+
 DEVINL void load_biases(const void* packed, size_t stream_bytes, int n_bias, uint32_t lds_off = MLP_RING_BYTES) {
     const float* b = reinterpret_cast<const float*>(reinterpret_cast<const char*>(packed) + stream_bytes);
     float* dst = reinterpret_cast<float*>(smem + lds_off);
@@ -467,10 +573,12 @@ DEVINL void mask_acc_init(uint32_t acc_wave, int lane) {
 // ================================================================================================
 template <class P, bool TRAIN, bool F8 = false>
 __global__ __launch_bounds__(P::NW * 64) void proposal_kernel(const void* __restrict__ packed, nerf_amd_samples s,
-                                                              float* __restrict__ density, ActDump dump) {
+                                                              float* __restrict__ density, ActDump dump, unsigned* tile_counter) {
     using L = PropLayout;
     using BReg = typename P::BReg;
     constexpr int FPC = P::FPC;
+    TileProbe<TILEPROBE && ray_tile<P>::value && !TRAIN> probe;
+    probe.begin();
     constexpr bool RES = MLP_RESIDENT_PROP && wide_bf16<P>() && !TRAIN;        // resident weights: see PropResident
     using R = typename conditional_type<RES, PropResident::R, NoResident>::type;
     using WS = typename conditional_type<RES, WeightStream<P, PropResident::NSLOT, R, PropResident::RES>, WeightStream<P, MLP_NSLOT>>::type;
@@ -486,8 +594,12 @@ __global__ __launch_bounds__(P::NW * 64) void proposal_kernel(const void* __rest
     const uint32_t macc = lds_maskacc<P>() + wave * 2 * NT * 1024;      // TRAIN: this wave's ReLU bit-mask records
     const uint32_t sacc = lds_scaleacc<P>() + wave * 2 * NT * 1024;     // F8: this wave's scale-exponent records
     if constexpr (TRAIN) mask_acc_init<P>(macc, lane);
+    constexpr bool ELASTIC = elastic_tiles<P, TRAIN>();                  // see TileQueue
+    TileQueue<ELASTIC> tq;
+    tq.init(tile_counter, RES ? PropResident::TOTAL : lds_total<P>());
 
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile = tq.next(tile)) {
+        ++probe.tiles;
         int64_t m[NT];
         BReg enc[NT][4];
         if constexpr (ray_tile<P>::value) {
@@ -497,6 +609,7 @@ __global__ __launch_bounds__(P::NW * 64) void proposal_kernel(const void* __rest
             int64_t n; int si0;
             split_wave_index(s, m0 < s.M ? m0 : s.M - 64, n, si0);            // (M is a multiple of 64: a wave is all inside or all outside)
             const Sample sm = fetch_ray_sample<false>(s, n, si0 + lane);
+            tq.fetch();                                                        // (behind the tile's loads: it returns behind them)
             encode_pair<P, 10, 4>(sm.x, sm.y, sm.z, enc[0], enc[1]);
             half_swap_groups<4>(enc[0], enc[1]);
         } else if constexpr (NT == 2 && P::FAST_PE) {
@@ -505,6 +618,7 @@ __global__ __launch_bounds__(P::NW * 64) void proposal_kernel(const void* __rest
             m[1] = m[0] + 32;
             const int64_t mo = h ? m[1] : m[0];
             const Sample sm = fetch_sample(s, mo < s.M ? mo : s.M - 1, false);
+            tq.fetch();
             encode_pair<P, 10, 4>(sm.x, sm.y, sm.z, enc[0], enc[1]);
             half_swap_groups<4>(enc[0], enc[1]);
             if constexpr (TRAIN) {
@@ -514,6 +628,7 @@ __global__ __launch_bounds__(P::NW * 64) void proposal_kernel(const void* __rest
                     for (int k = 0; k < 4; ++k) dump_breg<P>(dump, 4, tile * (TS / 32) + wave * NT + t, k, lane, enc[t][k]);
             }
         } else {
+        static_assert(!ELASTIC, "elastic tiles: the wide bf16 prologues");
 #pragma unroll
         for (int t = 0; t < NT; ++t) {
             m[t] = tile * TS + (wave * NT + t) * 32 + j;
@@ -525,6 +640,7 @@ __global__ __launch_bounds__(P::NW * 64) void proposal_kernel(const void* __rest
             }
         }
         }
+        tq.park();
         BReg a[NT][16], b[NT][16];
         // (layer indices for the training dump: `lay` = the layer whose block pairs are being computed, `lay_pend` = the layer
         // that owns the deferred pair -- the deferred slices run while the NEXT layer is computed)
@@ -577,6 +693,7 @@ __global__ __launch_bounds__(P::NW * 64) void proposal_kernel(const void* __rest
         }
     }
     ws.drain();
+    probe.end();
 }
 
 // ================================================================================================
@@ -659,10 +776,12 @@ struct FusedComposite {
 // instantiations carry neither its code nor its branches and can use the paired tile prologue.
 template <class P, bool TRAIN, bool IPE = false, bool F8 = false, bool FUSED = false>
 __global__ __launch_bounds__(P::NW * 64) void mip_kernel(const void* __restrict__ packed, nerf_amd_samples s,
-                                                         float* __restrict__ rgbo, FusedComposite fc, ActDump dump) {
+                                                         float* __restrict__ rgbo, FusedComposite fc, ActDump dump, unsigned* tile_counter) {
     using L = MipLayout;
     using BReg = typename P::BReg;
     constexpr int FPC = P::FPC;
+    TileProbe<TILEPROBE && ray_tile<P>::value && !TRAIN> probe;
+    probe.begin();
 #ifdef MLP_CLOCKPROBE
     const uint64_t probe_c0 = __builtin_readcyclecounter(), probe_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -688,8 +807,12 @@ __global__ __launch_bounds__(P::NW * 64) void mip_kernel(const void* __restrict_
     const uint32_t dir_lds0 = dirs_lds + wave * NT * 1024 + lane * 16;
     auto enc_lds = [&](int t) -> uint32_t { return enc_lds0 + t * 4 * P::BREG_LDS; };
     auto dir_lds = [&](int t) -> uint32_t { return dir_lds0 + t * 1024; };
+    constexpr bool ELASTIC = elastic_tiles<P, TRAIN, IPE, F8, FUSED>();   // see TileQueue
+    TileQueue<ELASTIC> tq;
+    tq.init(tile_counter, RES ? MipResident::TOTAL : lds_total<P>());
 
-    for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+    for (int64_t tile = blockIdx.x; tile < n_tiles; tile = tq.next(tile)) {
+        ++probe.tiles;
         int64_t m[NT];
         BReg a[NT][16], b[NT][16];
         int lay = 0, lay_pend = 0;                                  // training dump: see proposal_kernel
@@ -724,6 +847,7 @@ __global__ __launch_bounds__(P::NW * 64) void mip_kernel(const void* __restrict_
                 const BReg* row = reinterpret_cast<const BReg*>(reinterpret_cast<const char*>(rgbo + m0c * 4) + h * (DIR_TABLE_ROW / 2));
                 const BReg row0 = row[0], row1 = row[1];
                 const Sample sm = fetch_ray_sample<true>(s, n, si0 + lane);
+                tq.fetch();                                                   // (behind the tile's loads: it returns behind them)
                 P::stash(dir_lds(0), row0);                                   // (parked before the encoding starts: the rows are the oldest loads)
                 P::stash(dir_lds(1), row1);
                 encode_pair<P, 10, 4>(sm.x, sm.y, sm.z, enc[0], enc[1]);
@@ -739,6 +863,7 @@ __global__ __launch_bounds__(P::NW * 64) void mip_kernel(const void* __restrict_
                 m[1] = m[0] + 32;
                 const int64_t mo = h ? m[1] : m[0];
                 const Sample sm = fetch_sample(s, mo < s.M ? mo : s.M - 1, true);
+                tq.fetch();
                 encode_pair<P, 10, 4>(sm.x, sm.y, sm.z, enc[0], enc[1]);
                 half_swap_groups<4>(enc[0], enc[1]);
                 // the raw direction of BOTH tiles' samples for both halves: swap(d, copy of d) -> [d.lo | d.lo], [d.hi | d.hi]
@@ -759,6 +884,7 @@ __global__ __launch_bounds__(P::NW * 64) void mip_kernel(const void* __restrict_
                     *reinterpret_cast<f32x4*>(smem + dir_lds(t)) = dv;
                 }
             } else {
+            static_assert(!ELASTIC, "elastic tiles: the wide bf16 prologues");
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
                 m[t] = tile * TS + (wave * NT + t) * 32 + j;
@@ -795,6 +921,7 @@ __global__ __launch_bounds__(P::NW * 64) void mip_kernel(const void* __restrict_
                 *reinterpret_cast<f32x4*>(smem + dir_lds(t)) = dv;
             }
             }
+            tq.park();
             // lin_block1.0 : 63 -> 256
             d = dense<P, 4, 8, L::START[0]>(ws, bias0 + L::BIAS_OFF[0] * 4,
                 [&](int kg, int t) -> BReg { return enc[t][kg]; }, OA, NoPrev{});
@@ -980,6 +1107,7 @@ __global__ __launch_bounds__(P::NW * 64) void mip_kernel(const void* __restrict_
         }
     }
     ws.drain();
+    probe.end();
 #ifdef MLP_CLOCKPROBE
     // diagnostic build: shader cycles vs 100 MHz real-time ticks of workgroup 0 overwrite the first output record
     if (blockIdx.x == 0 && threadIdx.x == 0 && rgbo != nullptr) {
@@ -1429,18 +1557,41 @@ int grid_for(int64_t n_tiles) {
 // Dynamic LDS above 64 KiB is an opt-in per KERNEL FUNCTION and device (host_common.h)
 int allow_dynamic_lds(const void* fn, size_t lds) { return nerf_host::allow_dynamic_lds(fn, lds); }
 
+// The two persistent kernels' launch: `enqueue` launches them with the arguments they take behind `out`.
+template <class P, bool TRAIN, class K, class... Args>
+int enqueue(K kernel, int64_t n_tiles, size_t lds, const void* packed, const nerf_amd_samples& s, float* out, hipStream_t st, Args... args) {
+#ifdef MLP_TILEPROBE
+    if constexpr (ray_tile<P>::value && !TRAIN) hipLaunchKernelGGL(tileprobe_advance, dim3(1), dim3(1), 0, st);      // the next slot of the probe's buffer
+#endif
+    hipLaunchKernelGGL(kernel, dim3(grid_for(n_tiles)), dim3(P::NW * 64), lds, st, packed, s, out, args...);
+    return (int)hipGetLastError();
+}
 // LDS_FIXED: the LDS map of an instantiation with resident weights (PropResident / MipResident), 0 = the common map
-template <class P, class Lay, bool TRAIN = false, bool F8 = false, size_t LDS_FIXED = 0, class K, class... Extra>
+// TILES: -1 = the kernel's arguments are `extra` as they stand; 0 / 1 = elastic_tiles<>() of a render instantiation of proposal_kernel /
+//        mip_kernel, whose last argument, the tile counter, is added here: null with the static tile loop (0), else (1) the stream's
+//        counter of the library's pool, zeroed in stream order -- and the LDS map ends in the two words of TileQueue
+template <class P, class Lay, bool TRAIN = false, bool F8 = false, size_t LDS_FIXED = 0, int TILES = -1, class K, class... Extra>
 int launch(K kernel, const void* packed, const nerf_amd_samples& s, float* out, hipStream_t st, Extra... extra) {
     constexpr int TS = P::NW * P::NT * 32;
     const int64_t n_tiles = (s.M + TS - 1) / TS;
     if (n_tiles == 0) return 0;
-    const size_t lds = LDS_FIXED ? LDS_FIXED : (F8 ? lds_total_train_f8<P>() : (TRAIN ? lds_total_train<P>() : lds_total<P>()));
+    constexpr size_t lds = (LDS_FIXED ? LDS_FIXED : (F8 ? lds_total_train_f8<P>() : (TRAIN ? lds_total_train<P>() : lds_total<P>()))) + (TILES == 1 ? ELASTIC_LDS : 0);
+    static_assert(lds <= 160 * 1024, "LDS");
     if (int e = allow_dynamic_lds(reinterpret_cast<const void*>(kernel), lds)) return e;
-    hipLaunchKernelGGL(kernel, dim3(grid_for(n_tiles)), dim3(P::NW * 64), lds, st, packed, s, out, extra...);
-    return (int)hipGetLastError();
+    if constexpr (TILES == 1) {
+        unsigned* counter = nullptr;
+        if (int e = nerf_host::tile_counter(st, &counter)) return e;
+        if (n_tiles > grid_for(n_tiles))                                    // (no more tiles than workgroups: nothing is handed out, any count will do)
+            if (hipError_t e = hipMemsetAsync(counter, 0, sizeof(unsigned), st)) return (int)e;
+        return enqueue<P, TRAIN>(kernel, n_tiles, lds, packed, s, out, st, extra..., counter);
+    } else if constexpr (TILES == 0) {
+        return enqueue<P, TRAIN>(kernel, n_tiles, lds, packed, s, out, st, extra..., (unsigned*)nullptr);
+    } else {
+        return enqueue<P, TRAIN>(kernel, n_tiles, lds, packed, s, out, st, extra...);
+    }
 }
 const ActDump NO_DUMP{nullptr, 0ull, nullptr, 0ull};
+[[maybe_unused]] unsigned* const STATIC_TILES = nullptr;         // the tile_counter argument of an instantiation with the static tile loop
 
 // bf16 policy of the shipped library: the wide tile (measured 2.5 % faster end to end);
 // -DMLP_BF16_NARROW selects the 8-wave x 32-sample tile for A/B runs
@@ -1453,15 +1604,25 @@ using PB16 = PBF16W;
 #ifndef MLP_TU
 #define MLP_TU 0
 #endif
+#ifdef MLP_TILEPROBE
+// the probe's buffer of this translation unit (synchronises the device): TILEPROBE_LAUNCHES x TILEPROBE_WGS records of 48 bytes.  One name
+// per kernel family, since a variant_tu library carries the switch in one family only -- the script asks for the one it finds.
+#if MLP_TU == 0 || MLP_TU == 1
+extern "C" __attribute__((visibility("default"))) int nerf_amd_tileprobe_read_prop(void* dst, size_t bytes) { return tileprobe_read(dst, bytes); }
+#endif
+#if MLP_TU == 0 || MLP_TU == 2
+extern "C" __attribute__((visibility("default"))) int nerf_amd_tileprobe_read_mip(void* dst, size_t bytes) { return tileprobe_read(dst, bytes); }
+#endif
+#endif
 #if MLP_TU == 0 || MLP_TU == 1
 int nk::mlp_launch_proposal(const void* packed, int precision, const nerf_amd_samples& s, float* density, hipStream_t st) {
 #if MLP_RAY_TILE_PROP
     if (precision == NERF_AMD_BF16 && ray_tile_descriptor(s))
-        return launch<PBF16WR, PropLayout, false, false, (MLP_RESIDENT_PROP ? PropResident::TOTAL : 0)>(proposal_kernel<PBF16WR, false>, packed, s, density, st, NO_DUMP);
+        return launch<PBF16WR, PropLayout, false, false, (MLP_RESIDENT_PROP ? PropResident::TOTAL : 0), (int)elastic_tiles<PBF16WR, false>()>(proposal_kernel<PBF16WR, false>, packed, s, density, st, NO_DUMP);
 #endif
     if (precision == NERF_AMD_BF16)
-        return launch<PB16, PropLayout, false, false, (MLP_RESIDENT_PROP ? PropResident::TOTAL : 0)>(proposal_kernel<PB16, false>, packed, s, density, st, NO_DUMP);
-    return launch<PF32, PropLayout>(proposal_kernel<PF32, false>, packed, s, density, st, NO_DUMP);
+        return launch<PB16, PropLayout, false, false, (MLP_RESIDENT_PROP ? PropResident::TOTAL : 0), (int)elastic_tiles<PB16, false>()>(proposal_kernel<PB16, false>, packed, s, density, st, NO_DUMP);
+    return launch<PF32, PropLayout>(proposal_kernel<PF32, false>, packed, s, density, st, NO_DUMP, STATIC_TILES);
 }
 #endif
 #if MLP_TU == 0 || MLP_TU == 2
@@ -1476,16 +1637,16 @@ int nk::mlp_launch_mip(const void* packed, int precision, const nerf_amd_samples
 #if MLP_RAY_TILE_MIP
     if (precision == NERF_AMD_BF16 && s.z && ray_tile_descriptor(s)) {      // one small launch leaves every wave its ray's direction encoding in rgbo
         if (int e = launch_dir_rows(s.rays, s.M / 64, s.S / 64, 64 * 16, rgbo, st)) return e;
-        return launch<PBF16WR, MipLayout, false, false, (MLP_RESIDENT_MIP ? MipResident::TOTAL : 0)>(mip_kernel<PBF16WR, false>, packed, s, rgbo, st, off, NO_DUMP);
+        return launch<PBF16WR, MipLayout, false, false, (MLP_RESIDENT_MIP ? MipResident::TOTAL : 0), (int)elastic_tiles<PBF16WR, false>()>(mip_kernel<PBF16WR, false>, packed, s, rgbo, st, off, NO_DUMP);
     }
 #endif
     if (s.ipe) {                                            // integrated positional encoding (validated by the C-ABI: mode 1, z, dir norm)
-        if (precision == NERF_AMD_BF16) return launch<PB16, MipLayout>(mip_kernel<PB16, false, true>, packed, s, rgbo, st, off, NO_DUMP);
-        return launch<PF32, MipLayout>(mip_kernel<PF32, false, true>, packed, s, rgbo, st, off, NO_DUMP);
+        if (precision == NERF_AMD_BF16) return launch<PB16, MipLayout>(mip_kernel<PB16, false, true>, packed, s, rgbo, st, off, NO_DUMP, STATIC_TILES);
+        return launch<PF32, MipLayout>(mip_kernel<PF32, false, true>, packed, s, rgbo, st, off, NO_DUMP, STATIC_TILES);
     }
     if (precision == NERF_AMD_BF16)
-        return launch<PB16, MipLayout, false, false, (MLP_RESIDENT_MIP ? MipResident::TOTAL : 0)>(mip_kernel<PB16, false>, packed, s, rgbo, st, off, NO_DUMP);
-    return launch<PF32, MipLayout>(mip_kernel<PF32, false>, packed, s, rgbo, st, off, NO_DUMP);
+        return launch<PB16, MipLayout, false, false, (MLP_RESIDENT_MIP ? MipResident::TOTAL : 0), (int)elastic_tiles<PB16, false>()>(mip_kernel<PB16, false>, packed, s, rgbo, st, off, NO_DUMP);
+    return launch<PF32, MipLayout>(mip_kernel<PF32, false>, packed, s, rgbo, st, off, NO_DUMP, STATIC_TILES);
 }
 // packed = nerf_amd_pack_weights(NERF_AMD_NET_MIP_128, ...); point PE only (the C-ABI refuses s.ipe with this layout)
 int nk::mlp_launch_mip128(const void* packed, int precision, const nerf_amd_samples& s, float* rgbo, hipStream_t st) {
@@ -1496,8 +1657,8 @@ int nk::mlp_launch_mip128(const void* packed, int precision, const nerf_amd_samp
 int nk::mlp_launch_mip_composite(const void* packed, int precision, const nerf_amd_samples& s, float* rgb, float* depth, float* weights,
                              int white_bkg, float near, float far, hipStream_t st) {
     const FusedComposite fc{rgb, depth, weights, white_bkg, near, far};
-    if (precision == NERF_AMD_BF16) return launch<PB16, MipLayout>(mip_kernel<PB16, false, false, false, true>, packed, s, (float*)nullptr, st, fc, NO_DUMP);
-    return launch<PF32, MipLayout>(mip_kernel<PF32, false, false, false, true>, packed, s, (float*)nullptr, st, fc, NO_DUMP);
+    if (precision == NERF_AMD_BF16) return launch<PB16, MipLayout>(mip_kernel<PB16, false, false, false, true>, packed, s, (float*)nullptr, st, fc, NO_DUMP, STATIC_TILES);
+    return launch<PF32, MipLayout>(mip_kernel<PF32, false, false, false, true>, packed, s, (float*)nullptr, st, fc, NO_DUMP, STATIC_TILES);
 }
 #endif
 static ActDump make_dump(void* dump, int precision, int64_t M, int slots) {
@@ -1533,14 +1694,14 @@ size_t nk::mlp_train_mask_stride(int precision, int64_t M) { return (size_t)mlp_
 int nk::mlp_launch_proposal_train(const void* packed, int precision, const nerf_amd_samples& s, float* density, void* dump, hipStream_t st) {
     if (precision == NERF_AMD_BF16_F8) {                    // bf16 arithmetic, hidden slots of the dump in scaled e4m3 (mlp_layout.h)
         const ActDump d8 = make_dump(dump, NERF_AMD_BF16, s.M, PROP_DUMP_SLOTS);
-        return launch<PB16, PropLayout, true, true>(proposal_kernel<PB16, true, true>, packed, s, density, st, d8);
+        return launch<PB16, PropLayout, true, true>(proposal_kernel<PB16, true, true>, packed, s, density, st, d8, STATIC_TILES);
     }
     const ActDump d = make_dump(dump, precision, s.M, PROP_DUMP_SLOTS);
     // bf16 training forward of the proposal network: the 8-wave x 32-sample tile (two waves per SIMD hide the dump's stores and mask
     // arithmetic, and the 64-sample tile spills ~90 registers here) -- 0.83 -> 0.73 ms at 16 384 rays in a same-box A/B; the dump layout
     // does not depend on the tile policy (32-sample subtiles either way).  The MipNeRF forward and both dgrad chains measured no gain.
-    if (precision == NERF_AMD_BF16) return launch<PBF16, PropLayout, true>(proposal_kernel<PBF16, true>, packed, s, density, st, d);
-    return launch<PF32, PropLayout, true>(proposal_kernel<PF32, true>, packed, s, density, st, d);
+    if (precision == NERF_AMD_BF16) return launch<PBF16, PropLayout, true>(proposal_kernel<PBF16, true>, packed, s, density, st, d, STATIC_TILES);
+    return launch<PF32, PropLayout, true>(proposal_kernel<PF32, true>, packed, s, density, st, d, STATIC_TILES);
 }
 #endif
 #if MLP_TU == 0 || MLP_TU == 2
@@ -1548,17 +1709,17 @@ int nk::mlp_launch_mip_train(const void* packed, int precision, const nerf_amd_s
     const FusedComposite off{nullptr, nullptr, nullptr, 0, 0.0f, 1.0f};
     if (precision == NERF_AMD_BF16_F8) {                    // bf16 arithmetic, hidden slots of the dump in scaled e4m3 (mlp_layout.h)
         const ActDump d8 = make_dump(dump, NERF_AMD_BF16, s.M, MIP_DUMP_SLOTS);
-        if (s.ipe) return launch<PB16, MipLayout, true, true>(mip_kernel<PB16, true, true, true>, packed, s, rgbo, st, off, d8);
-        return launch<PB16, MipLayout, true, true>(mip_kernel<PB16, true, false, true>, packed, s, rgbo, st, off, d8);
+        if (s.ipe) return launch<PB16, MipLayout, true, true>(mip_kernel<PB16, true, true, true>, packed, s, rgbo, st, off, d8, STATIC_TILES);
+        return launch<PB16, MipLayout, true, true>(mip_kernel<PB16, true, false, true>, packed, s, rgbo, st, off, d8, STATIC_TILES);
     }
     const ActDump d = make_dump(dump, precision, s.M, MIP_DUMP_SLOTS);
     if (s.ipe) {                                            // integrated PE on the training path (BASELINE configs[2]): the dumped encoding slot
         // holds the IPE features in the PE10 slot map, so the dgrad chain and the weight-gradient kernels run unchanged
-        if (precision == NERF_AMD_BF16) return launch<PB16, MipLayout, true>(mip_kernel<PB16, true, true>, packed, s, rgbo, st, off, d);
-        return launch<PF32, MipLayout, true>(mip_kernel<PF32, true, true>, packed, s, rgbo, st, off, d);
+        if (precision == NERF_AMD_BF16) return launch<PB16, MipLayout, true>(mip_kernel<PB16, true, true>, packed, s, rgbo, st, off, d, STATIC_TILES);
+        return launch<PF32, MipLayout, true>(mip_kernel<PF32, true, true>, packed, s, rgbo, st, off, d, STATIC_TILES);
     }
-    if (precision == NERF_AMD_BF16) return launch<PB16, MipLayout, true>(mip_kernel<PB16, true>, packed, s, rgbo, st, off, d);
-    return launch<PF32, MipLayout, true>(mip_kernel<PF32, true>, packed, s, rgbo, st, off, d);
+    if (precision == NERF_AMD_BF16) return launch<PB16, MipLayout, true>(mip_kernel<PB16, true>, packed, s, rgbo, st, off, d, STATIC_TILES);
+    return launch<PF32, MipLayout, true>(mip_kernel<PF32, true>, packed, s, rgbo, st, off, d, STATIC_TILES);
 }
 
 #endif
