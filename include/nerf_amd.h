@@ -847,6 +847,38 @@ int nerf_amd_rows_gemm(int64_t M, int64_t N, int64_t K, const void* X, int64_t l
 int nerf_amd_rows_to_bf16(const float* src, int64_t rows_src, int64_t src_stride, int64_t rows, int cols, int fill, void* dst,
                           int64_t dst_stride, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Image metrics (additive; the ABI number stays): SSIM and MSE of rendered views against their ground truth, per view, on the device.
+ *
+ *   pred, target   contiguous fp32 (V, C, H, W), V >= 1, C >= 1, H >= 11, W >= 11.  Values are nominally in [0, 1], the dynamic range is
+ *                  L = 1; values outside [0, 1] are legal and go through the same formulas.
+ *   window         g[i] ~ exp(-(i - 5)^2 / (2 * 1.5^2)), i = 0 .. 10, normalised to sum 1 in fp64 on the host and handed to the kernel as
+ *                  11 fp32 constants; the 2-D window is g g^T (separable).
+ *   positions      VALID ones only: the map has (H - 10) x (W - 10) entries per (view, channel); no padding of any kind.
+ *   per position   with <.> the windowed average:
+ *                      mu_x = <x>, mu_y = <y>, s_x^2 = <x^2> - mu_x^2, s_y^2 = <y^2> - mu_y^2, s_xy = <xy> - mu_x mu_y
+ *                      C1 = (0.01 L)^2, C2 = (0.03 L)^2
+ *                      SSIM = (2 mu_x mu_y + C1)(2 s_xy + C2) / ((mu_x^2 + mu_y^2 + C1)(s_x^2 + s_y^2 + C2))
+ *                  No clamp belongs to the definition.  The kernel forms the fp32 moments about 0.5 (of a = x - 0.5, b = y - 0.5; the
+ *                  variances do not depend on the offset, mu_x = 0.5 + <a>); tests/image_metrics_ref.py bounds its rounding per position.
+ *   ssim_out[v]    fp64: the mean of the map over channels and valid positions
+ *   mse_out[v]     fp64: the mean of (x - y)^2 over ALL C H W elements of the view (the difference in fp32, its square and the sums in
+ *                  fp64); exactly 0 for identical images.  PSNR = -10 log10(mse) is left to the caller.
+ *   ssim_map       optional (NULL: not written): fp32 (V, C, H - 10, W - 10)
+ *   workspace      nerf_amd_image_metrics_workspace_bytes(V, C, H, W) bytes, 8-byte aligned, any content: one (SSIM sum, squared-difference
+ *                  sum) pair of fp64 per workgroup.  A workgroup walks one segment of one plane's map, NERF_AMD_IMAGE_METRICS_SEGMENT_H rows
+ *                  by _TILE_W columns, in tiles of _TILE_H rows.
+ * Two launches, no atomics, no host synchronisation, no allocation: the partials are added in a fixed order, so the outputs are a
+ * function of the inputs' bits alone, a view's values do not depend on the other views of the call, and the call can be captured into
+ * a graph.  V * C * H * W may exceed 2^31; V * C * segments must stay below 2^31.
+ * NERF_AMD_EINVAL (with a message): H or W < 11, a non-positive size, a NULL required pointer, too many segments. */
+#define NERF_AMD_IMAGE_METRICS_TILE_H 16
+#define NERF_AMD_IMAGE_METRICS_TILE_W 64
+#define NERF_AMD_IMAGE_METRICS_SEGMENT_H 128
+size_t nerf_amd_image_metrics_workspace_bytes(int64_t V, int C, int H, int W);
+int nerf_amd_image_metrics(const float* pred, const float* target, int64_t V, int C, int H, int W, double* mse_out, double* ssim_out,
+                           float* ssim_map, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

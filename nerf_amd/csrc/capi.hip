@@ -1325,4 +1325,23 @@ int nerf_amd_rows_to_bf16(const float* src, int64_t rows_src, int64_t src_stride
     return hip_status(rg_rows_to_bf16(src, rows_src, src_stride, rows, cols, fill, dst, dst_stride, S(stream)), "nerf_amd_rows_to_bf16");
 }
 
+static int check_image_metrics_shape(int64_t V, int C, int H, int W) {
+    if (V <= 0 || C <= 0 || H <= 0 || W <= 0) return fail(NERF_AMD_EINVAL, "nerf_amd_image_metrics: V, C, H, W must be positive");
+    if (H < 11 || W < 11) return fail(NERF_AMD_EINVAL, "nerf_amd_image_metrics: H and W must be at least 11 (the window; valid positions only)");
+    // (factor by factor: none of the products can overflow)
+    if (V > 0x7fffffffLL / C || im_workgroups(1, 1, H, W) > 0x7fffffffLL / (V * C)) return fail(NERF_AMD_EINVAL, "nerf_amd_image_metrics: too many segments (V * C * segments must stay below 2^31)");
+    return NERF_AMD_OK;
+}
+size_t nerf_amd_image_metrics_workspace_bytes(int64_t V, int C, int H, int W) {
+    if (check_image_metrics_shape(V, C, H, W)) return 0;
+    return (size_t)im_workgroups(V, C, H, W) * 2 * sizeof(double);
+}
+int nerf_amd_image_metrics(const float* pred, const float* target, int64_t V, int C, int H, int W, double* mse_out, double* ssim_out, float* ssim_map, void* workspace,
+                           void* stream) {
+    if (int e = check_image_metrics_shape(V, C, H, W)) return e;
+    if (!pred || !target || !mse_out || !ssim_out || !workspace) return fail(NERF_AMD_EINVAL, "nerf_amd_image_metrics: NULL argument (only ssim_map is optional)");
+    if (reinterpret_cast<uintptr_t>(workspace) & 7u) return fail(NERF_AMD_EINVAL, "nerf_amd_image_metrics: the workspace must be 8-byte aligned");
+    return hip_status(im_image_metrics(pred, target, V, C, H, W, mse_out, ssim_out, ssim_map, workspace, S(stream)), "nerf_amd_image_metrics");
+}
+
 }  // extern "C"

@@ -146,4 +146,10 @@ int gr_add_rows(float* dst, int64_t ldd, const float* src, int64_t lds_, int64_t
 int rg_rows_gemm(int64_t M, int64_t N, int64_t K, const void* X, int64_t ldx, const void* W, int64_t ldw, int64_t n_pad, const float* bias, int act, void* C, int64_t ldc, int out_bf16,
                  hipStream_t st);
 int rg_rows_to_bf16(const float* src, int64_t rows_src, int64_t lds, int64_t rows, int cols, int fill, void* dst, int64_t ldd, hipStream_t st);
+// ---- image_metrics_kernels.hip
+// workgroups (= fp64 pairs of workspace) of a call; H, W >= 11
+int64_t im_workgroups(int64_t V, int C, int H, int W);
+void im_window(float* g11);
+int im_image_metrics(const float* pred, const float* target, int64_t V, int C, int H, int W, double* mse_out, double* ssim_out, float* ssim_map, void* workspace,
+                     hipStream_t st);
 }  // namespace nk

@@ -392,10 +392,18 @@ def ipe_feature(z: torch.Tensor, rays: torch.Tensor, L: int, r: float, dir_norm:
     return feat, mu, mu_t
 
 
+def _pose_host(pose: torch.Tensor):
+    """the 12 values of the pose's first three rows as the host array the ray generators take: the list that rides on the tensor object
+    as ``_nerf_amd_host_pose`` when its uploader still held the values on the host (metrics.evaluate_views), else one read of the tensor"""
+    vals = getattr(pose, "_nerf_amd_host_pose", None)
+    vals = pose.detach().float().cpu().reshape(-1).tolist() if vals is None else [float(v) for v in vals]
+    return (C.c_float * 12)(*vals[:12])
+
+
 def generate_rays(pose: torch.Tensor, H: int, W: int, fx: float, fy: float, device, ray_offset: int = 0,
                   n: Optional[int] = None) -> torch.Tensor:
     n = H * W - ray_offset if n is None else n
-    host = (C.c_float * 12)(*pose.detach().float().cpu().reshape(-1).tolist()[:12])
+    host = _pose_host(pose)
     rays = torch.empty((n, 6), dtype=torch.float32, device=device)
     check(lib.nerf_amd_generate_rays(host, H, W, float(fx), float(fy), ray_offset, n, _ptr(rays), _stream()), "nerf_amd_generate_rays")
     return rays
@@ -405,7 +413,7 @@ def generate_camera_rays(pose: torch.Tensor, H: int, W: int, camera, device, ray
     """generate_rays for a ``nerf_amd.camera.Camera`` (principal point, lens distortion; nerf_amd_generate_rays_camera): rays (n, 6) of
     pixels ray_offset .. ray_offset + n - 1 in raster order.  ``Camera.reference(H, W, focal)`` gives generate_rays' bits."""
     n = H * W - ray_offset if n is None else n
-    host = (C.c_float * 12)(*pose.detach().float().cpu().reshape(-1).tolist()[:12])
+    host = _pose_host(pose)
     row = (C.c_float * 12)(*camera.row())
     rays = torch.empty((n, 6), dtype=torch.float32, device=device)
     check(lib.nerf_amd_generate_rays_camera(host, H, W, row, ray_offset, n, _ptr(rays), _stream()), "nerf_amd_generate_rays_camera")
@@ -1749,3 +1757,45 @@ def rows_gemm(x: torch.Tensor, layer: PackedLinear, act: int = 0, out: Optional[
                                  layer.bias.data_ptr(), int(act), out.data_ptr(), max(int(out.stride(0)), layer.N) if M > 1 else _pad(layer.N, 8),
                                  1 if out.dtype == torch.bfloat16 else 0, _stream()), "nerf_amd_rows_gemm")
     return out
+
+
+# ------------------------------------------------------------------------------------------------ image metrics
+IMAGE_METRICS_MIN_SIZE = 11                # the SSIM window: H and W of nerf_amd_image_metrics
+
+
+def _image_metrics_args(pred: torch.Tensor, target: torch.Tensor, who: str = "nerf_amd.image_metrics"):
+    """the checks of image_metrics, all ahead of any launch or allocation -> (V, C, H, W)"""
+    for name, t in (("pred", pred), ("target", target)):
+        if not isinstance(t, torch.Tensor):
+            raise ValueError("%s: '%s' must be a torch.Tensor (got %s)" % (who, name, type(t).__name__))
+        if t.dtype != torch.float32:
+            raise ValueError("%s: '%s' must be float32 (got %s)" % (who, name, t.dtype))
+        if t.dim() not in (3, 4):
+            raise ValueError("%s: '%s' must be (V, C, H, W) or (C, H, W) (got %s)" % (who, name, tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError("%s: '%s' must be contiguous (got strides %s for shape %s)" % (who, name, tuple(t.stride()), tuple(t.shape)))
+    if tuple(pred.shape) != tuple(target.shape):
+        raise ValueError("%s: pred and target must have one shape (got %s and %s)" % (who, tuple(pred.shape), tuple(target.shape)))
+    V, C_, H, W = ((1,) + tuple(pred.shape)) if pred.dim() == 3 else tuple(pred.shape)
+    if V < 1 or C_ < 1:
+        raise ValueError("%s: needs at least one view and one channel (got %s)" % (who, tuple(pred.shape)))
+    if H < IMAGE_METRICS_MIN_SIZE or W < IMAGE_METRICS_MIN_SIZE:
+        raise ValueError("%s: H and W must be at least %d, the SSIM window (got %d x %d); there is no padding" % (who, IMAGE_METRICS_MIN_SIZE, H, W))
+    if not (pred.is_cuda and target.is_cuda) or pred.device != target.device:      # (last: the checks above need no device to be exercised)
+        raise ValueError("%s: pred and target must live on one HIP device (got %s and %s); there is no CPU path" % (who, pred.device, target.device))
+    return V, C_, H, W
+
+
+def image_metrics(pred: torch.Tensor, target: torch.Tensor, *, want_map: bool = False):
+    """(mse, ssim[, ssim_map]) of fp32 device images (V, C, H, W) -- (C, H, W) is one view -- by nerf_amd_image_metrics (include/nerf_amd.h):
+    mse (V,) fp64, the mean of (pred - target)^2 over each view; ssim (V,) fp64, the mean over channels and VALID positions of the
+    11 x 11 Gaussian (sigma 1.5) SSIM with L = 1; ssim_map (V, C, H - 10, W - 10) fp32 when asked for.  Two launches on the current
+    stream, nothing read back, no atomics: equal inputs give equal bits, whatever else shares the call."""
+    V, C_, H, W = _image_metrics_args(pred, target)
+    dev = pred.device
+    mse = torch.empty((V,), dtype=torch.float64, device=dev)
+    ssim = torch.empty((V,), dtype=torch.float64, device=dev)
+    smap = torch.empty((V, C_, H - 10, W - 10), dtype=torch.float32, device=dev) if want_map else None
+    ws = torch.empty((int(lib.nerf_amd_image_metrics_workspace_bytes(V, C_, H, W)) // 8,), dtype=torch.float64, device=dev)
+    check(lib.nerf_amd_image_metrics(_ptr(pred), _ptr(target), V, C_, H, W, _ptr(mse), _ptr(ssim), _ptr(smap), _ptr(ws), _stream()), "nerf_amd_image_metrics")
+    return (mse, ssim, smap) if want_map else (mse, ssim)

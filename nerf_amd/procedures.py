@@ -208,6 +208,21 @@ def _check_spacing(spacing, near, far) -> bool:
     return True
 
 
+_COARSE_DEPTHS = {}
+
+
+def _coarse_depths(near, far, dev) -> torch.Tensor:
+    """the coarse depths of render_image, torch.linspace(near, far, 64) evaluated on the CPU (the reference's bits) and uploaded ONCE per
+    (near, far, device): a constant that every later call reads -- a test set's views do not upload it again (and do not wait for it)"""
+    key = (float(near), float(far), str(dev), RENDER_COARSE_PNUM)
+    z = _COARSE_DEPTHS.get(key)
+    if z is None:
+        if len(_COARSE_DEPTHS) >= 64:
+            _COARSE_DEPTHS.clear()
+        z = _COARSE_DEPTHS[key] = torch.linspace(near, far, RENDER_COARSE_PNUM, device="cpu").to(dev)
+    return z
+
+
 def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Tensor, image_size, focal,
                  near: float, far: float, sample_num: int = 128, white_bkg: bool = False, render_depth=False,
                  render_normal=False, rng: str = "philox", contract: bool = False, ipe=False, seed: Optional[int] = None,
@@ -303,11 +318,14 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
     network._check_config()
     prop_net._check_config()
     prec = ops.current_precision()
+    pose_rows = render_pose[:3]
+    if getattr(render_pose, "_nerf_amd_host_pose", None) is not None:             # the pose's values, where its uploader kept them (metrics.evaluate_views):
+        pose_rows._nerf_amd_host_pose = render_pose._nerf_amd_host_pose           # they ride on to the ray generator, which then reads nothing back
     if camera is not None:
         fx, fy = camera.fx, camera.fy
-        rays = ops.generate_camera_rays(render_pose[:3], H, W, camera, dev)         # (H*W, 6), raster order
+        rays = ops.generate_camera_rays(pose_rows, H, W, camera, dev)              # (H*W, 6), raster order
     else:
-        rays = ops.generate_rays(render_pose[:3], H, W, fx, fy, dev)               # (H*W, 6), raster order
+        rays = ops.generate_rays(pose_rows, H, W, fx, fy, dev)                     # (H*W, 6), raster order
     sz, patch_num = get_patch_size((H, W))
     if sz is not None:                                                             # reorder rays tile by tile
         pr, pc = patch_num
@@ -328,7 +346,7 @@ def render_image(network: NeRF, prop_net: ProposalNetwork, render_pose: torch.Te
     if _shard is not None:
         off = int(_shard[0])
         rays = rays[off: int(_shard[1])].contiguous()
-    z_base = torch.linspace(near, far, RENDER_COARSE_PNUM, device="cpu").to(dev)   # procedures.py:52 (CPU linspace bits)
+    z_base = _coarse_depths(near, far, dev)                                        # procedures.py:52 (CPU linspace bits)
     normal_px = None
     ipe_radius = None
     if ipe:
@@ -439,6 +457,10 @@ def render_only(args, model_path: str, opt_level: str, dataset_root: str = "../d
     mip_net.eval()
     prop_net.eval()
     low_precision = bool(args.use_scaler) or args.opt_mode == "native"
+    eval_ssim = bool(eval_poses and getattr(args, "eval_ssim", False))            # an addition: off -> every line and PNG below is what it was
+    if eval_ssim:
+        from .metrics import image_metrics
+        view_metrics = []
     with torch.no_grad():
         for i, pose in tqdm(list(enumerate(all_poses))):
             pose = pose.clone()
@@ -450,9 +472,16 @@ def render_only(args, model_path: str, opt_level: str, dataset_root: str = "../d
                 gt_img = testset[i][0].cuda()
                 loss = loss_func(result["rgb"], gt_img)
                 print("Image loss:%.6f\tPSNR:%.4f" % (loss.item(), psnr_func(loss).item()))
+                if eval_ssim:
+                    m = image_metrics(result["rgb"].float().contiguous(), gt_img.float().contiguous())
+                    view_metrics.append(torch.stack((m["psnr"][0], m["ssim"][0])))
+                    print("Image SSIM:%.6f" % m["ssim"][0].item())
                 result["gt_img"] = gt_img
             save_image(list(result.values()), "%s%s/result_%03d.png" % (output_root, "given" if eval_poses else "sphere", i),
                        nrow=1 + render_depth + render_depth + eval_poses)                  # (the reference counts render_depth twice)
+    if eval_ssim and view_metrics:
+        mean_psnr, mean_ssim = torch.stack(view_metrics).mean(0).tolist()          # means of the per-view values (the papers' convention)
+        print("Test set (%d views): mean PSNR:%.4f\tmean SSIM:%.6f" % (len(view_metrics), mean_psnr, mean_ssim))
 
 
 def get_parser():
@@ -491,6 +520,7 @@ def get_parser():
     ):
         p.add_argument(short, long_, default=False, action="store_true", help=hlp)
     for long_, hlp in (("--render_depth", "Render depth image"), ("--render_normal", "Render normal image"),
-                       ("--prop_normal", "(For proposal net) Whether to learn normals")):
+                       ("--prop_normal", "(For proposal net) Whether to learn normals"),
+                       ("--eval_ssim", "(Render only; an addition) with -e: print each view's SSIM too, and the test set's mean PSNR and mean SSIM")):
         p.add_argument(long_, default=False, action="store_true", help=hlp)
     return p
