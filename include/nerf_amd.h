@@ -879,6 +879,58 @@ size_t nerf_amd_image_metrics_workspace_bytes(int64_t V, int C, int H, int W);
 int nerf_amd_image_metrics(const float* pred, const float* target, int64_t V, int C, int H, int W, double* mse_out, double* ssim_out,
                            float* ssim_map, void* workspace, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Iso-surface extraction (additive; the ABI number stays): a triangle mesh of { f = iso } from a lattice of field values (for a NeRF:
+ * the density), by marching tetrahedra on the Kuhn split of every cell into six tetrahedra.  The build's own definition (nothing of the
+ * kind is in the reference); tests/mesh_ref.py restates it in fp64 without a case table.
+ *
+ *   field      contiguous fp32 (nz, ny, nx), x fastest; every dimension >= 2, nx * ny * nz < 2^31.  Lattice point (i, j, k) has the
+ *              linear index p = (k ny + j) nx + i and the position origin + spacing * (i, j, k) (component-wise).
+ *   inside     a point is inside when f >= iso, on the fp32 values; a NaN is outside.
+ *   edges      every point a owns 7 edge slots s = 0..6 with direction d = ((s+1) & 1, ((s+1) >> 1) & 1, ((s+1) >> 2) & 1): the three axis
+ *              edges, the three face diagonals and the body diagonal, all towards +.  The edge a -> b = a + d exists if b is in the
+ *              lattice and carries a vertex if inside(a) != inside(b).
+ *   vertices   numbered in ascending (p, s).  t = (iso - f_a) / (f_b - f_a) in fp32 (two subtractions, one division), a non-finite t
+ *              becomes 0.5 (so +-inf entries still give finite positions), else t is clamped to [0, 1]; always measured from the owner a.
+ *              position = origin + spacing * (a + t d), per component: fl(a + t) where d is 1, one multiplication, one addition.
+ *   normals    optional.  g = the central difference of the field at a and at b, one-sided on the lattice's faces:
+ *              (f[hi] - f[lo]) / (spacing (hi - lo)) per axis.  n = -normalize((1 - t) g_a + t g_b); a zero or non-finite vector is
+ *              stored as (0, 0, 0).  The normal points from high values to low, like the winding.
+ *   cells      named by their lowest corner p (i < nx-1, j < ny-1, k < nz-1).  The six tetrahedra are the axis permutations (a1, a2, a3) in
+ *              lexicographic order xyz, xzy, yxz, yzx, zxy, zyx, with corners v0 = the cell's corner, v1 = v0 + e_a1, v2 = v1 + e_a2,
+ *              v3 = v2 + e_a3.  Every tetrahedron edge is one of the 7 slot directions from its component-wise lower end, which owns it.
+ *   triangles  of one tetrahedron, with I the inside local corners ascending, O the outside ones, E(u, w) the vertex on edge u-w:
+ *                  |I| = 1: a = I0, (b, c, d) = O:   (E(a,b), E(a,c), E(a,d))
+ *                  |I| = 3: a = O0, (b, c, d) = I:   the same expression
+ *                  |I| = 2: (a, b) = I, (c, d) = O:  (E(a,c), E(a,d), E(b,d)) then (E(a,c), E(b,d), E(b,c))
+ *   winding    the 2nd and 3rd entry of a triangle are swapped when needed so that, with every crossing placed at the MIDPOINT of its edge,
+ *              (p1 - p0) x (p2 - p0) has a positive dot product with (mean of the outside corners - mean of the inside corners): an exact
+ *              integer test on lattice coordinates, independent of t and therefore of ties f == iso.  A closed iso-surface comes out
+ *              closed and consistently oriented: there are no ambiguous faces.
+ *   faces      int32 vertex ids, ordered by ascending (cell p, tetrahedron, triangle).
+ *
+ * Two calls, with the caller reading the counts in between (the pair is therefore not capturable into a graph):
+ *   nerf_amd_mesh_count   classifies every point (one byte: the crossed slots and the inside flag; the later passes do not read the
+ *                         field to classify), counts vertices and triangles per tile of 256 points, scans the tiles and stores
+ *                         counts_dev[0] = vertices, counts_dev[1] = faces (device, int64).
+ *   nerf_amd_mesh_emit    with the SAME field, shape, iso and workspace: stores vertices (V, 3) fp32, normals (V, 3) fp32 unless NULL, and
+ *                         faces (F, 3) int32.  Every store is guarded by vertex_capacity / face_capacity (in vertices / faces): with
+ *                         capacities below the counts the first entries are written and nothing beyond them.  origin_host and
+ *                         spacing_host are three floats each on the host.
+ *   workspace             nerf_amd_mesh_workspace_bytes(nx, ny, nz) bytes (0: the shape is refused), about 5 bytes per point: the byte,
+ *                         and one int32 per point -- the id of its first vertex; the id of (p, s) is that plus the number of crossed
+ *                         slots below s.  Any content on entry to nerf_amd_mesh_count.
+ * No atomics: wave scans, popcounts and one scan of the tile counts; the outputs are a function of the inputs' bits alone.
+ * NERF_AMD_EINVAL (with a message), before any launch: a NULL pointer (only normals is optional; vertices / faces may be NULL with a zero
+ * capacity), a dimension < 2, nx * ny * nz >= 2^31, a non-finite iso or origin, a spacing that is not positive and finite, a capacity that
+ * is negative or would let a vertex id or 3 * faces reach 2^31. */
+#define NERF_AMD_MESH_SCAN_STEP_TILES 4096 /* tiles of 256 points per step of the one workgroup that scans the tile counts */
+size_t nerf_amd_mesh_workspace_bytes(int nx, int ny, int nz);
+int nerf_amd_mesh_count(const float* field, int nx, int ny, int nz, float iso, int64_t* counts_dev, void* workspace, void* stream);
+int nerf_amd_mesh_emit(const float* field, int nx, int ny, int nz, float iso, const float* origin_host, const float* spacing_host,
+                       void* workspace, int64_t vertex_capacity, int64_t face_capacity, float* vertices, float* normals, int32_t* faces,
+                       void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,7 @@ class Samples(C.Structure):
 
 IMAGE_METRICS_TILE = (16, 64)   # NERF_AMD_IMAGE_METRICS_TILE_H, _TILE_W: the SSIM map tile of nerf_amd_image_metrics
 IMAGE_METRICS_SEGMENT_H = 128   # NERF_AMD_IMAGE_METRICS_SEGMENT_H: map rows (a whole number of tiles) that one workgroup walks
+MESH_SCAN_STEP_TILES = 4096     # NERF_AMD_MESH_SCAN_STEP_TILES: tiles of 256 lattice points per step of nerf_amd_mesh_count's tile scan
 DEPTH_QUANTILES_MAX = 4   # NERF_AMD_DEPTH_QUANTILES_MAX: quantiles per nerf_amd_ray_depth_stats / nerf_amd_render call
 
 
@@ -182,6 +183,9 @@ SIGNATURES = {
     "nerf_amd_rows_to_bf16": (C.c_int, [c_void, i64, i64, i64, C.c_int, C.c_int, c_void, i64, c_void]),
     "nerf_amd_image_metrics_workspace_bytes": (C.c_size_t, [i64, C.c_int, C.c_int, C.c_int]),
     "nerf_amd_image_metrics": (C.c_int, [c_void, c_void, i64, C.c_int, C.c_int, C.c_int, c_void, c_void, c_void, c_void, c_void]),
+    "nerf_amd_mesh_workspace_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_int]),
+    "nerf_amd_mesh_count": (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_float, c_void, c_void, c_void]),
+    "nerf_amd_mesh_emit": (C.c_int, [c_void, C.c_int, C.c_int, C.c_int, C.c_float, c_float_p, c_float_p, c_void, i64, i64, c_void, c_void, c_void, c_void]),
 }
 
 
@@ -189,7 +193,8 @@ SIGNATURES = {
 ADDED_AFTER_125 = ("nerf_amd_direction_table", "nerf_amd_render_rounds_workspace_bytes", "nerf_amd_render_rays_rounds",
                    "nerf_amd_ipe_feature_gaussian", "nerf_amd_ray_depth_stats", "nerf_amd_render_request_workspace_bytes", "nerf_amd_render",
                    "nerf_amd_ray_alive_workspace_bytes", "nerf_amd_ray_alive", "nerf_amd_gather_rows", "nerf_amd_generate_rays_camera",
-                   "nerf_amd_sample_scene_rays_camera", "nerf_amd_image_metrics_workspace_bytes", "nerf_amd_image_metrics")
+                   "nerf_amd_sample_scene_rays_camera", "nerf_amd_image_metrics_workspace_bytes", "nerf_amd_image_metrics",
+                   "nerf_amd_mesh_workspace_bytes", "nerf_amd_mesh_count", "nerf_amd_mesh_emit")
 
 
 def _load():

@@ -1344,4 +1344,34 @@ int nerf_amd_image_metrics(const float* pred, const float* target, int64_t V, in
     return hip_status(im_image_metrics(pred, target, V, C, H, W, mse_out, ssim_out, ssim_map, workspace, S(stream)), "nerf_amd_image_metrics");
 }
 
+static int check_mesh_shape(const char* name, int nx, int ny, int nz) {
+    if (nx < 2 || ny < 2 || nz < 2) return fail(NERF_AMD_EINVAL, "%s: every dimension of the lattice must be at least 2", name);
+    if ((int64_t)nx * ny > 0x7fffffffLL / nz) return fail(NERF_AMD_EINVAL, "%s: nx * ny * nz must stay below 2^31 (points are ranked in int32)", name);
+    return NERF_AMD_OK;
+}
+static bool finite_f(float x) { return x - x == 0.0f; }
+size_t nerf_amd_mesh_workspace_bytes(int nx, int ny, int nz) { return check_mesh_shape("nerf_amd_mesh_workspace_bytes", nx, ny, nz) ? 0 : mesh_workspace_bytes(nx, ny, nz); }
+int nerf_amd_mesh_count(const float* field, int nx, int ny, int nz, float iso, int64_t* counts_dev, void* workspace, void* stream) {
+    if (int e = check_mesh_shape("nerf_amd_mesh_count", nx, ny, nz)) return e;
+    if (!finite_f(iso)) return fail(NERF_AMD_EINVAL, "nerf_amd_mesh_count: iso must be finite");
+    if (!field || !counts_dev || !workspace) return fail(NERF_AMD_EINVAL, "nerf_amd_mesh_count: NULL argument");
+    return hip_status(mesh_count(field, nx, ny, nz, iso, counts_dev, workspace, S(stream)), "nerf_amd_mesh_count");
+}
+int nerf_amd_mesh_emit(const float* field, int nx, int ny, int nz, float iso, const float* origin_host, const float* spacing_host, void* workspace,
+                       int64_t vertex_capacity, int64_t face_capacity, float* vertices, float* normals, int32_t* faces, void* stream) {
+    if (int e = check_mesh_shape("nerf_amd_mesh_emit", nx, ny, nz)) return e;
+    if (!finite_f(iso)) return fail(NERF_AMD_EINVAL, "nerf_amd_mesh_emit: iso must be finite");
+    if (!field || !origin_host || !spacing_host || !workspace) return fail(NERF_AMD_EINVAL, "nerf_amd_mesh_emit: NULL argument");
+    for (int c = 0; c < 3; ++c) {
+        if (!finite_f(origin_host[c])) return fail(NERF_AMD_EINVAL, "nerf_amd_mesh_emit: origin must be finite");
+        if (!(spacing_host[c] > 0.0f) || !finite_f(spacing_host[c])) return fail(NERF_AMD_EINVAL, "nerf_amd_mesh_emit: spacing must be positive and finite");
+    }
+    if (vertex_capacity < 0 || face_capacity < 0) return fail(NERF_AMD_EINVAL, "nerf_amd_mesh_emit: negative capacity");
+    if (vertex_capacity > 0x7fffffffLL || face_capacity > 0x7fffffffLL / 3)
+        return fail(NERF_AMD_EINVAL, "nerf_amd_mesh_emit: the vertex count and three times the face count must stay below 2^31 (indices are int32)");
+    if ((vertex_capacity && !vertices) || (face_capacity && !faces)) return fail(NERF_AMD_EINVAL, "nerf_amd_mesh_emit: NULL output with a non-zero capacity");
+    return hip_status(mesh_emit(field, nx, ny, nz, iso, origin_host, spacing_host, workspace, vertex_capacity, face_capacity, vertices, normals, faces, S(stream)),
+                      "nerf_amd_mesh_emit");
+}
+
 }  // extern "C"

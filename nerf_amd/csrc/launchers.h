@@ -152,4 +152,10 @@ int64_t im_workgroups(int64_t V, int C, int H, int W);
 void im_window(float* g11);
 int im_image_metrics(const float* pred, const float* target, int64_t V, int C, int H, int W, double* mse_out, double* ssim_out, float* ssim_map, void* workspace,
                      hipStream_t st);
+// ---- mesh_kernels.hip
+// marching tetrahedra on an (nz, ny, nx) lattice; dimensions >= 2, nx * ny * nz < 2^31 (checked by the caller); origin, spacing: host
+size_t mesh_workspace_bytes(int nx, int ny, int nz);
+int mesh_count(const float* field, int nx, int ny, int nz, float iso, int64_t* counts_dev, void* workspace, hipStream_t st);
+int mesh_emit(const float* field, int nx, int ny, int nz, float iso, const float* origin, const float* spacing, void* workspace, int64_t vertex_capacity,
+              int64_t face_capacity, float* vertices, float* normals, int32_t* faces, hipStream_t st);
 }  // namespace nk

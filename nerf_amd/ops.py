@@ -1799,3 +1799,71 @@ def image_metrics(pred: torch.Tensor, target: torch.Tensor, *, want_map: bool = 
     ws = torch.empty((int(lib.nerf_amd_image_metrics_workspace_bytes(V, C_, H, W)) // 8,), dtype=torch.float64, device=dev)
     check(lib.nerf_amd_image_metrics(_ptr(pred), _ptr(target), V, C_, H, W, _ptr(mse), _ptr(ssim), _ptr(smap), _ptr(ws), _stream()), "nerf_amd_image_metrics")
     return (mse, ssim, smap) if want_map else (mse, ssim)
+
+
+# ------------------------------------------------------------------------------------------------ iso-surface extraction
+def _mesh_args(field: torch.Tensor, iso, origin, spacing, who: str):
+    """the checks of the mesh calls, all ahead of any launch or allocation -> (nx, ny, nz, iso, origin[3], spacing[3]) as Python numbers"""
+    if not isinstance(field, torch.Tensor):
+        raise ValueError("%s: 'field' must be a torch.Tensor (got %s)" % (who, type(field).__name__))
+    if field.dtype != torch.float32:
+        raise ValueError("%s: 'field' must be float32 (got %s)" % (who, field.dtype))
+    if field.dim() != 3:
+        raise ValueError("%s: 'field' must be (nz, ny, nx) (got %s)" % (who, tuple(field.shape)))
+    if not field.is_contiguous():
+        raise ValueError("%s: 'field' must be contiguous (got strides %s for shape %s)" % (who, tuple(field.stride()), tuple(field.shape)))
+    nz, ny, nx = (int(v) for v in field.shape)
+    if min(nx, ny, nz) < 2:
+        raise ValueError("%s: every dimension of the lattice must be at least 2 (got %s)" % (who, tuple(field.shape)))
+    if nx * ny * nz >= 2 ** 31:
+        raise ValueError("%s: nx * ny * nz must stay below 2^31 (got %s)" % (who, tuple(field.shape)))
+    iso = float(iso)
+    if not math.isfinite(iso) or not math.isfinite(C.c_float(iso).value):
+        raise ValueError("%s: iso must be finite in float32 (got %r)" % (who, iso))
+    vec = []
+    for name, v in (("origin", origin), ("spacing", spacing)):
+        v = tuple(float(x) for x in v)
+        if len(v) != 3 or not all(math.isfinite(C.c_float(x).value) for x in v):
+            raise ValueError("%s: '%s' must be three finite numbers (got %r)" % (who, name, v))
+        vec.append(v)
+    if not all(C.c_float(x).value > 0.0 for x in vec[1]):
+        raise ValueError("%s: every spacing must be positive in float32 (got %r)" % (who, vec[1]))
+    if not field.is_cuda:                                   # (last: the checks above need no device to be exercised)
+        raise ValueError("%s: 'field' must live on the HIP device (got %s); there is no CPU path" % (who, field.device))
+    return nx, ny, nz, iso, vec[0], vec[1]
+
+
+def _mesh_refuse_capture(who: str):
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError("%s reads the vertex and face counts on the host between its two calls: not on a capturing stream" % who)
+
+
+def mesh_count(field: torch.Tensor, iso: float):
+    """nerf_amd_mesh_count on an fp32 device field (nz, ny, nx) -> (counts (2,) int64 on the device: vertices, faces; the workspace that
+    mesh_emit continues from).  Nothing is read back here."""
+    nx, ny, nz, iso, _, _ = _mesh_args(field, iso, (0.0, 0.0, 0.0), (1.0, 1.0, 1.0), "nerf_amd.mesh_count")
+    _mesh_refuse_capture("nerf_amd.mesh_count")
+    counts = torch.empty((2,), dtype=torch.int64, device=field.device)
+    ws = torch.empty((int(lib.nerf_amd_mesh_workspace_bytes(nx, ny, nz)),), dtype=torch.uint8, device=field.device)
+    check(lib.nerf_amd_mesh_count(_ptr(field), nx, ny, nz, iso, _ptr(counts), _ptr(ws), _stream()), "nerf_amd_mesh_count")
+    return counts, ws
+
+
+def mesh_emit(field: torch.Tensor, iso: float, workspace: torch.Tensor, n_vertices: int, n_faces: int, *, origin=(0.0, 0.0, 0.0), spacing=(1.0, 1.0, 1.0),
+              normals: bool = True):
+    """nerf_amd_mesh_emit behind mesh_count (same field, iso and workspace), with the counts the caller read -> (vertices (V,3) fp32,
+    faces (F,3) int32, normals (V,3) fp32 or None)"""
+    nx, ny, nz, iso, origin, spacing = _mesh_args(field, iso, origin, spacing, "nerf_amd.mesh_emit")
+    n_vertices, n_faces = int(n_vertices), int(n_faces)
+    if n_vertices < 0 or n_faces < 0 or n_vertices >= 2 ** 31 or 3 * n_faces >= 2 ** 31:
+        raise ValueError("nerf_amd.mesh_emit: the vertex count and three times the face count must stay below 2^31 (got %d vertices, %d faces)" % (n_vertices, n_faces))
+    dev = field.device
+    vertices = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev)
+    faces = torch.empty((n_faces, 3), dtype=torch.int32, device=dev)
+    nrm = torch.empty((n_vertices, 3), dtype=torch.float32, device=dev) if normals else None
+    if n_vertices == 0 and n_faces == 0:
+        return vertices, faces, nrm                         # an empty surface: no emit pass
+    o3, s3 = (C.c_float * 3)(*origin), (C.c_float * 3)(*spacing)
+    check(lib.nerf_amd_mesh_emit(_ptr(field), nx, ny, nz, iso, o3, s3, _ptr(workspace), n_vertices, n_faces, _ptr(vertices), _ptr(nrm), _ptr(faces), _stream()),
+          "nerf_amd_mesh_emit")
+    return vertices, faces, nrm

@@ -482,6 +482,14 @@ def render_only(args, model_path: str, opt_level: str, dataset_root: str = "../d
     if eval_ssim and view_metrics:
         mean_psnr, mean_ssim = torch.stack(view_metrics).mean(0).tolist()          # means of the per-view values (the papers' convention)
         print("Test set (%d views): mean PSNR:%.4f\tmean SSIM:%.6f" % (len(view_metrics), mean_psnr, mean_ssim))
+    mesh_path = getattr(args, "mesh", None)                                        # an addition: without it nothing above or below changes
+    if mesh_path:
+        from .mesh import extract_mesh, write_ply
+        box = [float(v) for v in args.mesh_aabb]
+        with torch.autocast("cuda", dtype=torch.bfloat16, enabled=low_precision):
+            mesh = extract_mesh(mip_net, (box[:3], box[3:]), args.mesh_res, args.mesh_iso, colors=True)
+        write_ply(mesh_path, mesh["vertices"], mesh["faces"], mesh["normals"], mesh["colors"])
+        print("Mesh: %d vertices, %d faces (iso %g, %d^3 lattice) -> %s" % (mesh["vertices"].shape[0], mesh["faces"].shape[0], args.mesh_iso, args.mesh_res, mesh_path))
 
 
 def get_parser():
@@ -523,4 +531,10 @@ def get_parser():
                        ("--prop_normal", "(For proposal net) Whether to learn normals"),
                        ("--eval_ssim", "(Render only; an addition) with -e: print each view's SSIM too, and the test set's mean PSNR and mean SSIM")):
         p.add_argument(long_, default=False, action="store_true", help=hlp)
+    # (Render only; additions) the density field's iso-surface as a PLY.  The defaults are conveniences for the Blender scenes, not measured choices.
+    p.add_argument("--mesh", type=str, default=None, help="(Render only; an addition) also write the iso-surface of the fine network's density to this PLY file")
+    p.add_argument("--mesh_res", type=int, default=256, help="Lattice points per axis of the mesh extraction")
+    p.add_argument("--mesh_iso", type=float, default=10.0, help="Density level of the extracted surface")
+    p.add_argument("--mesh_aabb", type=float, nargs=6, default=[-1.5, -1.5, -1.5, 1.5, 1.5, 1.5], metavar=("x0", "y0", "z0", "x1", "y1", "z1"),
+                   help="Box that the mesh lattice spans")
     return p
