@@ -413,7 +413,10 @@ int nerf_amd_interlevel_loss_backward(const float* w, const float* t, const floa
  * in practice). */
 int nerf_amd_mfma_stream(int iters, int workgroups, int mode, float* sink, void* stream);
 
-/* getBounds (addtional.py:14-18): w_prop (N,C), below (N,K) int64 -> bounds (N,K-1). */
+/* getBounds (addtional.py:14-18): w_prop (N,C), below (N,K) int64 -> bounds (N,K-1).
+ * bounds_k = sat[below_{k+1} + 1] - sat[below_k] over the summed-area row sat[0 .. C] of w_prop.  Every entry of `below` must lie in
+ * 0 ... C - 1 (what the resampling kernels emit), sorted or not; like the reference's torch.gather, which raises outside that range, the
+ * forward kernel does not clamp, and an index outside it reads outside the row.  nerf_amd_get_bounds_backward has the same contract. */
 int nerf_amd_get_bounds(const float* w_prop, const int64_t* below, int64_t N, int C, int K, float* bounds, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
