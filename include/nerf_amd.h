@@ -83,6 +83,13 @@ int         nerf_amd_device_info(int* n_cu, int* arch_is_gfx950);
  *                                   (H/2-row+.5)/fy, -1) generated in-kernel for ray n = row*W + col
  *                                   (procedures.py:43-51)
  * M = total samples = N*S in modes 1/2.
+ * ARGUMENT DOMAIN OF THE ENCODING (a contract of every entry point that encodes a position: the MLP forwards and renders,
+ * nerf_amd_positional_encoding, nerf_amd_ipe_feature*, nerf_amd_encode_rows): the octave-(L-1) argument 2^(L-1) x of every ENCODED
+ * coordinate must satisfy |2^(L-1) x| <= 2^21, i.e. |x| <= 4096 at L = 10 -- with disparity spacing out to far = 1000 and |d| <= 3 the
+ * largest argument is 1.54e6.  Inside the domain each sine / cosine is within 4 * 2^-24 of the exact function of the fp32 argument
+ * (tests/encoding_ref.py); beyond it the range reduction loses accuracy gradually and nothing is promised.  With the scene contraction
+ * on, the encoded coordinate is the contracted one (|x| < 2): any finite position is inside the domain.  No field of this descriptor
+ * bounds far or |d|, so keeping un-contracted scenes inside the domain is the caller's part.
  * ------------------------------------------------------------------------------------------------ */
 #define NERF_AMD_CONTRACT_GAUSSIAN 2 /* nerf_amd_samples.contract: contract the frustum mean AND its covariance (integrated PE) */
 typedef struct nerf_amd_samples {

@@ -41,9 +41,9 @@ own rounding:
     a / b:   e = (e_a + |a / b| e_b) / (|b| - e_b)     + 5 u (|v| + e) + 2^-126        (2.5 ulp: the bound forward_ref.py uses)
     sqrt a:  e = e_a / (sqrt(max(a - e_a, 0)) + sqrt a) + 4 u (|v| + e)                (2 ulp)
     2^j a:   exact
-    sin, cos a:  e = e_a + 4 u     1-Lipschitz; the Cody-Waite reduction (device_common.h sin_quadrant) rounds twice, <= 2^-25 each, its
-                                   constants' truncation is k 2^-72, and the two fdlibm kernels evaluated in fp32 stay within 1.5 ulp of a
-                                   result <= 1 (3 u): 4 u in all, for |a| <= 2^15 (here |a| <= 2^9 . 2)
+    sin, cos a:  e = e_a + max(4 u, D(|a|))     1-Lipschitz, plus the error of device_common.h sin_quadrant at an argument of that size.
+                                   D is derived operation by operation below (SIN_QUADRANT); D <= 4 u for |a| <= 2^21, so the constant
+                                   4 u this module has always used stands there (here |a| <= 2^9 . 2) and D takes over beyond
     exp a (a <= 0):  e = e_a exp(v + e_a) + 6 u exp(v + e_a)       mean value theorem with the LARGER of the two exponentials; 3 ulp
                                    (forward_ref.py's figure for expf)
 
@@ -71,13 +71,45 @@ than fp64 does, so the GPU tests assert that their inputs have none (`sphere_gap
 
 THE COMPARATOR (`compare`): max(err / tol) over every element of feat and mu', and -- because inside the unit ball the Gaussian mode must
 return the bits of contract = 1, which no tolerance can see -- the number of elements of inside-ball frusta whose bits differ from the
-metric twin's.  None of these is fitted to what the kernels produce."""
+metric twin's.  None of these is fitted to what the kernels produce.
+
+SIN_QUADRANT (`sincos_abs`): the error of sin_quadrant / sincos_quadrant (device_common.h) as a function of the argument's size.  With
+q = |a| 2 / pi (a real number), u = 2^-24:
+  k = rint(fl(a c0)), c0 = fl(2 / pi) = (2 / pi) (1 + e0), e0 = -4.0342e-8; the product rounds once, so |fl(a c0) - a 2 / pi| <= ETA q with
+      ETA = |e0| + u + |e0| u < 1.0e-7, and rint moves it by at most 1/2:   |a 2 / pi - k| <= 1/2 + ETA q.
+      Near a half-integer of a 2 / pi, k can therefore be the OTHER neighbour: the reduced argument r = a - k pi / 2 is then no longer
+      inside [-pi/4, pi/4] but inside |r| <= R(q) = (pi / 2) (1/2 + ETA q): 0.7887 at |a| = 2^15, 0.995 at |a| = 2^21.
+  r1 = fma(-k, C1, a), C1 = fl(pi / 2) = m 2^-23:  EXACT.  For |a| >= 1, a and k C1 are multiples of 2^-23 and |a - k C1| <= R + |k| |pi/2 - C1|
+      (4.38e-8 |k|) < 2, so the difference has at most 24 bits; for |a| < 1, k is 0 (r1 = a) or +-1 (|a| >= 0.78: a multiple of 2^-24 minus a
+      multiple of 2^-23, below 1 in size).  This holds while R(q) + 4.38e-8 |k| < 2, i.e. for |k| < 6.0e6 -- far beyond the domain below.
+  r2 = fma(-k, C2, r1), r3 = fma(-k, C3, r2):  each rounds once, |delta| <= u |exact| <= u R (1 + 2^-20)   (|k C3| <= 2^21 . 1.8e-15).
+  C1 + C2 + C3 = pi / 2 - rho, |rho| = 1.06e-23 < 2^-72 (exact rational arithmetic on the three literals, re-done in
+      tests/test_encoding_ref_host.py): r3 = (a - k pi / 2) + k rho + delta2 + delta3, |k| <= q (1 + ETA) + 1/2.
+  z = fl(r r);  sine: five fma for ps (|ps| <= 1/6, its error <= 2 u / 6 with room), w = fl(r z) (2 u relative), s = fma(w, ps, r):
+      |s - P_s(r)| <= 2 u |r|^3 / 6 + |r|^3 2 u / 6 + u |s| <= u (|sin r| + 0.67 |r|^3);
+      cosine: zz = fl(z z) (3 u relative), five fma for pc (|pc| <= 1/24, error <= 2 u / 24), h = fma(-1/2, z, 1) (u r^2 / 2 + u |h|, and
+      |h| = 1 - r^2 / 2 for |r| <= 1.2), c = fma(zz, pc, h):   |c - P_c(r)| <= u (1 + |cos r| + 0.21 r^4).
+  P_s, P_c: the two polynomials with their fp32 coefficients against sin and cos on |r| <= 1.2, evaluated in fp64 on two million points
+      (a property of the coefficients, not of a kernel): 0.126 u and 0.042 u; allowed POLY_APPROX = 0.25 u.
+  The quadrant selects +-s or +-c exactly.  Both |r|-dependent sums grow with |r|, so with R' = R(q) (1 + 2^-20):
+      D(|a|) = u (2 R' + max(1 + cos R' + 0.21 R'^4, sin R' + 0.67 R'^3) + 0.25) + (q (1 + ETA) + 1/2) 2^-72
+  = 3.61 u at |a| = 2^15 (the range device_common.h documents), 3.88 u at 1.54e6 = 2^9 . 1000 . 3 (disparity spacing to far = 1000, |d| = 3,
+  no contraction) and 3.99 u at 2^21; just beyond, it passes 4 u.  SINCOS_DOMAIN = 2^21 is the range over which this derivation is used
+  as a PROOF (R(2^21) = 0.995 lies inside the |r| <= 1.2 of the polynomial sup): `sincos_abs` refuses a larger argument.  No descriptor
+  field bounds far or |d|, so the domain is a contract of the entry points: include/nerf_amd.h states it."""
+import math
+
 import torch
 
 U = 2.0 ** -24
 TINY = 2.0 ** -126
 BF16_HALF_ULP = 2.0 ** -8
 DIV_U, SQRT_U, EXP_U, SINCOS_ABS = 5 * U, 4 * U, 6 * U, 4 * U
+SINCOS_ETA = 4.0342060334366545e-08 * (1 + U) + U      # |fl(a c0) - a 2 / pi| <= SINCOS_ETA |a| 2 / pi
+SINCOS_RHO = 2.0 ** -72                                # >= |pi / 2 - C1 - C2 - C3|
+SINCOS_DOMAIN = 2.0 ** 21                              # the largest |a| for which sincos_abs is a proof
+POLY_APPROX = 0.25 * U                                 # >= sup |P(r) - sin / cos r| on |r| <= POLY_RANGE (measured 0.126 u, 0.042 u)
+POLY_RANGE = 1.2
 FIVE_TWELFTHS_F32 = 0.4166666567325592          # the constant of the reference's fp32 arithmetic (the specification uses 5 / 12)
 
 
@@ -129,14 +161,15 @@ def lift(mu, var, L):
 
 def spec(z, rays, L, r2, dn, mode="gaussian"):
     """z (N,S+1), rays (N,6) fp32 (CPU), r2 = the fp32 square of the pixel radius, dn = the fp32 direction norm the kernel read.
-    -> feat (N,S,6L), mu' (N,S,3), var' (N,S,3) in fp64.  mode: "gaussian" (the definition above) or "metric" (contract = 1)."""
+    -> feat (N,S,6L), mu' (N,S,3), var' (N,S,3) in fp64.  mode: "gaussian" (the definition above), "metric" (contract = 1) or "plain"
+    (contract = 0: the reference's ipe_feature, neither mean nor covariance contracted)."""
     x, diag, var_t, var_r, d = gaussian(z, rays, r2, dn)
     var = diag
     if mode == "gaussian":
         outside = x.norm(dim=-1, keepdim=True) > 1
         safe = torch.where(outside, x, torch.full_like(x, 2.0))
         var = torch.where(outside, pushed_variance(safe, d, var_t, var_r, dn), diag)
-    mu = contract(x)
+    mu = x if mode == "plain" else contract(x)
     return lift(mu, var, L), mu, var
 
 
@@ -250,12 +283,32 @@ def fma(a, b, c):
     return a._rounded(a.v * b.v + c.v, a.v.abs() * b.e + b.v.abs() * a.e + a.e * b.e + c.e, U)
 
 
+def sincos_reduced_range(mag):
+    """R(q) of SIN_QUADRANT: the bound on |a - k pi / 2| for an argument of size mag (a float64 tensor)"""
+    return (math.pi / 2) * (0.5 + SINCOS_ETA * mag * (2 / math.pi))
+
+
+def sincos_derived(mag):
+    """D(|a|) of SIN_QUADRANT (module docstring) for an argument of size mag <= SINCOS_DOMAIN"""
+    q = mag * (2 / math.pi)
+    R = sincos_reduced_range(mag) * (1 + 2.0 ** -20)
+    poly = torch.maximum(1 + torch.cos(R) + 0.21 * R ** 4, torch.sin(R) + 0.67 * R ** 3)
+    return U * (2 * R + poly) + POLY_APPROX + (q * (1 + SINCOS_ETA) + 0.5) * SINCOS_RHO
+
+
+def sincos_abs(a):
+    """the bound on |sin_quadrant(computed a) - sin(computed a)|: the constant 4 u wherever the derivation stays below it"""
+    mag = a.v.abs() + a.e
+    assert bool((mag <= SINCOS_DOMAIN).all()), "an argument of sin_quadrant beyond 2^21: outside the range the bound is derived for"
+    return sincos_derived(mag).clamp_min(SINCOS_ABS)
+
+
 def fl_sin(a):
-    return Fl(torch.sin(a.v), a.e + SINCOS_ABS)
+    return Fl(torch.sin(a.v), a.e + sincos_abs(a))
 
 
 def fl_cos(a):
-    return Fl(torch.cos(a.v), a.e + SINCOS_ABS)
+    return Fl(torch.cos(a.v), a.e + sincos_abs(a))
 
 
 def fl_exp(a):
@@ -278,12 +331,15 @@ def fl_moments(z, r2):
 
 
 def fl_gaussian(z, rays, r2, dn, mode):
-    """-> (mu', var') as Fl of shape (N,S,3): the operations of cone_moments, cone_mean_cov and the contracted Gaussian, in their order"""
+    """-> (mu', var') as Fl of shape (N,S,3): the operations of cone_moments, cone_mean_cov and the contracted Gaussian, in their order.
+    mode "plain": cone_mean_cov's values as they are (contract = 0)"""
     mu_t, var_t, var_r = fl_moments(z, r2)
     o, d, dn = Fl(rays[:, None, :3].double()), Fl(rays[:, None, 3:6].double()), Fl(float(dn))
     x = o + mu_t * d
     dd = d * d
     diag = var_t * dd + var_r * (Fl(1.0) - dd / dn)
+    if mode == "plain":                                                                  # no contraction at all
+        return x, diag
     xs = [Fl(x.v[..., c: c + 1], x.e[..., c: c + 1]) for c in range(3)]
     ds = [Fl(d.v[..., c: c + 1]) for c in range(3)]
     n = ((xs[0] * xs[0] + xs[1] * xs[1]) + xs[2] * xs[2]).sqrt()
