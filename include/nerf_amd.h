@@ -251,7 +251,18 @@ int nerf_amd_sigma_to_weights(const float* sigma, const float* z, const float* d
 int nerf_amd_max_blur(const float* w, int64_t N, int S, float alpha, float* out, void* stream);
 
 /* inverseSample (utils.py:34-44) + sample_pdf (utils.py:108-133) with the uniforms explicit:
- * w (N,C), z (N,C), u (N,K) -> z_out (N,K) [sorted when sort!=0], below (N,K) int64 (NULL to skip). C <= 256. */
+ * w (N,C), z (N,C), u (N,K) -> z_out (N,K) [sorted when sort!=0], below (N,K) int64 (NULL to skip). C <= 256.
+ * The sampling contract, which this entry, nerf_amd_sample_pdf and every fused resampling entry (nerf_amd_resample,
+ * nerf_amd_warped_resample, the render requests) share:
+ *   cdf        [0 | cumsum((w + 1e-5) / sum(w + 1e-5))] in fp32, bit for bit torch's CPU result (the sum in ATen's order, the running sum
+ *              in fp64 rounded per element); inds = #{j: cdf[j] <= u} (searchsorted, right=True)
+ *   indices    below = max(inds - 1, 0), above = min(inds, nb - 1), nb = the number of bin edges; u >= cdf[nb - 1] gives below == above
+ *   sample     bins[below] + t (bins[above] - bins[below]), t = (u - cdf[below]) / d, d = cdf[above] - cdf[below], d < 1e-5 -> 1;
+ *              separate fp32 operations in this order, IEEE division
+ *   sort != 0  the samples ASCENDING BY VALUE for every input -- the stable sort of the raw fp32 samples, like torch.sort -- and
+ *              `below` permuted with them (equal values may come in any order).  Over ascending bin edges that is the order of the
+ *              uniforms except where a sample exceeds its bin's upper edge by an ulp of fp32 rounding; such rays, and rays whose bin
+ *              edges descend, are sorted by value all the same. */
 int nerf_amd_inverse_sample(const float* w, const float* z, const float* u, int64_t N, int C, int K, int sort,
                             float* z_out, int64_t* below, void* stream);
 

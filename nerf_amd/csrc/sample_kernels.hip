@@ -572,10 +572,16 @@ DEVINL void wave_inverse_sample(const float* pw, const float* bins, int nw, floa
     }
     if (!sort) return;
     lds_wave_sync();
-    // Sort.  The inverse CDF is monotone, so the order of the samples is the order of their uniforms: bucket the
-    // elements by floor(u * 256) (LDS atomics hand out the slot inside a bucket), prefix-sum the bucket counts, and rank
-    // every element against the <= SORT_CAP members of its own bucket only.  Adversarial inputs (a bucket holding more
-    // than SORT_CAP elements) fall back to the O(K^2) stable rank sort; both give the same sorted values.
+    // Sort BY VALUE, like torch.sort.  Inside one bin every fp32 operation of the interpolation is monotone in u and a bin's samples
+    // start at its lower edge b0, so over ascending bin edges the order of the samples is the order of their uniforms AS LONG AS no
+    // sample exceeds its own upper edge b1.  In fp32 one can: for u one ulp below cdf[above], t rounds to 1 and b0 + fl(b1 - b0)
+    // exceeds b1 by an ulp when the width b1 - b0 is not exact, while the next uniform, on the edge, gives b1 itself -- a descent, and
+    // across a bucket boundary one that the bucket sort would keep.  Where the width IS exact (0 <= b0 <= b1 <= 2 b0, or the mirror
+    // image below zero: Sterbenz) t <= 1 gives fl(t w) <= w and b0 + fl(t w) <= b1.  So: a ray none of whose bins is `risky` is sorted
+    // by its uniforms -- bucket the elements by floor(u * 256) (LDS atomics hand out the slot inside a bucket), prefix-sum the bucket
+    // counts, and rank every element against the <= SORT_CAP members of its own bucket only -- and a ray with risky bins first looks
+    // for a sample above its upper edge among the samples of those bins.  Such a ray, and a ray with more than SORT_CAP elements in
+    // one bucket, takes the O(K^2) stable rank sort; both sorts give the same sorted values.
     int* cnt = sortbuf;
     int* pre = sortbuf + SORT_NB;
     unsigned short* mem = reinterpret_cast<unsigned short*>(sortbuf + 2 * SORT_NB);
@@ -583,8 +589,20 @@ DEVINL void wave_inverse_sample(const float* pw, const float* bins, int nw, floa
     lds_wave_sync();
     // (the order-of-uniforms argument needs ascending bin edges; a ray whose edges are not -- unsorted depths passed to inverseSample,
     // or stratified depths whose jitter exceeds the bin spacing -- takes the rank sort below, which sorts the VALUES like torch.sort)
-    int overflow = 0;
-    for (int j = lane; j + 1 < nb; j += 64) overflow |= (bins[j + 1] < bins[j]) ? 1 : 0;
+    int overflow = 0, risky = -1;                 // risky: this lane's last bin whose width is not exact in fp32
+    for (int j = lane; j + 1 < nb; j += 64) {
+        const float b0 = bins[j], b1 = bins[j + 1];
+        overflow |= (b1 < b0) ? 1 : 0;
+        const bool exact = b0 >= 0.0f ? (b1 <= 2.0f * b0 || b0 == 0.0f) : (b1 <= 0.0f && b0 >= 2.0f * b1);
+        if (!exact) risky = j;
+    }
+    if (__any(risky >= 0)) {                      // (never on metric depths a factor of two apart at most; bin 0 under disparity spacing)
+        risky = wave_max_i(risky);
+        for (int k = lane; k < K; k += 64) {
+            const int bl = bel[k];                // bl <= risky < nb - 1: the upper edge is bins[bl + 1]
+            if (bl <= risky) overflow |= (samp[k] > bins[bl + 1]) ? 1 : 0;
+        }
+    }
     for (int k = lane, i = 0; k < K; k += 64, ++i) {
         int b = (int)(uf(i, k) * (float)SORT_NB);
         b = b < 0 ? 0 : (b > SORT_NB - 1 ? SORT_NB - 1 : b);
