@@ -489,6 +489,9 @@ int nerf_amd_encode_rows(const float* x, int x_stride, int64_t M, int L, int nor
  *      by grad_scale first (1 = plain; 1/world_size after a summing all-reduce).  lr / betas / eps are doubles like torch's Python
  *      scalars (the bias corrections 1 - beta^step are formed in double, as torch does); a non-NULL lr_dev (one double on the device)
  *      overrides lr when the kernel runs, so that a captured graph follows a learning-rate schedule.
+ *      grad_scale multiplies every gradient element once, in fp32, before anything else reads it: both moments are formed from
+ *      g * grad_scale (exp_avg_sq from its square), and `grads` itself is not written.  The device step counter is an fp32 incremented
+ *      by 1.0f per call (once per call, however many table launches the tensor list takes), so it is exact up to 2^24 steps.
  * Gradients w.r.t. the sample positions are not produced (the reference detaches them for these two networks).
  * ------------------------------------------------------------------------------------------------ */
 size_t nerf_amd_packed_backward_bytes(int net, int precision);
