@@ -392,7 +392,11 @@ int nerf_amd_weighted_dot_loss_backward(const float* g, const float* w, const fl
  *   mode 1  Mip-NeRF 360 L_dist (Barron et al. 2022, eq. 15): w (N, S - 1), t = the S sorted interval edges, m_i = interval midpoints:
  *           out[0] = scale / N * sum_n ( sum_ij w_i w_j |m_i - m_j|  +  sum_i w_i^2 (t_i+1 - t_i) / 3 )
  * workspace: NERF_AMD_DISTORTION_WORKSPACE_FLOATS floats.  Backward: g = d loss / d out (ONE float in device memory) -> d_w (the shape of w),
- * d_t (N, S); either may be NULL (not computed).  sgn(0) = 0 in the gradient of |x|, as torch. */
+ * d_t (N, S); either may be NULL (not computed).  sgn(0) = 0 in the gradient of |x|, as torch: intervals whose centres tie bit for bit
+ * (zero-width intervals from repeated depths) exchange no |x| gradient.  g and scale are multiplied in on the device (in fp64); out[0]
+ * does not contain g.  A ray all of whose centres coincide: mode 0 stores NaN in every column of THAT ray's rows of d_w and d_t (and
+ * out[0] is NaN), every other ray's rows are unaffected; mode 1 stores exact zeros in its d_w row and the widths' part in d_t.  A
+ * gradient entry all of whose terms are exact zeros (zero weights) is stored as an exact zero.  (tests/test_gpu_regularizers.py) */
 #define NERF_AMD_DISTORTION_MAX_S 1024
 #define NERF_AMD_DISTORTION_WORKSPACE_FLOATS 4096
 int nerf_amd_distortion_loss(const float* w, const float* t, int64_t N, int S, int mode, float scale, float* out, float* workspace, void* stream);
@@ -415,7 +419,12 @@ int nerf_amd_distortion_loss_backward(const float* w, const float* t, int64_t N,
  * Backward: g = d loss / d out (ONE float in device memory) -> d_w_prop (N, K):
  *   d_w_prop[j] = g scale sum_{i : lo(t_i) <= j < hi(t_i+1)} -2 relu(w_i - bound_i) / (w_i + 1e-8)
  * -- the i of one j are a contiguous range (t_i < e_j+1 and t_i+1 >= e_j): two binary searches and a difference of an fp64 prefix sum,
- * no atomics.  The loss is piecewise constant in the edges and w is a constant: there is no other gradient. */
+ * no atomics.  The loss is piecewise constant in the edges and w is a constant: there is no other gradient.
+ * Settled by tests/test_gpu_regularizers.py: bounds_out of a fine interval outside a closed proposal span is the exact 0 (hi = lo: one
+ * prefix entry minus itself), elsewhere the fp32 rounding of an fp64 difference of prefix sums (absolute error ~1e-16 of the row's total
+ * weight, which is what a bound ten decades below the total carries); a fine edge that equals a proposal edge bit for bit counts on both
+ * sides (`<=` in lo, `>` in hi); d_w_prop[j] of a proposal interval that no fine interval touches is the stored constant 0; a row of M
+ * coincident fine edges is M zero-width intervals, nothing special; g and scale are multiplied in on the device, out[0] does not contain g. */
 #define NERF_AMD_INTERLEVEL_MAX 1024
 #define NERF_AMD_INTERLEVEL_WORKSPACE_FLOATS 2048
 int nerf_amd_interlevel_loss(const float* w, const float* t, const float* w_prop, const float* t_prop, int64_t N, int M, int K, int Kp, float scale,
